@@ -10,6 +10,13 @@ projection+SH -> tile binning -> radix sort -> compositing forward -> fused L1-R
 N > 1 (launched by torch.distributed.run): every rank holds the full Gaussian set and renders its
 own camera (yawed by 5 degrees * rank); gradients are summed with one all-reduce of the flat 59 N
 float buffer; weak scaling (per-GPU work fixed).
+
+A plain run sets up, warms up, times the K steps (replayed from a captured hipGraph at N = 1) and prints the result line.
+--full adds everything beyond the headline: the instrumented per-kernel region and the roofline figures, per-step
+percentiles, the list lengths of the reference and after the timed steps, the reference-shaped route and the CPU
+baseline.  --dump-outputs DIR then replays the timed step DUMP_STEPS times from the initial scene and writes what the
+last replay computed (its losses, and its gradients and the updated parameters on a fixed sample of Gaussians) as
+DIR/<name>.npy, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -24,6 +31,11 @@ sys.path.insert(0, ROOT)
 # committed rocprofv3 --pmc summaries the roofline objects quote (re-taken whenever the compositing kernels change)
 PMC_TRAFFIC = "r05_hbm_traffic_pmc.json"
 PMC_VALU = "r05_valu_issue_pmc.json"
+# --dump-outputs: steps replayed from the initial scene, rows of the sample (59 parameter + at most 59 gradient floats
+# each: 31 MB at most)
+DUMP_STEPS = 2
+DUMP_ROWS = 65536
+DUMP_SEED = 0
 
 import torch  # noqa: E402
 
@@ -54,8 +66,8 @@ def parse():
     ap.add_argument("--gaussians", type=int, default=500_000)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-api-path", action="store_true", help="skip timing the reference-shaped eager route")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-api-path", action="store_true", help="--full: skip timing the reference-shaped eager route")
     ap.add_argument("--cpu-sample-div", type=int, default=4, help="CPU sample = config / div^2 (area and N)")
     ap.add_argument("--sync-m", action="store_true", help="read the intersection count back every step")
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
@@ -76,6 +88,14 @@ def parse():
     ap.add_argument("--graph-split", action="store_true",
                     help="capture forward+backward and the Adam step as two graphs with the gradient all-reduce "
                          "between them (the default for N > 1; this flag forces it at N = 1 for testing)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the instrumented per-kernel region and roofline, "
+                         "per-step percentiles, list lengths, the reference-shaped route and the CPU baseline (the last two "
+                         "can still be left out with --no-api-path / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help=f"after the timed steps, replay the timed step {DUMP_STEPS} times from the initial scene and write "
+                         "what the last replay computed as DIR/<name>.npy: its losses (float64), and its gradients and the "
+                         f"updated parameters of a fixed, seeded sample of {DUMP_ROWS} Gaussians (float32)")
     return ap.parse_args()
 
 
@@ -87,6 +107,29 @@ def make_scene(n, w, h, rank, dev):
     sc["camera_to_worlds"] = sc["camera_to_worlds"][rank:rank + 1]
     sc["Ks"] = sc["Ks"][rank:rank + 1]
     return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in sc.items()}
+
+
+def dump_outputs(path, losses, model, grads):
+    """--dump-outputs: what a caller of the timed step receives -- ``losses`` as <name>.npy (float64, shape [1]), the
+    step's gradients ``grads`` (name -> per-Gaussian tensor) as grad_<name>.npy and the model's current parameters as
+    param_<group>.npy (float32), both on the rows of sample_rows.npy (float64 indices): all Gaussians up to DUMP_ROWS,
+    else a fixed sample drawn with DUMP_SEED."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(path, f"{k}.npy"), v.detach().reshape(-1).to("cpu", torch.float64).numpy())
+    n = model.num_points
+    if n > DUMP_ROWS:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(DUMP_SEED))[:DUMP_ROWS].sort().values
+    else:
+        rows = torch.arange(n)
+    np.save(os.path.join(path, "sample_rows.npy"), rows.to(torch.float64).numpy())
+    idx = rows.to(model.device)
+    for name in model.group_names:
+        p = model.gauss_params[name].detach()
+        np.save(os.path.join(path, f"param_{name}.npy"), p[idx].to("cpu", torch.float32).numpy())
+    for name, g in grads.items():
+        np.save(os.path.join(path, f"grad_{name}.npy"), g.detach()[idx].to("cpu", torch.float32).numpy())
 
 
 def cpu_baseline(args, m_full=None):
@@ -501,9 +544,9 @@ def main():
 
     # The unit count of SURVEY 8(d) is the length of the REFERENCE's list (gsplat's 3-sigma squares); the tight
     # lists this run uses are a subset that renders the same image.  One un-timed forward gives that length
-    # (then the intersection-buffer capacity is re-calibrated for the lists actually used).
+    # (then the intersection-buffer capacity is re-calibrated for the lists actually used).  --full only.
     M_ref = None
-    if cfg.tight_tile_lists:
+    if args.full and cfg.tight_tile_lists:
         from qed_splatter_amd.rasterization import _workspace
         cfg.tight_tile_lists = False
         with torch.no_grad():
@@ -534,23 +577,26 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    barrier()
-    L.TIMER.reset()
-    L.TIMER.active = (rank == 0)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(args.sync_m)
-    barrier()
-    dt = time.perf_counter() - t0
-    L.TIMER.active = False
-    if dist is not None:
-        t = torch.tensor([dt], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t)
-    kern = L.TIMER.summary()
-    log(f"instrumented region: {dt / args.steps * 1e3:.3f} ms/step")
+    # --full: K eager steps with a HIP event pair around every entry point (kernels_ms, roofline)
+    kern, dt = {}, None
+    if args.full:
+        barrier()
+        L.TIMER.reset()
+        L.TIMER.active = (rank == 0)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step(args.sync_m)
+        barrier()
+        dt = time.perf_counter() - t0
+        L.TIMER.active = False
+        if dist is not None:
+            t = torch.tensor([dt], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t)
+        kern = L.TIMER.summary()
+        log(f"instrumented region: {dt / args.steps * 1e3:.3f} ms/step")
 
-    # a second, un-instrumented timed region gives the headline number (event records cost host time).
+    # an un-instrumented timed region gives the headline number (event records cost host time).
     # Default at N = 1: the whole step replayed from one captured hipGraph (same kernels, same work;
     # only the host dispatch cost is removed).  --no-graph times eager dispatch instead.
     # N > 1: forward+backward and the Adam step are captured as TWO graphs and the RCCL all-reduce of the
@@ -756,11 +802,36 @@ def main():
         t = torch.tensor([dt2], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt2 = float(t)
+    if args.dump_outputs:
+        # What the timed step computes, from inputs that are the same run after run: DUMP_STEPS replays of it from the
+        # initial scene.  The state after the W + K timed steps is not reproducible: the compositing backward sums each
+        # Gaussian's per-tile partial gradients with float atomics in whatever order the tiles finish, and training
+        # amplifies those last-bit differences (parameters: 1 ulp after one step, ~1e-2 after 25; the loss ~1e-4 after
+        # 220).  Past the first step, so that the Adam update depends on the gradients' sizes and not on their signs
+        # alone; the gradients themselves are written too (Adam's update is blind to a per-coordinate scale of them).
+        from qed_splatter_amd.model import _raw_grad
+        for _ in range(3):
+            restore()
+            for _ in range(DUMP_STEPS):
+                out_last = run()                       # (every rank: the data-parallel step issues collectives)
+            if replays_had_room():                     # (an overflowed replay trained on an empty frame)
+                break
+        else:
+            raise SystemExit("bench: the --dump-outputs replays kept overflowing the intersection buffer")
+        if rank == 0:
+            # (compact SH gradients: features_dc's field holds the clamp-masked colour gradient, features_rest's is not
+            # written -- the optimiser expands the SH gradients itself)
+            grads = {("colors" if k == "features_dc" and dp_compact else k): _raw_grad(model.gauss_params[k])
+                     for k in model.group_names if not (k == "features_rest" and dp_compact)
+                     and _raw_grad(model.gauss_params[k]) is not None}
+            # (the split forms' run_ returns nothing: their losses are the forward+backward graph's static outputs)
+            dump_outputs(args.dump_outputs, out_last if out_last else graphs[0].outputs, model, grads)
+            log(f"outputs of {DUMP_STEPS} replays of the timed step from the initial scene written to {args.dump_outputs}")
 
     # per-step spread (median and p10/p90): a third, short region with a HIP event between
     # consecutive steps -- kept out of the headline region, which contains nothing but the steps
     pct = None
-    if world == 1:
+    if world == 1 and args.full:
         n_ev = min(max(args.steps, 20), 100)
         rewind()
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_ev + 1)]
@@ -774,64 +845,18 @@ def main():
                "p90": round(per[int(0.9 * (n_ev - 1))], 4), "steps": n_ev}
 
     # list length after W + K steps of training (the scene drifts; config.intersections is the first step's)
-    rewind()
-    for _ in range(args.steps):
-        run()
-    with torch.no_grad():
-        model.fused_loss(cam, batch, background=bg, sync=True)
-    M_end = int(model.info["n_isects"])
+    M_end = None
+    if args.full:
+        rewind()
+        for _ in range(args.steps):
+            run()
+        with torch.no_grad():
+            model.fused_loss(cam, batch, background=bg, sync=True)
+        M_end = int(model.info["n_isects"])
 
     if rank == 0:
         ms_step = dt2 / args.steps * 1e3
         n_px = w * h
-        # dominant kernel = compositing backward; algorithmic bytes: 92 B per list entry the launch
-        # processed + 28 B per pixel.  The list shrinks as training proceeds (config.intersections ->
-        # intersections_after_timed_steps), so the mean of the two ends of the run is used.
-        dom = "qed_composite_bwd"
-        dom_ms = kern.get(dom, (0, float("nan")))[1]
-        M_proc = 0.5 * (M + M_end)
-        alg_bytes = 92.0 * M_proc + 28.0 * n_px
-        achieved = alg_bytes / (dom_ms * 1e-3) / 1e9
-        # Counter-derived figures of that kernel come from COMMITTED rocprofv3 --pmc passes (FETCH_SIZE and WRITE_SIZE
-        # cannot share a pass and counters cannot be read from inside this process): valid only for this workload and
-        # for the kernel version named in the profile; null otherwise.
-        traffic = valu_frac = prof_note = None
-        if (n, w, h) == (500_000, 1920, 1080):
-            prof, vp = committed_counters(PMC_TRAFFIC), committed_counters(PMC_VALU)
-            try:
-                if prof is not None:
-                    kk = prof["kernels"]["qed::composite_bwd_kernel<4>"]
-                    traffic = (2.0 * kk["fetch_size_kb"] + kk["write_size_kb"]) * 1024.0    # gfx950: FETCH_SIZE counts half
-                if vp is not None:
-                    valu_frac = vp["kernels"]["qed::composite_bwd_kernel<4>"]["valu_issue_frac"]
-                if prof is not None or vp is not None:
-                    prof_note = f"from committed profiles {PMC_TRAFFIC} / {PMC_VALU} (kernels " \
-                                f"{(prof or vp).get('kernels_version', '?')}; source hashes match this tree), not measured in this run"
-                else:
-                    prof_note = f"{PMC_TRAFFIC} / {PMC_VALU} were taken on other kernel sources (sha256 mismatch): not quoted"
-            except (KeyError, TypeError):
-                pass
-        roof = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": prof_note,
-                "algorithmic_bytes_per_launch": alg_bytes, "list_entries_per_launch": M_proc,
-                "list_entries_reference": M_ref, "kernel_ms": dom_ms,
-                "kernel_ms_covers": "HIP events on the launch stream around the qed_composite_bwd ENTRY POINT, eager: the "
-                                    "one-workgroup ordering launch (tile_order_kernel, ~10 us) + composite_bwd_kernel + the two "
-                                    "event records; the rocprofv3 kernel trace of the same command lists the two kernels "
-                                    "separately (profiles/r05_bench_kernel_stats_v3.txt: 9.8 + 276.1 us on that box)",
-                # the same launch priced on the list the REFERENCE operator would have walked for this image (SURVEY 8d's
-                # unit is gsplat's intersection): a shorter list for the same image lowers `frac` while the kernel gets
-                # faster, so both are given; `achieved` / `frac` stay on what the launch really processed
-                "frac_at_reference_list": (92.0 * M_ref * (M_proc / max(M, 1)) + 28.0 * n_px) / (dom_ms * 1e-3) / 1e9 / 8000.0,
-                "note": "algorithmic bytes = 92 B x (list entries this launch processed) + 28 B x pixels (SURVEY 8d).  The "
-                        "reference (gsplat) would list list_entries_reference entries for the same image; this run lists "
-                        "only the tiles in which some pixel can reach alpha >= 1/255 (exact per-tile test).  The kernel is "
-                        "not HBM bound (see roofline_issue): measured traffic is BELOW the algorithmic bytes because culled "
-                        "/ early-terminated entries are never gathered."}
-        roof_issue = {"bound": "valu_issue", "kernel": dom, "frac": valu_frac, "source": prof_note,
-                      "definition": "SQ_ACTIVE_INST_VALU / (SIMDs x GRBM_GUI_ACTIVE / 8 / 4) quad-cycles; a wave64 "
-                                    "cross-lane op (v_readlane 11.5, v_permlane*_swap 8.4, DPP 4.3 cycles) occupies the "
-                                    "pipe several times longer than a plain op (2.2-2.5): DESIGN.md section 4"}
         out = {
             "metric": "train iters/sec @ 1080p, 500k Gaussians (fwd + loss + bwd + Adam; camera-steps/s over all GPUs)",
             "value": world * args.steps / dt2, "unit": "iters/s", "n_gpus": world, "steps": args.steps,
@@ -839,8 +864,9 @@ def main():
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{n} Gaussians, SH deg 3, {world} cam(s) @ {w}x{h}, 1 per GPU, fwd+bwd with "
                                    f"depth-L1 + (0.8 L1 + 0.2 (1-SSIM)) RGB loss + fused Adam",
-                       "gaussians": n, "visible": n_vis, "intersections": M, "intersections_after_timed_steps": M_end,
-                       "intersections_reference_list": M_ref,
+                       "gaussians": n, "visible": n_vis, "intersections": M,
+                       **({"intersections_after_timed_steps": M_end, "intersections_reference_list": M_ref}
+                          if args.full else {}),
                        "forward_launch_order": "costliest tiles first, from the work counts of the PREVIOUS frame of the same "
                                                "camera (frame_key; a scheduling hint: images and gradients unchanged; "
                                                "QED_BENCH_FRAME_KEY=0 turns it off: raster order + quadrant tail)"
@@ -858,27 +884,78 @@ def main():
                        # timed again: see replays_had_room)
                        "intersection_overflows": ws.overflows - overflows_before},
             "msplats_per_s": n_vis * world / (dt2 / args.steps) / 1e6,
-            # Msplats rasterized / s = N_visible / t_fwd (t_fwd = projection + binning + compositing
-            # forward, HIP-event sums of the instrumented region), the list rate M / t_fwd, and the step rate
-            # with the optimiser launch left out
-            "forward_ms": round(sum(kern.get(k, (0, 0.0))[1] for k in
-                                    ("qed_camera_setup", "qed_project_fwd", "qed_bin_tiles", "qed_composite_fwd")), 4),
-            "msplats_per_s_forward": n_vis / max(sum(kern.get(k, (0, 0.0))[1] for k in
-                                                     ("qed_camera_setup", "qed_project_fwd", "qed_bin_tiles",
-                                                      "qed_composite_fwd")), 1e-9) / 1e3,
-            "mintersections_per_s_forward": M_ref / max(sum(kern.get(k, (0, 0.0))[1] for k in
-                                                            ("qed_camera_setup", "qed_project_fwd", "qed_bin_tiles",
-                                                             "qed_composite_fwd")), 1e-9) / 1e3,
-            "iters_per_s_without_optimizer": world * 1e3 / max(ms_step - max(kern.get("qed_adam_step", (0, 0.0))[1],
-                                                                                      kern.get("qed_adam_step_sh", (0, 0.0))[1]), 1e-9),
-            "ms_per_step_instrumented": dt / args.steps * 1e3,
-            "ms_per_step_percentiles": pct,
-            "kernels_ms": {k: round(v[1], 4) for k, v in sorted(kern.items())},
-            "roofline": roof,
-            "roofline_issue": roof_issue,
         }
+        if args.full:
+            # dominant kernel = compositing backward; algorithmic bytes: 92 B per list entry the launch
+            # processed + 28 B per pixel.  The list shrinks as training proceeds (config.intersections ->
+            # intersections_after_timed_steps), so the mean of the two ends of the run is used.
+            dom = "qed_composite_bwd"
+            dom_ms = kern.get(dom, (0, float("nan")))[1]
+            M_proc = 0.5 * (M + M_end)
+            alg_bytes = 92.0 * M_proc + 28.0 * n_px
+            achieved = alg_bytes / (dom_ms * 1e-3) / 1e9
+            # Counter-derived figures of that kernel come from COMMITTED rocprofv3 --pmc passes (FETCH_SIZE and WRITE_SIZE
+            # cannot share a pass and counters cannot be read from inside this process): valid only for this workload and
+            # for the kernel version named in the profile; null otherwise.
+            traffic = valu_frac = prof_note = None
+            if (n, w, h) == (500_000, 1920, 1080):
+                prof, vp = committed_counters(PMC_TRAFFIC), committed_counters(PMC_VALU)
+                try:
+                    if prof is not None:
+                        kk = prof["kernels"]["qed::composite_bwd_kernel<4>"]
+                        traffic = (2.0 * kk["fetch_size_kb"] + kk["write_size_kb"]) * 1024.0    # gfx950: FETCH_SIZE counts half
+                    if vp is not None:
+                        valu_frac = vp["kernels"]["qed::composite_bwd_kernel<4>"]["valu_issue_frac"]
+                    if prof is not None or vp is not None:
+                        prof_note = f"from committed profiles {PMC_TRAFFIC} / {PMC_VALU} (kernels " \
+                                    f"{(prof or vp).get('kernels_version', '?')}; source hashes match this tree), not measured in this run"
+                    else:
+                        prof_note = f"{PMC_TRAFFIC} / {PMC_VALU} were taken on other kernel sources (sha256 mismatch): not quoted"
+                except (KeyError, TypeError):
+                    pass
+            roof = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                    "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": prof_note,
+                    "algorithmic_bytes_per_launch": alg_bytes, "list_entries_per_launch": M_proc,
+                    "list_entries_reference": M_ref, "kernel_ms": dom_ms,
+                    "kernel_ms_covers": "HIP events on the launch stream around the qed_composite_bwd ENTRY POINT, eager: the "
+                                        "one-workgroup ordering launch (tile_order_kernel, ~10 us) + composite_bwd_kernel + the two "
+                                        "event records; the rocprofv3 kernel trace of the same command lists the two kernels "
+                                        "separately (profiles/r05_bench_kernel_stats_v3.txt: 9.8 + 276.1 us on that box)",
+                    # the same launch priced on the list the REFERENCE operator would have walked for this image (SURVEY 8d's
+                    # unit is gsplat's intersection): a shorter list for the same image lowers `frac` while the kernel gets
+                    # faster, so both are given; `achieved` / `frac` stay on what the launch really processed
+                    "frac_at_reference_list": (92.0 * M_ref * (M_proc / max(M, 1)) + 28.0 * n_px) / (dom_ms * 1e-3) / 1e9 / 8000.0,
+                    "note": "algorithmic bytes = 92 B x (list entries this launch processed) + 28 B x pixels (SURVEY 8d).  The "
+                            "reference (gsplat) would list list_entries_reference entries for the same image; this run lists "
+                            "only the tiles in which some pixel can reach alpha >= 1/255 (exact per-tile test).  The kernel is "
+                            "not HBM bound (see roofline_issue): measured traffic is BELOW the algorithmic bytes because culled "
+                            "/ early-terminated entries are never gathered."}
+            roof_issue = {"bound": "valu_issue", "kernel": dom, "frac": valu_frac, "source": prof_note,
+                          "definition": "SQ_ACTIVE_INST_VALU / (SIMDs x GRBM_GUI_ACTIVE / 8 / 4) quad-cycles; a wave64 "
+                                        "cross-lane op (v_readlane 11.5, v_permlane*_swap 8.4, DPP 4.3 cycles) occupies the "
+                                        "pipe several times longer than a plain op (2.2-2.5): DESIGN.md section 4"}
+            out.update({
+                # Msplats rasterized / s = N_visible / t_fwd (t_fwd = projection + binning + compositing
+                # forward, HIP-event sums of the instrumented region), the list rate M / t_fwd, and the step rate
+                # with the optimiser launch left out
+                "forward_ms": round(sum(kern.get(k, (0, 0.0))[1] for k in
+                                        ("qed_camera_setup", "qed_project_fwd", "qed_bin_tiles", "qed_composite_fwd")), 4),
+                "msplats_per_s_forward": n_vis / max(sum(kern.get(k, (0, 0.0))[1] for k in
+                                                         ("qed_camera_setup", "qed_project_fwd", "qed_bin_tiles",
+                                                          "qed_composite_fwd")), 1e-9) / 1e3,
+                "mintersections_per_s_forward": M_ref / max(sum(kern.get(k, (0, 0.0))[1] for k in
+                                                                ("qed_camera_setup", "qed_project_fwd", "qed_bin_tiles",
+                                                                 "qed_composite_fwd")), 1e-9) / 1e3,
+                "iters_per_s_without_optimizer": world * 1e3 / max(ms_step - max(kern.get("qed_adam_step", (0, 0.0))[1],
+                                                                                          kern.get("qed_adam_step_sh", (0, 0.0))[1]), 1e-9),
+                "ms_per_step_instrumented": dt / args.steps * 1e3,
+                "ms_per_step_percentiles": pct,
+                "kernels_ms": {k: round(v[1], 4) for k, v in sorted(kern.items())},
+                "roofline": roof,
+                "roofline_issue": roof_issue,
+            })
         log(f"timed region: {ms_step:.3f} ms/step")
-        if world == 1 and not args.no_api_path:
+        if args.full and world == 1 and not args.no_api_path:
             # the reference-shaped route, driver-timed in the same run (see api_path_ms)
             # The route's get_outputs / backward can replay captured hipGraphs (segments.py).  The default policy
             # (config.graph_segments = True) captures a shape once it has been stable for ~240 calls AND the host is the
@@ -928,7 +1005,7 @@ def main():
                 "iters_per_s": 1e3 / api_qed}
             log(f"reference-shaped route: {api_qed:.3f} ms/step (QedAdam), {api_torch:.3f} ms/step (torch.optim.Adam), "
                 f"{api_sep:.3f} ms/step (QedAdam, separate Parameters)")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, m_full=M_ref)
             # the same full-size configs[0] step on the GPU (fused route, eager dispatch), beside the CPU figure
             from qed_splatter_amd.scene import synthetic_scene

@@ -8,8 +8,8 @@ O=$R/gpurun_out/r5p
 mkdir -p $O
 WHAT=${1:-all}
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --steps 30 --warmup 10 --no-cpu-baseline --no-api-path"
-PB="python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-api-path"
+BENCH="python3 $R/bench.py --full --steps 30 --warmup 10 --no-cpu-baseline --no-api-path"
+PB="python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-api-path"
 if [ $WHAT = kt ] || [ $WHAT = all ]; then
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o kt -- $BENCH > $O/kt.json 2> $O/kt.err
   echo "kernel trace done" ; tail -1 $O/kt.err
@@ -26,13 +26,13 @@ if [ $WHAT = k7 ] || [ $WHAT = all ]; then
   for p in pmc1 pmc2 pmc3; do python3 $R/scripts/pmc_db_summary.py $(ls $O/$p/*.db | head -1) composite > $O/$p.txt 2>&1; done
   rocprofv3 --pmc FETCH_SIZE -d $O/fetch -o fetch -- $PB > $O/fetch.json 2> $O/fetch.err ; echo "fetch done"
   rocprofv3 --pmc WRITE_SIZE -d $O/write -o write -- $PB > $O/write.json 2> $O/write.err ; echo "write done"
-  python3 $R/scripts/pmc_to_json.py traffic $(ls $O/fetch/*.db | head -1) $(ls $O/write/*.db | head -1) $O/hbm_traffic_pmc.json "round-5 tree, bench.py --steps 10 --warmup 3"
-  python3 $R/scripts/pmc_to_json.py valu $(ls $O/pmc1/*.db | head -1) $O/valu_issue_pmc.json "round-5 tree, bench.py --steps 10 --warmup 3"
+  python3 $R/scripts/pmc_to_json.py traffic $(ls $O/fetch/*.db | head -1) $(ls $O/write/*.db | head -1) $O/hbm_traffic_pmc.json "round-5 tree, bench.py --full --steps 10 --warmup 3"
+  python3 $R/scripts/pmc_to_json.py valu $(ls $O/pmc1/*.db | head -1) $O/valu_issue_pmc.json "round-5 tree, bench.py --full --steps 10 --warmup 3"
 fi
 if [ $WHAT = rccl ] || [ $WHAT = all ]; then
   # the N > 1 dispatch (three graphs + eager collectives through RCCL) in a group of ONE rank, at config B
-  QED_BENCH_RCCL_SELF=1 python3 $R/bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-api-path > $O/bench_rccl_self.json 2> $O/bench_rccl_self.err
-  python3 $R/bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-api-path > $O/bench_single.json 2> $O/bench_single.err
+  QED_BENCH_RCCL_SELF=1 python3 $R/bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-api-path > $O/bench_rccl_self.json 2> $O/bench_rccl_self.err
+  python3 $R/bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-api-path > $O/bench_single.json 2> $O/bench_single.err
   python3 -c "
 import json
 a=json.load(open('$O/bench_rccl_self.json')); b=json.load(open('$O/bench_single.json'))

@@ -193,6 +193,42 @@ def test_committed_counters_are_quoted_only_for_the_sources_they_were_taken_on(t
             warnings.warn(f"{name} does not describe this tree's kernels: bench.py will report traffic: null")
 
 
+def test_dump_outputs_writes_float_arrays_on_a_fixed_parameter_sample(tmp_path):
+    """bench.py --dump-outputs: the losses as float64, every parameter group (param_<group>.npy) and every gradient
+    (grad_<name>.npy) as float32 on the same fixed, seeded rows (recorded in sample_rows.npy), within the 64 MB the option
+    promises; two dumps of one state are identical."""
+    import numpy as np
+    import torch
+
+    import bench
+    n = bench.DUMP_ROWS + 1000
+    g = torch.Generator().manual_seed(3)
+    shapes = {"means": (3,), "scales": (3,), "quats": (4,), "opacities": (1,), "features_dc": (3,), "features_rest": (15, 3)}
+    params = {k: torch.randn((n,) + s, generator=g) for k, s in shapes.items()}
+    model = types.SimpleNamespace(num_points=n, group_names=list(shapes), gauss_params=params, device=torch.device("cpu"))
+    losses = {"loss": torch.tensor(1.5), "main_loss": torch.tensor(0.5), "depth_loss": torch.tensor(1.0)}
+    grads = {k: 1e-3 * torch.randn((n,) + s, generator=g) for k, s in shapes.items()}     # (every group: the larger case)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), losses, model, grads)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted([f"{k}.npy" for k in losses] + [f"param_{k}.npy" for k in shapes] +
+                           [f"grad_{k}.npy" for k in shapes] + ["sample_rows.npy"])
+    total = 0
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 * 2 ** 20
+    rows = np.load(tmp_path / "a" / "sample_rows.npy").astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and len(np.unique(rows)) == len(rows) and 0 <= rows.min() and rows.max() < n
+    for k in shapes:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"param_{k}.npy"), params[k].numpy()[rows])
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"grad_{k}.npy"), grads[k].numpy()[rows])
+    for k, v in losses.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.float64 and got.shape == (1,) and got[0] == float(v)
+
+
 def test_lazy_sh_gradients_are_off_whenever_a_c_level_reader_could_see_them(monkeypatch):
     """Only Python reads of ``.grad`` complete a compact SH gradient.  DistributedDataParallel's reducer and tensor /
     post-accumulate-grad hooks take the raw field, so with more than one rank in the default process group, or with a hook

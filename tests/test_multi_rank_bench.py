@@ -42,7 +42,7 @@ def test_bench_exchange_path_through_rccl_in_a_group_of_one(cuda):
     env = dict(os.environ, QED_BENCH_RCCL_SELF="1", QED_BENCH_COLLECTIVE_TIMEOUT="120")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "QED_BENCH_REHEARSE"):
         env.pop(k, None)
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
             "--no-cpu-baseline", "--no-api-path", "--gaussians", "100000", "--width", "960", "--height", "540"]
     outs = []
     # default: the whole step, collectives included, as ONE captured graph (gather behind the backward pass); =1: the gather
@@ -68,6 +68,44 @@ def test_bench_exchange_path_through_rccl_in_a_group_of_one(cuda):
     assert o_self["config"]["intersections"] == o_single["config"]["intersections"]
     a, b = o_self["config"]["intersections_after_timed_steps"], o_single["config"]["intersections_after_timed_steps"]
     assert abs(a - b) <= 2e-3 * b, (a, b)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(cuda, tmp_path):
+    """A plain run (no --full) prints the headline fields only, value and ms_per_step describing the same timed region;
+    --dump-outputs writes what the second of two replays of the timed step from the initial scene computes: its losses,
+    and its gradients and the updated parameters on a sample of Gaussians.  Two runs with the same arguments start from the
+    same inputs (same first list length) and write the same outputs, to rounding of each array's largest value."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--gaussians", "100000", "--width", "960", "--height", "540", "--dump-outputs", str(tmp_path / d)]
+        p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-4000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        outs.append(json.loads(lines[0]))
+    a, b = outs
+    for o in outs:
+        assert o["steps"] == 3 and o["warmup"] == 1 and o["n_gpus"] == 1 and o["higher_is_better"] is True
+        assert o["unit"] == "iters/s" and o["dtype"] == "f32" and o["ms_per_step"] > 0
+        assert o["value"] == pytest.approx(3 / (o["ms_per_step"] * 3e-3), rel=1e-6)
+        for k in ("kernels_ms", "roofline", "ms_per_step_percentiles", "api_path_ms_per_step", "cpu_baseline"):
+            assert k not in o, k                                      # --full only
+    assert a["config"]["intersections"] == b["config"]["intersections"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "main_loss.npy", "depth_loss.npy", "sample_rows.npy", "param_means.npy", "grad_means.npy",
+            "grad_opacities.npy", "grad_colors.npy"} <= set(names)
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and x.shape == y.shape and np.isfinite(x).all(), f
+        if f == "sample_rows.npy":
+            assert np.array_equal(x, y)
+        else:                                                      # a few ulp of the array's largest value at most
+            d = np.abs(x.astype(np.float64) - y)
+            assert float(d.max()) <= 1e-5 * float(np.abs(y).max()), (f, float(d.max()))
 
 
 @pytest.mark.gpu
