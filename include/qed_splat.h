@@ -551,6 +551,28 @@ int qed_adam_step_sh(float* params, const float* grads, float* exp_avg, float* e
 int qed_lr_exp_decay_dev(float* dev_lr_slot, const float* dev_state, float lr_init, float lr_final,
                          int32_t max_steps, void* stream);
 
+/* ---- bilateral grid (the reference's use_bilateral_grid, model.py:299-302; nerfstudio 1.1.x lib_bilagrid) ---------
+ * One slab grid[12, L, Y, X] per training image: a 3x4 affine colour transform (row-major) at every lattice vertex;
+ * grid_shape (X, Y, L) = splatfacto's (16, 16, 8) by default, every extent >= 2.
+ * qed_bilagrid_slice_fwd: out[H,W,3] = A[:, :3] rgb + A[:, 3], A = the slab trilinearly sliced at
+ *   x = j (X-1)/(W-1), y = i (Y-1)/(H-1), z = (0.299 r + 0.587 g + 0.114 b)(L-1)  (clipped to [0, L-1]),
+ * i.e. F.grid_sample(align_corners=True, padding_mode="border") at linspace coordinates and guidance 2 gray - 1.
+ * qed_bilagrid_slice_bwd: v_out[H,W,3] -> v_rgb[H,W,3] (A^T v_out plus the term through the guidance, 0 where the
+ * clipped z sits at or beyond either end) and v_grid[12,L,Y,X] (written, not accumulated; float atomics: the last bits
+ * may differ from run to run).  workspace: 12 L Y X floats (cleared by the call).
+ * qed_bilagrid_tv_fwd: out[0] = (1/N) sum over d in {L, Y, X} of sum((g[d+1] - g[d])^2) / numel(difference along d) of
+ * grids[N,12,L,Y,X] (block partials, fixed-order fold: deterministic).  workspace: QED_BILAGRID_TV_WS_DOUBLES doubles.
+ * qed_bilagrid_tv_bwd: v_grids[N,12,L,Y,X] = v_tv[0] * d tv / d grids (written; v_tv is a DEVICE scalar). */
+#define QED_BILAGRID_TV_WS_DOUBLES 1024
+int qed_bilagrid_slice_fwd(int32_t height, int32_t width, const float* rgb, const float* grid, int32_t gx, int32_t gy,
+                           int32_t gl, float* out, void* stream);
+int qed_bilagrid_slice_bwd(int32_t height, int32_t width, const float* rgb, const float* grid, int32_t gx, int32_t gy,
+                           int32_t gl, const float* v_out, float* v_rgb, float* v_grid, float* workspace, void* stream);
+int qed_bilagrid_tv_fwd(int32_t n_grids, const float* grids, int32_t gx, int32_t gy, int32_t gl, float* out,
+                        double* workspace, void* stream);
+int qed_bilagrid_tv_bwd(int32_t n_grids, const float* grids, int32_t gx, int32_t gy, int32_t gl, const float* v_tv,
+                        float* v_grids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

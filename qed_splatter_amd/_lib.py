@@ -71,6 +71,10 @@ SIGNATURES = {
     "qed_adam_step_dev": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _D, _D, _F, _P, _P, _P]),
     "qed_adam_step_sh": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _D, _D, _F, _I, _P, _I, _F, _F, _I, _I, _I, _P, _I,
                                    _P, _L, _P, _L, _F, _I, _P, _P]),
+    "qed_bilagrid_slice_fwd": (C.c_int, [_I, _I, _P, _P, _I, _I, _I, _P, _P]),
+    "qed_bilagrid_slice_bwd": (C.c_int, [_I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "qed_bilagrid_tv_fwd": (C.c_int, [_I, _P, _I, _I, _I, _P, _P, _P]),
+    "qed_bilagrid_tv_bwd": (C.c_int, [_I, _P, _I, _I, _I, _P, _P, _P]),
 }
 
 class Post(C.Structure):
@@ -93,6 +97,7 @@ class AdamTick(C.Structure):
 LOSS_SUMS_FLOATS = 8 + 4 * 1024          # QED_LOSS_SUMS_FLOATS
 METRICS_WS_DOUBLES = 10 * 1024           # QED_METRICS_WS_DOUBLES
 STEP_METRICS_WS_DOUBLES = 16 * 1024      # QED_STEP_METRICS_WS_DOUBLES
+BILAGRID_TV_WS_DOUBLES = 1024            # QED_BILAGRID_TV_WS_DOUBLES
 F_ANTIALIASED = 1
 F_LOG_SCALES = 2
 F_LOGIT_OPAC = 4

@@ -27,7 +27,7 @@ import math
 import os
 import weakref
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import torch
 from torch import Tensor, nn
@@ -69,6 +69,9 @@ class QEDSplatterModelConfig:
     sh_degree_interval: int = 1000
     rasterize_mode: str = "classic"
     use_bilateral_grid: bool = False
+    # SplatfactoModelConfig.grid_shape: (X, Y, L) of each image's bilateral grid (built when use_bilateral_grid is set and
+    # the model is given num_train_data)
+    grid_shape: Tuple[int, int, int] = (16, 16, 8)
     # the defaults below are SplatfactoModelConfig's (nerfstudio 1.1.x), which the reference's config.py:39-42 leaves
     # untouched: random training background, two halvings of the resolution that end at steps 3000 / 6000
     background_color: str = "random"         # "random" | "black" | "white"
@@ -238,10 +241,12 @@ class StepContext:
     ``get_metrics_dict`` / ``get_loss_dict`` / the backward pass, and replaced by the next ``get_outputs``.  Everything in
     here is an OPTIMISATION of work that the calls can also do on their own (a conversion of the batch, an SSIM forward
     pass, a zero-filled accumulator), so every consumer falls back to the full computation when the context is not its
-    own -- ``outputs`` of an earlier step, a second ``get_loss_dict`` on the same outputs, metrics taken under ``no_grad``:
+    own -- ``outputs`` of an earlier step, a second ``get_loss_dict`` on the same outputs, metrics taken under ``no_grad``,
+    an image corrected by a bilateral grid:
 
-      * ``rgb``: the very tensor this step's ``get_outputs`` returned as ``outputs["rgb"]`` -- ``owns(outputs)`` is an
-        identity test, so ``outputs`` kept from an earlier step never pick up this step's state;
+      * ``rgb``: the very tensor this step's ``get_outputs`` returned as ``outputs["rgb"]``, or the image before the
+        bilateral grid when one corrected it (such outputs are never owned) -- ``owns(outputs)`` is an identity test, so
+        ``outputs`` kept from an earlier step never pick up this step's state;
       * ``gt_image(...)``: the last conversion of a batch image (uint8 -> float, downscaling, device), keyed by the source
         tensor's identity, version and the downscale factor -- get_metrics_dict and get_loss_dict prepare the same image;
       * ``ssim``: get_metrics_dict's SSIM forward on (rgb, ground truth) with the maps and sums the loss needs -- taken ONCE
@@ -587,9 +592,14 @@ class QEDSplatterModel(nn.Module):
 
     def __init__(self, config: Optional[QEDSplatterModelConfig] = None, *, means: Tensor, scales: Tensor,
                  quats: Tensor, opacities: Tensor, features_dc: Tensor, features_rest: Tensor,
-                 separate_params: bool = False):
+                 separate_params: bool = False, num_train_data: Optional[int] = None):
         super().__init__()
         self.config = config or QEDSplatterModelConfig()
+        # one bilateral grid per training image (splatfacto's bil_grids; its own optimiser group "bilateral_grid")
+        self.bil_grids = None
+        if self.config.use_bilateral_grid and num_train_data is not None:
+            from .bilagrid import BilateralGrid
+            self.bil_grids = BilateralGrid(int(num_train_data), *self.config.grid_shape, device=means.device)
         N = means.shape[0]
         srcs = dict(means=means, scales=scales, quats=quats, opacities=opacities.reshape(N, 1),
                     features_dc=features_dc.reshape(N, 3), features_rest=features_rest)
@@ -773,7 +783,10 @@ class QEDSplatterModel(nn.Module):
         return self.gauss_params["means"].shape[0]
 
     def get_param_groups(self) -> Dict[str, List[Tensor]]:
-        return {n: [self.gauss_params[n]] for n in self.group_names}
+        groups = {n: [self.gauss_params[n]] for n in self.group_names}
+        if self.bil_grids is not None:
+            groups["bilateral_grid"] = list(self.bil_grids.parameters())
+        return groups
 
     def _apply(self, fn, *args, **kwargs):
         """model.to() / .cuda() / .float() replace every Parameter's data: gather the six groups into a fresh flat
@@ -842,10 +855,14 @@ class QEDSplatterModel(nn.Module):
         return image
 
     def _apply_bilateral_grid(self, rgb: Tensor, cam_idx: int, H: int, W: int) -> Tensor:
-        raise NotImplementedError(
-            "use_bilateral_grid: the bilateral grid lives in the Nerfstudio parent class (lib_bilagrid) and is out of "
-            "scope for this mirror (SURVEY a8); it is reached unchanged when the real QEDSplatterModel uses this "
-            "package's rasterization() (INTEGRATION.md)")
+        """Splatfacto's per-image colour correction (bilagrid.apply_bilateral_grid on grid ``cam_idx``)."""
+        if self.bil_grids is None:
+            raise NotImplementedError(
+                "use_bilateral_grid: this model holds no bilateral grids.  Build them by constructing the model with "
+                "config.use_bilateral_grid=True and num_train_data=<number of training images> (one grid per image; "
+                "their optimiser group is get_param_groups()['bilateral_grid'])")
+        from .bilagrid import apply_bilateral_grid
+        return apply_bilateral_grid(self.bil_grids, rgb, cam_idx, H, W)
 
     def get_empty_outputs(self, width: int, height: int, background: Tensor) -> Dict[str, Tensor]:
         rgb = background.repeat(height, width, 1)
@@ -1051,8 +1068,10 @@ class QEDSplatterModel(nn.Module):
         if depth_im is not None:
             depth_im = depth_im.squeeze(0)
 
-        if self.config.use_bilateral_grid and self.training:                  # model.py:300-302 (not built: raises)
+        pre_grid = None
+        if self.config.use_bilateral_grid and self.training:                  # model.py:300-302
             if getattr(camera, "metadata", None) is not None and "cam_idx" in camera.metadata:
+                pre_grid = rgb.squeeze(0)
                 rgb = self._apply_bilateral_grid(rgb, camera.metadata["cam_idx"], H, W)
 
         # model.py:310-311 `del render; torch.cuda.empty_cache()` is a per-call device sync +
@@ -1063,7 +1082,10 @@ class QEDSplatterModel(nn.Module):
         rgb = rgb.squeeze(0)
         if seg is not None:
             rgb._qed_segment = (seg, seg.generation)       # (get_loss_dict / get_metrics_dict refuse them once overwritten)
-        ctx.bind(rgb, holder, info["radii"].numel())
+        # The step's shortcuts (shared SSIM, the loss writing the compositing backward's gradient buffers) assume the loss
+        # gradient goes straight to the compositing backward: they are bound to the image BEFORE a bilateral grid, so a
+        # corrected image takes the general path of get_loss_dict / get_metrics_dict
+        ctx.bind(rgb if pre_grid is None else pre_grid, holder, info["radii"].numel())
         return {
             "rgb": rgb,
             "depth": depth_im,
@@ -1137,7 +1159,12 @@ class QEDSplatterModel(nn.Module):
         main, depth = _ImageLosses.apply(pred_img, depth_out, gt_img, depth_batch, mask, float(cfg.ssim_lambda),
                                          float(cfg.depth_lambda), shared["maps_sum"] if shared else None, loss_shared, pair,
                                          grad_out)
-        return {"main_loss": main, "scale_reg": self._scale_reg(), "depth_loss": depth}
+        out = {"main_loss": main, "scale_reg": self._scale_reg()}
+        if self.training and cfg.use_bilateral_grid and self.bil_grids is not None:      # the parent's tv_loss
+            from .bilagrid import total_variation_loss
+            out["tv_loss"] = 10 * total_variation_loss(self.bil_grids.grids)
+        out["depth_loss"] = depth
+        return out
 
     # ---- get_metrics_dict (model.py:120-197) ----
     def get_metrics_dict(self, outputs, batch) -> Dict[str, Tensor]:
@@ -1248,6 +1275,10 @@ class QEDSplatterModel(nn.Module):
         122-126 at config B).  A scheduling hint only: images and gradients do not depend on it.  Leave it None when
         consecutive frames come from unrelated cameras and no index is at hand."""
         assert camera.shape[0] == 1, "Only one camera at a time"
+        if self.training and self.config.use_bilateral_grid and self.bil_grids is not None:
+            raise NotImplementedError(
+                "fused_loss does not apply the bilateral grid (nor its tv_loss): train a model with bilateral grids "
+                "through get_outputs -> get_loss_dict -> backward")
         if self.__dict__.get("_lazy_sh") is not None and torch.is_grad_enabled():
             self._materialise_sh_grads()          # (compact gradients of a get_outputs step nobody consumed: see there)
         cfg = self.config
