@@ -198,8 +198,11 @@ int qed_sort_pairs(uint64_t* keys, int32_t* vals, uint64_t* keys_alt, int32_t* v
  * mode: QED_BIN_TWO_STAGE is the pipeline above.  QED_BIN_TILE_SORT gives the same list another way: entries
  * are emitted in slot order and stably sorted on the tile bits, then one workgroup per tile sorts its run by
  * the 32 depth bits (stable, in LDS for runs of <= 2048 entries, through global scratch beyond) -- no global
- * sort of the C*N slots, 10 launches instead of 23, faster while the runs are short.  QED_BIN_AUTO picks by
- * capacity per tile.  block_sums (may be NULL): qed_project_fwd's per-256-slot sums of tiles_per_gauss, which
+ * sort of the C*N slots, 10 launches instead of 23, faster while the runs are short.  QED_BIN_BUCKET gives the
+ * same list in 6 launches: emit in slot order, ONE stable radix pass on the top <= 8 key bits (buckets of 2^s
+ * consecutive cam|tile keys), one workgroup per bucket that stably orders it by the low s bits and writes its tiles'
+ * offsets, then the per-tile depth sort of QED_BIN_TILE_SORT; keys of more than 16 cam|tile bits run the tile-sort
+ * pipeline.  QED_BIN_AUTO picks by capacity per tile: the bucket pipeline for short runs, two-stage for long ones.  block_sums (may be NULL): qed_project_fwd's per-256-slot sums of tiles_per_gauss, which
  * save the tile-sort pipeline one counting launch.
  * host_words (may be NULL): int32[4], 16-byte aligned, in HOST-MAPPED memory (hipHostMalloc / a pinned torch tensor);
  * the call's last list kernel stores {M, status[0], status[1], 0} there in ONE 16-byte store.  A caller that wants the
@@ -208,6 +211,7 @@ int qed_sort_pairs(uint64_t* keys, int32_t* vals, uint64_t* keys_alt, int32_t* v
 #define QED_BIN_AUTO 0
 #define QED_BIN_TWO_STAGE 1
 #define QED_BIN_TILE_SORT 2
+#define QED_BIN_BUCKET 3
 int64_t qed_bin_workspace_bytes(int64_t n_slots, int64_t capacity);
 int qed_bin_tiles(int32_t N, int32_t C, const float* means2d, const int32_t* radii, const float* depths,
                   const int32_t* tiles_per_gauss, const float* splats, const uint64_t* tile_masks,

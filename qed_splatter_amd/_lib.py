@@ -112,12 +112,14 @@ SH_JAC_FLOATS = 10            # QED_SH_JAC_FLOATS
 STATUS_WORDS = 4
 TILE = 16
 CL_TILE_WAVES, CL_QUADRANT_WAVES, CL_HALF_AND_HALF, CL_NO_CULL, CL_ORDER_READY = 1, 2, 3, 4, 8
-BIN_AUTO, BIN_TWO_STAGE, BIN_TILE_SORT = 0, 1, 2
+BIN_AUTO, BIN_TWO_STAGE, BIN_TILE_SORT, BIN_BUCKET = 0, 1, 2, 3
 
 
 def bin_mode() -> int:
-    """Test / measurement hook (auto in production): QED_BIN_MODE=two_stage|tile_sort forces one binning pipeline."""
-    return {"two": BIN_TWO_STAGE, "til": BIN_TILE_SORT}.get(os.environ.get("QED_BIN_MODE", "")[:3], BIN_AUTO)
+    """Test / measurement hook (auto in production): QED_BIN_MODE=two_stage|tile_sort|bucket forces one binning
+    pipeline."""
+    return {"two": BIN_TWO_STAGE, "til": BIN_TILE_SORT, "buc": BIN_BUCKET}.get(os.environ.get("QED_BIN_MODE", "")[:3],
+                                                                            BIN_AUTO)
 
 
 def composite_launch_flags() -> int:

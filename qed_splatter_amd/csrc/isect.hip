@@ -726,6 +726,158 @@ tile_depth_sort_kernel(const int* __restrict__ offsets, const int* __restrict__ 
     }
 }
 
+// ---- bucket binning (qed_bin_tiles, mode QED_BIN_BUCKET) ------------------------------------------------------------
+// After ONE stable radix pass on the top (<= 8) bits of the emitted (camera|tile) keys, bucket b -- the 2^low_bits
+// consecutive keys with key >> low_bits == b -- is a contiguous run of the list, still in slot order.  One workgroup per
+// bucket finishes the low bits with a stable counting sort and writes the offsets of the bucket's tiles: the second
+// global pass of the LSD sort (hist + scan + scatter) and the tile_offsets pass fall away.  Every wave owns a contiguous
+// segment of the bucket and counts its digits (LDS atomics); the digit x wave table is scanned; every wave then ranks
+// its entries again on top of its running counters (ballot match, as sort_scatter_kernel) and writes each value to its
+// tile's place.  Any bucket size is handled (one bucket may hold the whole list); up to 16 k entries the bucket is read
+// once and kept in registers between the two phases.
+constexpr int kPartThreads = 1024;
+constexpr int kPartWaves = kPartThreads / 64;
+constexpr int kPartRows = 16;     // rows of 64 entries a wave requests together
+constexpr int kPartStage = 32768; // buckets of up to this many entries are reordered in LDS and written out coalesced
+
+__global__ void __launch_bounds__(kPartThreads)
+bucket_partition_kernel(const unsigned* __restrict__ keys, const int* __restrict__ vals, const int* __restrict__ n_dev,
+                        const int* __restrict__ bucket_tot, int low_bits, int tile_bits, int n_tiles,
+                        int n_tiles_total, int* __restrict__ vals_out, unsigned* __restrict__ keys_out,
+                        int* __restrict__ offsets, const int* __restrict__ status, int* __restrict__ host_words) {
+    __shared__ int s_cnt[kPartWaves][256];   // per wave and digit: count -> the wave's running place in the digit
+    __shared__ int s_base[256];              // bucket-local exclusive digit base
+    __shared__ int s_wsum[4][2];
+    __shared__ int s_stage[kPartStage];      // the bucket's values in tile order
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x;
+    const int n = n_dev[0];
+    if (b == 0 && tid == 0) {
+        offsets[n_tiles_total] = n;
+        // host words as in tile_offsets_kernel: ONE 16-byte store, every kernel that sets a status word has retired
+        if (host_words != nullptr) {
+            *reinterpret_cast<int4*>(host_words) = make_int4(n, status[0], status[1], 0);
+            __threadfence_system();
+        }
+    }
+    const unsigned dmask = (1u << low_bits) - 1u;
+    // where the bucket starts: the totals of the buckets before it (<= 255 ints; all zero on overflow)
+    int before = 0, size = 0;
+    if (tid < 256) {
+        const int t = bucket_tot[tid];
+        before = tid < b ? t : 0;
+        if (tid == b) size = t;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o, 64); size += __shfl_xor(size, o, 64); }
+    if (wid < 4 && lane == 0) { s_wsum[wid][0] = before; s_wsum[wid][1] = size; }
+    for (int i = tid; i < kPartWaves * 256; i += kPartThreads) (&s_cnt[0][0])[i] = 0;
+    __syncthreads();
+    const int start = s_wsum[0][0] + s_wsum[1][0] + s_wsum[2][0] + s_wsum[3][0];
+    const int m = s_wsum[0][1] + s_wsum[1][1] + s_wsum[2][1] + s_wsum[3][1];
+    // wave wid owns [seg0, seg1) of the bucket, whole rows of 64
+    const int rpw = ((m + 63) / 64 + kPartWaves - 1) / kPartWaves;
+    const int seg0 = min(wid * rpw * 64, m), seg1 = min(seg0 + rpw * 64, m);
+    const unsigned* kin = keys + start;
+    const int* vin = vals + start;
+    // (1) digit counts per wave.  The first kPartRows rows of the segment (all of it for buckets of up to 16 k entries)
+    // are requested together, keys and values, and stay in registers for (3): one memory round trip for most buckets
+    unsigned k0[kPartRows];
+    int v0[kPartRows];
+#pragma unroll
+    for (int j = 0; j < kPartRows; ++j) {
+        const int i = seg0 + 64 * j + lane;
+        const int ic = i < seg1 ? i : max(seg1 - 1, 0);
+        k0[j] = seg1 > seg0 ? kin[ic] : 0u;
+        v0[j] = seg1 > seg0 ? vin[ic] : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < kPartRows; ++j)
+        if (seg0 + 64 * j + lane < seg1) atomicAdd(&s_cnt[wid][k0[j] & dmask], 1);
+    for (int r0 = seg0 + 64 * kPartRows; r0 < seg1; r0 += 64 * kPartRows) {
+        unsigned k[kPartRows];
+#pragma unroll
+        for (int j = 0; j < kPartRows; ++j) {
+            const int i = r0 + 64 * j + lane;
+            k[j] = kin[i < seg1 ? i : seg1 - 1];
+        }
+#pragma unroll
+        for (int j = 0; j < kPartRows; ++j)
+            if (r0 + 64 * j + lane < seg1) atomicAdd(&s_cnt[wid][k[j] & dmask], 1);
+    }
+    __syncthreads();
+    // (2) digit tid (threads 0..255 = waves 0..3): per-wave places, bucket-local base, the tile's offset
+    int tot = 0, x = 0;
+    if (tid < 256) {
+#pragma unroll
+        for (int w = 0; w < kPartWaves; ++w) { const int c = s_cnt[w][tid]; s_cnt[w][tid] = tot; tot += c; }
+        x = tot;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) s_wsum[wid][0] = x;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        int wb = 0;
+        for (int w = 0; w < wid; ++w) wb += s_wsum[w][0];
+        const int base = wb + x - tot;
+        s_base[tid] = base;
+        if (tid <= (int)dmask) {
+            const unsigned key = ((unsigned)b << low_bits) | (unsigned)tid;
+            const unsigned t = key & ((1u << tile_bits) - 1u);
+            const long long lin = (long long)(key >> tile_bits) * n_tiles + t;
+            if ((int)t < n_tiles && lin < n_tiles_total) offsets[lin] = start + base;
+        }
+    }
+    __syncthreads();
+    // (3) stable rank of every entry among its wave's entries of the same digit, then the scatter.  Written straight to
+    // global memory a row of 64 would land in ~32 tiles' runs, one or two 4-byte stores to a line; staged in LDS, the
+    // bucket goes out in consecutive lanes to consecutive addresses (measured at config B: within 0.3 us either way)
+    const bool staged = m <= kPartStage;                                      // (block-uniform)
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    auto place = [&](int r0, const unsigned (&k)[kPartRows], const int (&v)[kPartRows]) {
+#pragma unroll
+        for (int j = 0; j < kPartRows; ++j) {
+            if (r0 + 64 * j >= seg1) break;                                   // (wave-uniform)
+            const bool valid = r0 + 64 * j + lane < seg1;
+            const unsigned d = k[j] & dmask;
+            unsigned long long peers = __ballot(valid);
+            for (int bit = 0; bit < low_bits; ++bit) {
+                const bool on = (d >> bit) & 1u;
+                const unsigned long long bal = __ballot(on);
+                peers &= on ? bal : ~bal;
+            }
+            if (valid) {
+                const int r = s_cnt[wid][d] + __popcll(peers & lt);
+                if ((peers >> lane) == 1ull) s_cnt[wid][d] = r + 1;          // highest peer publishes (in-order LDS)
+                const int pos = s_base[d] + r;
+                if (staged) s_stage[pos] = v[j];
+                else vals_out[start + pos] = v[j];
+                if (keys_out != nullptr) keys_out[start + pos] = k[j];
+            }
+        }
+    };
+    place(seg0, k0, v0);
+    for (int r0 = seg0 + 64 * kPartRows; r0 < seg1; r0 += 64 * kPartRows) {
+        unsigned k[kPartRows];
+        int v[kPartRows];
+#pragma unroll
+        for (int j = 0; j < kPartRows; ++j) {
+            const int i = r0 + 64 * j + lane;
+            const int ic = i < seg1 ? i : seg1 - 1;
+            k[j] = kin[ic];
+            v[j] = vin[ic];
+        }
+        place(r0, k, v);
+    }
+    if (!staged) return;
+    __syncthreads();
+    for (int i = tid; i < m; i += kPartThreads) vals_out[start + i] = s_stage[i];
+}
+
 // gsplat-style 64-bit keys of the sorted list (info["isect_ids"]), rebuilt on demand
 __global__ void __launch_bounds__(256)
 isect_ids_kernel(const unsigned* __restrict__ tile_keys, const int* __restrict__ flatten_ids,
@@ -826,7 +978,7 @@ extern "C" int qed_bin_tiles(int32_t N, int32_t C, const float* means2d, const i
         return QED_OK;
     }
     QED_REQUIRE(means2d && radii && depths && tiles_per_gauss && flatten_ids, "null buffers");
-    QED_REQUIRE(mode >= QED_BIN_AUTO && mode <= QED_BIN_TILE_SORT, "unknown binning mode");
+    QED_REQUIRE(mode >= QED_BIN_AUTO && mode <= QED_BIN_BUCKET, "unknown binning mode");
     const unsigned gridS = (unsigned)((S + 255) / 256);
     // The emit kernel adds up its predecessors' block sums itself (one launch and one serial scan less): every one of the
     // G workgroups reads G ints, O(G^2) L2 traffic in all -- 15 MB at config B (G = 1 954), 1.5 GB at 5 M slots, and it would
@@ -850,7 +1002,46 @@ extern "C" int qed_bin_tiles(int32_t N, int32_t C, const float* means2d, const i
     // Which pipeline: sorting every tile's run by depth costs time in proportion to the list and runs in LDS only
     // for runs of <= 2048 entries; the global depth sort of the slots costs ~12 launch latencies whatever the list.
     // The capacity (1.25 x the longest list seen) per tile decides: short lists per tile -> per-tile sort.
-    if (mode == QED_BIN_AUTO) mode = capacity <= 1024 * n_tot ? QED_BIN_TILE_SORT : QED_BIN_TWO_STAGE;
+    // The bucket pipeline is the tile-sort pipeline with its second global pass and its offsets pass folded into one
+    // launch; it needs the low key bits of a bucket to fit one 8-bit digit (cam|tile keys of <= 16 bits: up to a 4K image
+    // with two cameras), and runs the tile-sort pipeline beyond.
+    if (mode == QED_BIN_AUTO) mode = capacity <= 1024 * n_tot ? QED_BIN_BUCKET : QED_BIN_TWO_STAGE;
+    if (mode == QED_BIN_BUCKET && tile_bits + cam_bits > 16) mode = QED_BIN_TILE_SORT;
+    if (mode == QED_BIN_BUCKET) {
+        const int* bsums = block_sums_in;
+        if (bsums == nullptr) {
+            hipLaunchKernelGGL(count_sorted_kernel, dim3(gridS), dim3(256), 0, st, (int)S, (const int*)nullptr,
+                               tiles_per_gauss, block_sums);
+            bsums = block_sums;
+        }
+        // (1) emit (cam|tile, slot) in slot order -- into flatten_ids, which is only written for good by the depth sort
+        launch_emit(bsums, (const int*)nullptr, flatten_ids);
+        // (2) ONE stable pass on the top <= 8 key bits: bucket b = key >> low_bits, a contiguous run in slot order
+        const int end_bit = tile_bits + cam_bits;
+        const int low_bits = end_bit > 8 ? end_bit - 8 : 0;
+        const int* bucket_tot = nullptr;
+        int rc = sort_pass_u32(kB0, flatten_ids, kB1, vB, n_isect, capacity, low_bits, end_bit - low_bits, sort_ws,
+                               L.sort_ws_bytes, &bucket_tot, st);
+        if (rc != QED_OK) return rc;
+        // (3) one workgroup per bucket: the low bits, stably -> every tile's run in slot order (tv0), the offsets, the
+        // host words; the tile-ordered keys (tk1) only when isect_ids are asked for
+        const long long max_key = ((long long)(C - 1) << tile_bits) | (long long)(tile_w * tile_h - 1);
+        const unsigned n_buckets = (unsigned)((max_key >> low_bits) + 1);
+        int* v_tiles = (int*)(w + L.tv0);
+        unsigned* k_tiles = isect_ids != nullptr ? (unsigned*)(w + L.tk1) : nullptr;
+        hipLaunchKernelGGL(bucket_partition_kernel, dim3(n_buckets), dim3(kPartThreads), 0, st, (const unsigned*)kB1,
+                           (const int*)vB, (const int*)n_isect, bucket_tot, low_bits, tile_bits, tile_w * tile_h,
+                           (int)n_tot, v_tiles, k_tiles, offsets, (const int*)status, host_words);
+        // (4) every tile's run into depth order (stable: ties stay in slot order); scratch: the buffers free by now
+        hipLaunchKernelGGL(tile_depth_sort_kernel, dim3((unsigned)((n_tot + 3) / 4)), dim3(256), 0, st,
+                           (const int*)offsets, (const int*)v_tiles, depths, flatten_ids, kB0, kB1, vB,
+                           (int*)(w + L.tv1), (int)n_tot);
+        if (isect_ids != nullptr)
+            hipLaunchKernelGGL(isect_ids_kernel, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, st,
+                               (const unsigned*)k_tiles, (const int*)flatten_ids, depths, (const int*)n_isect,
+                               (unsigned long long*)isect_ids);
+        return check_launch("qed_bin_tiles");
+    }
     if (mode == QED_BIN_TILE_SORT) {
         // (1) list positions in SLOT order: block sums of the tile counts (project_fwd's, or counted here), scanned
         // by the emit kernel itself

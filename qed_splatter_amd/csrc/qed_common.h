@@ -14,6 +14,10 @@ void set_error(const char* fmt, ...);
 long long sort32_workspace_bytes(long long capacity);
 int sort_pairs_u32(unsigned* keys, int* vals, unsigned* keys_alt, int* vals_alt, const int* n_dev, long long capacity,
                    int end_bit, void* workspace, long long workspace_bytes, int* status, hipStream_t st);
+// one stable pass on bits [shift, shift + bits), bits <= 8; *digit_tot: the device address of the 256 digit totals
+int sort_pass_u32(const unsigned* kin, const int* vin, unsigned* kout, int* vout, const int* n_dev, long long capacity,
+                  int shift, int bits, void* workspace, long long workspace_bytes, const int** digit_tot,
+                  hipStream_t st);
 
 // constants of the operator behind model.py:267-288
 constexpr float kAlphaMax = 0.999f;

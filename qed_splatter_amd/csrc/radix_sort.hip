@@ -421,6 +421,45 @@ int sort_pairs_u32(unsigned* keys, int* vals, unsigned* keys_alt, int* vals_alt,
                                              workspace_bytes, status, st);
 }
 
+// ONE stable pass on the digit (key >> shift) & ((1 << bits) - 1), bits <= 8 (the MSD pass of the bucket binning,
+// qed_bin_tiles): histogram + scan + scatter, kin/vin -> kout/vout.  *digit_tot receives the device address of the 256
+// digit totals the scan wrote (the buckets' sizes).  Same workspace as sort_pairs_u32.
+template <int KPT>
+static int sort_pass_impl(const unsigned* kin, const int* vin, unsigned* kout, int* vout, const int* n_dev,
+                          long long capacity, int shift, int bits, void* workspace, long long workspace_bytes,
+                          const int** digit_tot_out, hipStream_t st) {
+    constexpr int kItems = SortCfg<unsigned, KPT>::kItems;
+    const int nblocks_max = (int)((capacity + kItems - 1) / kItems);
+    const long long need = sort_workspace_need<unsigned, KPT>(capacity);
+    if (nblocks_max == 0 || workspace_bytes < need) {
+        set_error("sort_pass_u32: empty capacity or workspace too small (%lld < %lld)", workspace_bytes, need);
+        return QED_E_WORKSPACE;
+    }
+    int* hist = (int*)workspace;
+    int* digit_tot = hist + (long long)kRadix * nblocks_max;
+    const unsigned mask = (1u << bits) - 1u;
+    hipLaunchKernelGGL((sort_hist_kernel<unsigned, KPT>), dim3(nblocks_max), dim3(kSortThreads), 0, st, kin, n_dev,
+                       shift, mask, nblocks_max, hist);
+    hipLaunchKernelGGL((sort_scan_kernel<kItems>), dim3(kRadix), dim3(kSortThreads), 0, st, n_dev, nblocks_max, hist,
+                       digit_tot);
+    hipLaunchKernelGGL((sort_scatter_kernel<unsigned, KPT, false>), dim3(nblocks_max), dim3(kSortThreads), 0, st, kin,
+                       vin, kout, vout, n_dev, shift, mask, nblocks_max, (const int*)hist, (const int*)digit_tot,
+                       (unsigned*)nullptr, (int*)nullptr, (int*)nullptr);
+    *digit_tot_out = digit_tot;
+    return check_launch("sort_pass_u32");
+}
+
+int sort_pass_u32(const unsigned* kin, const int* vin, unsigned* kout, int* vout, const int* n_dev, long long capacity,
+                  int shift, int bits, void* workspace, long long workspace_bytes, const int** digit_tot,
+                  hipStream_t st) {
+    if (bits < 1 || bits > kRadixBits) { set_error("sort_pass_u32: 1..8 digit bits"); return QED_E_INVALID_ARG; }
+    if (capacity >= kSortLongList)
+        return sort_pass_impl<kKpt32Long>(kin, vin, kout, vout, n_dev, capacity, shift, bits, workspace,
+                                          workspace_bytes, digit_tot, st);
+    return sort_pass_impl<kKpt32>(kin, vin, kout, vout, n_dev, capacity, shift, bits, workspace, workspace_bytes,
+                                  digit_tot, st);
+}
+
 }  // namespace qed
 
 using namespace qed;

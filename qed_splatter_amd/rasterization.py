@@ -503,7 +503,7 @@ def _bin_and_sort(N, C, means2d, radii, depths, tiles_per_gauss, block_sums, til
     # (generously padded) capacity the library's own QED_BIN_AUTO would go by
     mode = L.bin_mode()
     if mode == L.BIN_AUTO and ws.m_seen.get(key, 0) > 0:
-        mode = L.BIN_TILE_SORT if int(1.25 * ws.m_seen[key]) <= 1024 * C * n_tiles else L.BIN_TWO_STAGE
+        mode = L.BIN_BUCKET if int(1.25 * ws.m_seen[key]) <= 1024 * C * n_tiles else L.BIN_TWO_STAGE
     host = host_ptr = None
     if not sync and not capturing:
         host, host_ptr = ws.host_slot()
