@@ -577,6 +577,48 @@ int qed_bilagrid_tv_fwd(int32_t n_grids, const float* grids, int32_t gx, int32_t
 int qed_bilagrid_tv_bwd(int32_t n_grids, const float* grids, int32_t gx, int32_t gy, int32_t gl, const float* v_tv,
                         float* v_grids, void* stream);
 
+/* ---- MCMC densification (splatfacto strategy="mcmc"; gsplat MCMCStrategy) -------------------------------------------
+ * Flat buffers as qed_densify_emit's: six groups means, scales (log), quats, opacities (logit), features_dc,
+ * features_rest, each [N, width], h_*begin[7] their element offsets (+ end), starting at 0.  sigma = sigmoid(logit).
+ * Draws are proportional to sigma over the rows with sigma > min_opacity: weights sigma 2^32 rounded (>= 1) and their
+ * exact uint64 prefix, searched with an integer uniform.  Every random number is a function of (seed, counter, row) --
+ * of (seed, step, row) for the noise -- so equal arguments give bit-identical results.  workspace: device memory of
+ * qed_mcmc_workspace_bytes(N, n_draws) bytes (n_draws = N for qed_mcmc_relocate, n_add for qed_mcmc_add).
+ * qed_mcmc_sample: out_idx[n_draws] = rows drawn with replacement (a zero total weight draws row k mod N).
+ * qed_mcmc_relocate (in place, no host read-back): the dead rows D = {sigma <= min_opacity} draw one live source each
+ *   (or take sources[i], i in D: a live row; other entries are not read).  Per source drawn c times, ratio =
+ *   min(c + 1, 51): sigma' = 1 - (1 - sigma)^(1/ratio) clamped to [min_opacity, 1 - 2^-23], scales *= sigma /
+ *   sum_{j=1..ratio} C(ratio,j) (-1)^(j-1) sigma'^j / sqrt(j) (fp64), both Adam moments of the source zeroed in every
+ *   group; then every group of each dead row <- its source.  The dead rows' moments are left as they were.  n_dead
+ *   (may be NULL): device int32, |D|.
+ * qed_mcmc_add: n_add draws over all rows with sigma > 0 (or sources[n_add], in [0, N)); the sources are updated as
+ *   above with ratio = 1 + times drawn, IN PLACE in `params`; the new buffers [N + n_add rows] hold the N rows (moments
+ *   kept) followed by one copy of each draw with zero moments.
+ * qed_mcmc_noise: means += Sigma (eps gate lr noise_lr), Sigma = R diag(s^2) R^T (R of the normalised wxyz quaternion),
+ *   gate = sigmoid(100 ((1 - sigma) - 0.995)), eps = noise[N,3] or standard normals of (seed, step, row).  dev_lr /
+ *   dev_state (may be NULL) replace lr / step by dev_lr[0] / dev_state[0] (qed_adam_step_dev's state: the launch can
+ *   then be replayed from a hipGraph).  skip_flag: as the Adam entry points' (non-zero: no update).
+ * qed_mcmc_reg: out (may be NULL) = {lo mean(sigma), ls mean(exp(scales)) over 3N, their sum} from a fixed-order fold of
+ *   block partials (deterministic; workspace QED_MCMC_REG_WS_DOUBLES doubles); grad_opacities[N] += lo sigma(1-sigma)/N
+ *   and grad_scales[N,3] += ls exp(scale)/(3N), each times *v_*_reg (DEVICE scalars; NULL = 1), when given. */
+#define QED_MCMC_REG_WS_DOUBLES 2048
+int64_t qed_mcmc_workspace_bytes(int32_t N, int64_t n_draws);
+int qed_mcmc_sample(int32_t N, const float* opacities, float min_opacity, int64_t n_draws, uint64_t seed,
+                    uint64_t counter, int32_t* out_idx, void* workspace, int64_t workspace_bytes, void* stream);
+int qed_mcmc_relocate(int32_t N, float* params, float* exp_avg, float* exp_avg_sq, const int64_t* h_group_begin,
+                      float min_opacity, const int32_t* sources, uint64_t seed, uint64_t counter, int32_t* n_dead,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+int qed_mcmc_add(int32_t N, int32_t n_add, float* params, const float* exp_avg, const float* exp_avg_sq,
+                 const int64_t* h_old_begin, float min_opacity, const int32_t* sources, uint64_t seed, uint64_t counter,
+                 float* new_params, float* new_exp_avg, float* new_exp_avg_sq, const int64_t* h_new_begin,
+                 void* workspace, int64_t workspace_bytes, void* stream);
+int qed_mcmc_noise(int32_t N, float* means, const float* scales, const float* quats, const float* opacities,
+                   const float* noise, float lr, const float* dev_lr, float noise_lr, int64_t step,
+                   const float* dev_state, uint64_t seed, const int32_t* skip_flag, void* stream);
+int qed_mcmc_reg(int32_t N, const float* scales, const float* opacities, float opacity_reg, float scale_reg,
+                 float* out, float* grad_scales, float* grad_opacities, const float* v_opacity_reg,
+                 const float* v_scale_reg, double* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

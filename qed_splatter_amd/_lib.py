@@ -22,6 +22,7 @@ _L = C.c_int64
 _F = C.c_float
 _U = C.c_uint32
 _D = C.c_double
+_Q = C.c_uint64
 SIGNATURES = {
     "qed_version": (C.c_int, []),
     "qed_last_error": (C.c_char_p, []),
@@ -75,6 +76,12 @@ SIGNATURES = {
     "qed_bilagrid_slice_bwd": (C.c_int, [_I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "qed_bilagrid_tv_fwd": (C.c_int, [_I, _P, _I, _I, _I, _P, _P, _P]),
     "qed_bilagrid_tv_bwd": (C.c_int, [_I, _P, _I, _I, _I, _P, _P, _P]),
+    "qed_mcmc_workspace_bytes": (_L, [_I, _L]),
+    "qed_mcmc_sample": (C.c_int, [_I, _P, _F, _L, _Q, _Q, _P, _P, _L, _P]),
+    "qed_mcmc_relocate": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _Q, _Q, _P, _P, _L, _P]),
+    "qed_mcmc_add": (C.c_int, [_I, _I, _P, _P, _P, _P, _F, _P, _Q, _Q, _P, _P, _P, _P, _P, _L, _P]),
+    "qed_mcmc_noise": (C.c_int, [_I, _P, _P, _P, _P, _P, _F, _P, _F, _L, _P, _Q, _P, _P]),
+    "qed_mcmc_reg": (C.c_int, [_I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 class Post(C.Structure):
@@ -98,6 +105,7 @@ LOSS_SUMS_FLOATS = 8 + 4 * 1024          # QED_LOSS_SUMS_FLOATS
 METRICS_WS_DOUBLES = 10 * 1024           # QED_METRICS_WS_DOUBLES
 STEP_METRICS_WS_DOUBLES = 16 * 1024      # QED_STEP_METRICS_WS_DOUBLES
 BILAGRID_TV_WS_DOUBLES = 1024            # QED_BILAGRID_TV_WS_DOUBLES
+MCMC_REG_WS_DOUBLES = 2048               # QED_MCMC_REG_WS_DOUBLES
 F_ANTIALIASED = 1
 F_LOG_SCALES = 2
 F_LOGIT_OPAC = 4

@@ -178,14 +178,6 @@ densify_positions_kernel(int N, const unsigned char* __restrict__ flags, const i
     }
 }
 
-struct EmitLayout {
-    long long old_begin[7], new_begin[7];   // element offsets of the six groups (+ end) in the flat buffers
-    int width[6];                           // floats per Gaussian in each group
-    int total_width;
-    int k_old, k_child, n_split;            // kept old rows, kept children per sample, all splits
-    int n_samples;
-};
-
 __device__ __forceinline__ void quat_rotate(const float* __restrict__ q4, float vx, float vy, float vz, float* out) {
     float w = q4[0], x = q4[1], y = q4[2], z = q4[3];
     const float inv = 1.f / sqrtf(w * w + x * x + y * y + z * z);
@@ -305,17 +297,8 @@ extern "C" int qed_densify_emit(int32_t N, int32_t n_samples, const uint8_t* fla
     if (n_new == 0) return QED_OK;
     QED_REQUIRE(new_params && new_exp_avg && new_exp_avg_sq, "null destination buffers");
     EmitLayout L;
-    L.total_width = 0;
-    for (int g = 0; g < 6; ++g) {
-        const long long w = (h_old_begin[g + 1] - h_old_begin[g]) / N;
-        QED_REQUIRE(w * N == h_old_begin[g + 1] - h_old_begin[g], "old group sizes must be multiples of N");
-        QED_REQUIRE(h_new_begin[g + 1] - h_new_begin[g] == w * n_new, "new group sizes must be width x N'");
-        L.width[g] = (int)w;
-        L.total_width += (int)w;
-    }
-    QED_REQUIRE(L.width[0] == 3 && L.width[1] == 3 && L.width[2] == 4 && L.width[3] == 1,
-                "group order: means, scales, quats, opacities, features_dc, features_rest");
-    for (int g = 0; g < 7; ++g) { L.old_begin[g] = h_old_begin[g]; L.new_begin[g] = h_new_begin[g]; }
+    const int rc = emit_layout("qed_densify_emit", N, h_old_begin, n_new, h_new_begin, L);
+    if (rc != QED_OK) return rc;
     L.k_old = k_old; L.k_child = k_child; L.n_split = n_split; L.n_samples = n_samples;
     hipLaunchKernelGGL(densify_emit_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, N, flags, pos, samples,
                        old_params, old_exp_avg, old_exp_avg_sq, new_params, new_exp_avg, new_exp_avg_sq, L);

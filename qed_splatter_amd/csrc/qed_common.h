@@ -46,6 +46,45 @@ inline int check_launch(const char* what) {
 
 __device__ __forceinline__ float sigmoidf_dev(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
+// Row layout of the flat parameter / Adam-moment buffers: six groups in the order means, scales, quats, opacities,
+// features_dc, features_rest, each [N, width] (densify.hip, mcmc.hip).
+struct EmitLayout {
+    long long old_begin[7], new_begin[7];   // element offsets of the six groups (+ end) in the flat buffers
+    int width[6];                           // floats per Gaussian in each group
+    int total_width;
+    int k_old, k_child, n_split;            // densify: kept old rows, kept children per sample, all splits
+    int n_samples;
+};
+
+// Fills L.width / L.total_width / L.old_begin from the group begins of a buffer of N >= 1 rows and checks the
+// layout; with h_new_begin (n_new rows) also L.new_begin.  QED_OK or QED_E_INVALID_ARG (error string set).
+inline int emit_layout(const char* who, long long N, const int64_t* h_old_begin, long long n_new,
+                       const int64_t* h_new_begin, EmitLayout& L) {
+    L.total_width = 0;
+    for (int g = 0; g < 6; ++g) {
+        const long long w = (h_old_begin[g + 1] - h_old_begin[g]) / N;
+        if (w * N != h_old_begin[g + 1] - h_old_begin[g]) {
+            set_error("%s: old group sizes must be multiples of N", who);
+            return QED_E_INVALID_ARG;
+        }
+        if (h_new_begin && h_new_begin[g + 1] - h_new_begin[g] != w * n_new) {
+            set_error("%s: new group sizes must be width x N'", who);
+            return QED_E_INVALID_ARG;
+        }
+        L.width[g] = (int)w;
+        L.total_width += (int)w;
+    }
+    if (!(L.width[0] == 3 && L.width[1] == 3 && L.width[2] == 4 && L.width[3] == 1)) {
+        set_error("%s: group order: means, scales, quats, opacities, features_dc, features_rest", who);
+        return QED_E_INVALID_ARG;
+    }
+    for (int g = 0; g < 7; ++g) {
+        L.old_begin[g] = h_old_begin[g];
+        L.new_begin[g] = h_new_begin ? h_new_begin[g] : 0;
+    }
+    return QED_OK;
+}
+
 // tile rectangle [x0,x1) x [y0,y1) of a projected Gaussian (gsplat isect_tiles)
 __device__ __forceinline__ void tile_rect(float mx, float my, float radius, int tile_w, int tile_h, int& x0,
                                           int& y0, int& x1, int& y1) {

@@ -80,6 +80,14 @@ class QEDSplatterModelConfig:
     resolution_schedule: int = 3000
     use_scale_regularization: bool = False
     max_gauss_ratio: float = 10.0
+    # splatfacto's densification strategy: "default" (split / clone / cull: densify.Densifier) or "mcmc" (a fixed budget
+    # of max_gs_num Gaussians, relocation and position noise: mcmc.McmcStrategy, plus the two regularisers below in the
+    # loss).  Splatfacto's defaults (nerfstudio 1.1.5)
+    strategy: str = "default"
+    max_gs_num: int = 1_000_000
+    noise_lr: float = 5e5
+    mcmc_opacity_reg: float = 0.01
+    mcmc_scale_reg: float = 0.01
     # ---- not reference fields ----
     # list each Gaussian only in the tiles of its 3-sigma square where some pixel can reach alpha >= 1/255
     # (QED_F_TIGHT_TILES): same images and gradients, shorter lists; info["flatten_ids"] etc. become subsets
@@ -1108,6 +1116,13 @@ class QEDSplatterModel(nn.Module):
             zero = self._zero_loss = torch.tensor(0.0, device=self.device)
         return zero
 
+    def _mcmc_reg_weights(self) -> Tuple[float, float]:
+        """(mcmc_opacity_reg, mcmc_scale_reg) when the loss carries the MCMC regularisers, else (0, 0)."""
+        cfg = self.config
+        if cfg.strategy != "mcmc":
+            return 0.0, 0.0
+        return max(float(cfg.mcmc_opacity_reg), 0.0), max(float(cfg.mcmc_scale_reg), 0.0)
+
     def _loss_mask(self, batch, shape) -> Optional[Tensor]:
         """batch["mask"] [H,W,1] (bool or float; Nerfstudio's are bool) downscaled like the images, as float32."""
         if "mask" not in batch:
@@ -1160,6 +1175,13 @@ class QEDSplatterModel(nn.Module):
                                          float(cfg.depth_lambda), shared["maps_sum"] if shared else None, loss_shared, pair,
                                          grad_out)
         out = {"main_loss": main, "scale_reg": self._scale_reg()}
+        lo, ls = self._mcmc_reg_weights()
+        if lo > 0.0 or ls > 0.0:                 # splatfacto (strategy="mcmc"): after scale_reg, before tv_loss / depth_loss
+            reg_o, reg_s = _McmcReg.apply(self.opacities, self.scales, lo, ls)
+            if lo > 0.0:
+                out["mcmc_opacity_reg"] = reg_o
+            if ls > 0.0:
+                out["mcmc_scale_reg"] = reg_s
         if self.training and cfg.use_bilateral_grid and self.bil_grids is not None:      # the parent's tv_loss
             from .bilagrid import total_variation_loss
             out["tv_loss"] = 10 * total_variation_loss(self.bil_grids.grids)
@@ -1329,6 +1351,14 @@ class QEDSplatterModel(nn.Module):
         holder: list = []         # (the fused loss launch leaves the compositing backward's zeroed accumulator here)
         # the launch-order buffer of this camera (see ``frame_key``): [C T + 1] int32, written by every training frame's
         # loss launch, read by the next frame's compositing forward -- persistent, so that a captured step replays against it
+        # strategy="mcmc": the two regularisers of get_loss_dict, folded into ``loss``; their gradient is added to the flat
+        # gradient by the projection backward, right after it has written it (for an upstream gradient of 1, as above)
+        lo, ls = self._mcmc_reg_weights()
+        mcmc_vals, post_bwd = None, None
+        if lo > 0.0 or ls > 0.0:
+            mcmc_vals = _mcmc_reg_values(self.opacities, self.scales, lo, ls)
+            if torch.is_grad_enabled():
+                post_bwd = _mcmc_reg_grad_adder(self.opacities, self.scales, lo, ls)
         frame_slot, frame_order, frame_order_valid = None, None, False
         if frame_key is not None:
             frame_slot = self._frame_order_slot(frame_key, H, W)
@@ -1344,7 +1374,7 @@ class QEDSplatterModel(nn.Module):
                 viewmats=viewmat, Ks=K, width=W, height=H, tile_size=16, packed=False, near_plane=0.01, far_plane=1e10,
                 render_mode="RGB+D", sh_degree=deg, sparse_grad=False, absgrad=True,
                 rasterize_mode=cfg.rasterize_mode, _flags=flags, _sh_rest=sh_rest, _sync=sync, _vsplat_holder=holder,
-                _c2w=cam_c2w, _tile_order=frame_order if frame_order_valid else None)
+                _c2w=cam_c2w, _tile_order=frame_order if frame_order_valid else None, _post_bwd=post_bwd)
             self.xys = self.info["means2d"]
             self.radii = self.info["radii"][0]
             self.last_viewmat, self.last_sh_degree = viewmat, deg
@@ -1363,7 +1393,62 @@ class QEDSplatterModel(nn.Module):
             if tick is not None:
                 optimizer.drop_tick()
             raise
-        return {"loss": total, "main_loss": parts[0], "depth_loss": parts[1]}
+        if mcmc_vals is None:
+            return {"loss": total, "main_loss": parts[0], "depth_loss": parts[1]}
+        out = {"loss": total + mcmc_vals[2], "main_loss": parts[0]}
+        if lo > 0.0:
+            out["mcmc_opacity_reg"] = mcmc_vals[0]
+        if ls > 0.0:
+            out["mcmc_scale_reg"] = mcmc_vals[1]
+        out["depth_loss"] = parts[1]
+        return out
+
+
+def _mcmc_reg_values(opacities: Tensor, scales: Tensor, lo: float, ls: float) -> Tensor:
+    """[3] device tensor (lo mean(sigmoid(opacities)), ls mean(exp(scales)), their sum): qed_mcmc_reg's deterministic fold."""
+    n = opacities.shape[0]
+    out = torch.empty(3, dtype=torch.float32, device=opacities.device)
+    ws = torch.empty(L.MCMC_REG_WS_DOUBLES, dtype=torch.float64, device=opacities.device)
+    L.check(L.load().qed_mcmc_reg(n, L.ptr(scales), L.ptr(opacities), lo, ls, L.ptr(out), None, None, None, None,
+                                  L.ptr(ws), _stream()), "qed_mcmc_reg")
+    return out
+
+
+def _mcmc_reg_grad_adder(opacities: Tensor, scales: Tensor, lo: float, ls: float):
+    """The projection backward's ``post_bwd`` of fused_loss: adds d(reg_o + reg_s) to the scale / opacity gradient rows."""
+    def add(v_scales: Tensor, v_opacities: Tensor) -> None:
+        L.check(L.load().qed_mcmc_reg(opacities.shape[0], L.ptr(scales), L.ptr(opacities), lo, ls, None, L.ptr(v_scales),
+                                      L.ptr(v_opacities), None, None, None, _stream()), "qed_mcmc_reg")
+    return add
+
+
+class _McmcReg(torch.autograd.Function):
+    """Splatfacto's MCMC regularisers (mcmc_opacity_reg, mcmc_scale_reg) of get_loss_dict: one pass for both values, one
+    for both gradients (scaled by the device-resident upstream gradients: no host sync)."""
+
+    @staticmethod
+    def forward(ctx, opacities, scales, lo, ls):
+        ctx.set_materialize_grads(False)
+        opacities, scales = opacities.detach().contiguous(), scales.detach().contiguous()
+        vals = _mcmc_reg_values(opacities, scales, lo, ls)
+        ctx.save_for_backward(opacities, scales)
+        ctx.lo, ctx.ls = lo, ls
+        return vals[0], vals[1]
+
+    @staticmethod
+    def backward(ctx, g_o, g_s):
+        opacities, scales = ctx.saved_tensors
+        lo = ctx.lo if g_o is not None else 0.0
+        ls = ctx.ls if g_s is not None else 0.0
+        v_opac = torch.zeros_like(opacities) if ctx.needs_input_grad[0] else None
+        v_scales = torch.zeros_like(scales) if ctx.needs_input_grad[1] else None
+        if v_opac is not None or v_scales is not None:
+            up_o = g_o.to(torch.float32).contiguous() if g_o is not None else None
+            up_s = g_s.to(torch.float32).contiguous() if g_s is not None else None
+            L.check(L.load().qed_mcmc_reg(opacities.shape[0], L.ptr(scales), L.ptr(opacities), lo, ls, None,
+                                          L.ptr(v_scales), L.ptr(v_opac), L.ptr(up_o), L.ptr(up_s), None, _stream()),
+                    "qed_mcmc_reg")
+        return v_opac, v_scales, None, None
 
 
 def exponential_decay_lr(step: int, lr_init: float, lr_final: float, max_steps: int, warmup_steps: int = 0,

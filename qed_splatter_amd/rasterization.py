@@ -297,9 +297,11 @@ class _ProjectSH(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, sh0, shN, viewmats, Ks, width, height, tile_w, tile_h,
-                sh_degree, flags, eps2d, near_plane, far_plane, radius_clip, c2w=None, intr=None, lazy_sh=None):
+                sh_degree, flags, eps2d, near_plane, far_plane, radius_clip, c2w=None, intr=None, lazy_sh=None,
+                post_bwd=None):
         lib = L.load()
         ctx.lazy_sh = lazy_sh
+        ctx.post_bwd = post_bwd
         # undefined output gradients arrive as None instead of freshly zero-filled tensors (autograd would
         # otherwise fill one per output per step, the 24 MB splat record included)
         ctx.set_materialize_grads(False)
@@ -421,8 +423,11 @@ class _ProjectSH(torch.autograd.Function):
             shN_stride, sh_degree, L.ptr(viewmats), L.ptr(Ks), width, height, eps2d, flags, L.ptr(radii),
             L.ptr(vsplat), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_scales), L.ptr(v_opacities), v_sh0_ptr,
             v_sh0_stride, v_shN_ptr, v_shN_stride, L.ptr(v_viewmats), L.ptr(sh_jac), _stream()), "qed_project_bwd")
+        post = getattr(ctx, "post_bwd", None)
+        if post is not None:
+            post(v_scales, v_opacities)         # terms of the loss that read the parameters directly (model: MCMC)
         v_opacities = v_opacities.view(ctx.opac_shape)
-        return (v_means, v_quats, v_scales, v_opacities, v_sh0, v_shN, v_viewmats, None) + (None,) * 13
+        return (v_means, v_quats, v_scales, v_opacities, v_sh0, v_shN, v_viewmats, None) + (None,) * 14
 
 
 _VSPLAT_REGISTRY: "weakref.WeakValueDictionary[int, Tensor]" = weakref.WeakValueDictionary()
@@ -689,7 +694,7 @@ def rasterization(
     backgrounds: Optional[Tensor] = None, _flags: int = 0, _sh_rest: Optional[Tensor] = None,
     _sync: bool = True, _vsplat_holder: Optional[list] = None, _c2w: Optional[Tuple[Tensor, Tensor]] = None,
     _post_background: Optional[Tensor] = None, _means2d_leaf: bool = False, _capture_slot=None,
-    _manual: Optional[list] = None, _lazy_sh=None, _tile_order: Optional[Tensor] = None,
+    _manual: Optional[list] = None, _lazy_sh=None, _tile_order: Optional[Tensor] = None, _post_bwd=None,
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Same call surface as the reference's call (model.py:267-288).
 
@@ -699,7 +704,9 @@ def rasterization(
     model.py:241.  ``_post_background`` [3]: the statements that follow the call in get_outputs (model.py:295-297,
     304-306) run inside the compositing kernels; ``info["post_rgb"]`` [C,H,W,3] and ``info["post_depth"]`` [C,H,W,1]
     (RGB+D) are their results, differentiable like ``render`` / ``alpha``.  ``_means2d_leaf``: ``info["means2d"]`` is a
-    leaf that receives ``.grad`` / ``.absgrad`` as views (see below) instead of gsplat's non-leaf.
+    leaf that receives ``.grad`` / ``.absgrad`` as views (see below) instead of gsplat's non-leaf.  ``_post_bwd(v_scales,
+    v_opacities)``: called by the projection backward right after it has written the parameter gradients, to add terms of
+    its own to them in place (the views alias the flat gradient).
     """
     if packed or sparse_grad:
         raise NotImplementedError("packed=True / sparse_grad=True are not used by the reference (model.py:278,283)")
@@ -748,7 +755,7 @@ def rasterization(
         _ProjectSH, _manual, None,
         means, quats, scales, opacities, sh0, shN, viewmats, Ks, int(width), int(height), tile_w, tile_h, deg, flags,
         float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
-        *(_c2w if _c2w is not None else (None, None)), _lazy_sh)
+        *(_c2w if _c2w is not None else (None, None)), _lazy_sh, _post_bwd)
 
     # the packed tile rectangles of the records save the emit pass a recomputation; with F_TIGHT_TILES they
     # are the only place the (smaller) rectangles exist

@@ -1,0 +1,581 @@
+"""Splatfacto's strategy="mcmc": csrc/mcmc.hip through the C ABI and McmcStrategy against the fp64 restatement
+(tests/mcmc_ref.py), the regularisers on both loss routes, graph capture and a short training run."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import pytest
+import torch
+
+from tests import mcmc_ref as R
+from tests.util import PARAM_NAMES
+
+
+# ---------------------------------------------------------------------------------------------------
+# CPU
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sigma_new", [0.005, 0.01, 0.1, 0.5, 0.9, 1.0 - 2.0 ** -23])
+def test_hockey_stick_equals_double_sum(sigma_new):
+    for ratio in range(1, R.N_MAX + 1):
+        a, b = R.hockey_stick(sigma_new, ratio), R.double_sum(sigma_new, ratio)
+        # both alternate: their rounding is bounded by the sum of the absolute terms, not by the result
+        terms = sum(math.comb(i - 1, k) * sigma_new ** (k + 1) / math.sqrt(k + 1)
+                    for i in range(1, ratio + 1) for k in range(i))
+        assert abs(a - b) <= 1e-14 * terms, (ratio, a, b)
+        if sigma_new * ratio <= 1.0:                      # the regime of the relocation: sigma' ~ sigma / ratio
+            assert abs(a - b) <= 1e-14 * abs(b), (ratio, a, b)
+
+
+def test_refinement_schedule():
+    from qed_splatter_amd.mcmc import McmcConfig
+    cfg = McmcConfig()
+    assert (cfg.cap_max, cfg.noise_lr, cfg.refine_start, cfg.refine_stop, cfg.refine_every, cfg.min_opacity) == \
+        (1_000_000, 5e5, 500, 15000, 100, 0.005)
+    steps = [s for s in range(0, 16001) if cfg.refines_at(s)]
+    assert steps[0] == 600 and steps[-1] == 14900 and len(steps) == 144
+    assert not cfg.refines_at(500) and not cfg.refines_at(15000) and not cfg.refines_at(650)
+    small = McmcConfig(refine_start=0, refine_stop=50, refine_every=10)
+    assert [s for s in range(100) if small.refines_at(s)] == [10, 20, 30, 40]
+
+
+def test_model_config_fields():
+    from qed_splatter_amd.model import QEDSplatterModelConfig
+    from qed_splatter_amd.mcmc import McmcConfig
+    cfg = QEDSplatterModelConfig()
+    assert (cfg.strategy, cfg.max_gs_num, cfg.noise_lr, cfg.mcmc_opacity_reg, cfg.mcmc_scale_reg) == \
+        ("default", 1_000_000, 5e5, 0.01, 0.01)
+    mc = McmcConfig.from_model(QEDSplatterModelConfig(strategy="mcmc", max_gs_num=1234, noise_lr=7.0))
+    assert mc.cap_max == 1234 and mc.noise_lr == 7.0
+
+
+def _cpu_model(n=8, **kw):
+    from qed_splatter_amd.model import QEDSplatterModel, QEDSplatterModelConfig
+    g = torch.Generator().manual_seed(0)
+    p = {"means": torch.randn(n, 3, generator=g), "scales": torch.randn(n, 3, generator=g) - 3,
+         "quats": torch.randn(n, 4, generator=g), "opacities": torch.randn(n, 1, generator=g),
+         "features_dc": torch.rand(n, 3, generator=g), "features_rest": torch.zeros(n, 15, 3)}
+    sep = kw.pop("separate_params", False)
+    return QEDSplatterModel(QEDSplatterModelConfig.synthetic(**kw), separate_params=sep, **p)
+
+
+def test_strategy_refuses_unsupported_setups():
+    from qed_splatter_amd.mcmc import McmcStrategy
+    with pytest.raises(ValueError, match="strategy"):
+        McmcStrategy(_cpu_model(), object())
+    with pytest.raises(RuntimeError, match="separate_params"):
+        McmcStrategy(_cpu_model(strategy="mcmc", separate_params=True), object())
+    m = _cpu_model(strategy="mcmc")
+    with pytest.raises(TypeError, match="FlatAdam"):
+        McmcStrategy(m, torch.optim.Adam(m.parameters()))
+
+
+def test_abi_rejects_bad_arguments(lib):
+    begin = (C.c_int64 * 7)(0, 30, 60, 100, 110, 140, 590)        # N = 10, SH degree 3
+    bad = (C.c_int64 * 7)(0, 30, 60, 100, 110, 140, 595)          # features_rest not a multiple of N
+    ws = 1 << 20
+    P = 0x1000                                                     # (never dereferenced: rejected on the host)
+    assert lib.qed_mcmc_workspace_bytes(-1, 0) < 0
+    assert lib.qed_mcmc_workspace_bytes(10, 10) > 0
+    rc = lib.qed_mcmc_relocate(-1, P, P, P, C.cast(begin, C.c_void_p), 0.005, None, 0, 0, None, P, ws, None)
+    assert rc == -1 and b"bad arguments" in lib.qed_last_error()
+    rc = lib.qed_mcmc_relocate(10, None, P, P, C.cast(begin, C.c_void_p), 0.005, None, 0, 0, None, P, ws, None)
+    assert rc == -1 and b"null" in lib.qed_last_error()
+    rc = lib.qed_mcmc_relocate(10, P, P, P, C.cast(bad, C.c_void_p), 0.005, None, 0, 0, None, P, ws, None)
+    assert rc == -1 and b"multiples of N" in lib.qed_last_error()
+    rc = lib.qed_mcmc_relocate(10, P, P, P, C.cast(begin, C.c_void_p), 0.005, None, 0, 0, None, P, 16, None)
+    assert rc == -1 and b"workspace" in lib.qed_last_error()
+    new_ok = (C.c_int64 * 7)(0, 33, 66, 110, 121, 154, 649)       # N' = 11
+    rc = lib.qed_mcmc_add(10, 1, P, P, P, C.cast(begin, C.c_void_p), 0.005, None, 0, 0, P, P, P,
+                          C.cast(begin, C.c_void_p), P, ws, None)
+    assert rc == -1 and b"width x N'" in lib.qed_last_error()
+    rc = lib.qed_mcmc_add(10, 1, P, P, P, C.cast(begin, C.c_void_p), 0.005, None, 0, 0, None, P, P,
+                          C.cast(new_ok, C.c_void_p), P, ws, None)
+    assert rc == -1 and b"null" in lib.qed_last_error()
+    rc = lib.qed_mcmc_noise(10, None, P, P, P, None, 1.0, None, 1.0, 0, None, 0, None, None)
+    assert rc == -1 and b"null" in lib.qed_last_error()
+    rc = lib.qed_mcmc_noise(-3, P, P, P, P, None, 1.0, None, 1.0, 0, None, 0, None, None)
+    assert rc == -1
+    rc = lib.qed_mcmc_reg(0, P, P, 0.01, 0.01, P, None, None, None, None, P, None)
+    assert rc == -1 and b"bad arguments" in lib.qed_last_error()
+    rc = lib.qed_mcmc_reg(10, P, P, 0.01, 0.01, P, None, None, None, None, None, None)
+    assert rc == -1 and b"workspace" in lib.qed_last_error()
+    rc = lib.qed_mcmc_sample(0, P, 0.0, 5, 0, 0, P, P, ws, None)
+    assert rc == -1 and b"empty" in lib.qed_last_error()
+
+
+# ---------------------------------------------------------------------------------------------------
+# GPU helpers
+# ---------------------------------------------------------------------------------------------------
+MIN_OP = 0.005
+
+
+def _params(n, seed, dead_frac=0.1, rest=15):
+    """Opacities well away from min_opacity (no fp32 / fp64 disagreement on who is dead)."""
+    g = torch.Generator().manual_seed(seed)
+    sig = torch.tensor([0.02, 0.2, 0.5, 0.8, 0.97])[torch.randint(0, 5, (n, 1), generator=g)]
+    dead = torch.rand(n, 1, generator=g) < dead_frac
+    sig = torch.where(dead, torch.tensor([0.001, 0.004])[torch.randint(0, 2, (n, 1), generator=g)], sig)
+    return {"means": torch.randn(n, 3, generator=g), "scales": torch.randn(n, 3, generator=g) * 0.5 - 3.0,
+            "quats": torch.randn(n, 4, generator=g), "opacities": torch.log(sig / (1 - sig)),
+            "features_dc": torch.rand(n, 3, generator=g), "features_rest": torch.randn(n, rest, 3, generator=g) * 0.1}
+
+
+def _moments(p, seed):
+    g = torch.Generator().manual_seed(seed)
+    return ({k: torch.randn(v.shape, generator=g) * 0.01 for k, v in p.items()},
+            {k: torch.rand(v.shape, generator=g) * 0.01 for k, v in p.items()})
+
+
+def _model(p, dev, kind="flat", **cfg_kw):
+    from qed_splatter_amd.model import FlatAdam, QedAdam, QedAdamSet, QEDSplatterModel, QEDSplatterModelConfig
+    cfg_kw.setdefault("strategy", "mcmc")
+    model = QEDSplatterModel(QEDSplatterModelConfig.synthetic(**cfg_kw), **{k: p[k].to(dev) for k in PARAM_NAMES})
+    if kind == "flat":
+        opt = FlatAdam(model)
+    else:
+        opts = {k: QedAdam([model.gauss_params[k]], lr=FlatAdam.DEFAULT_LRS[k], eps=1e-15) for k in model.group_names}
+        opt = QedAdamSet(model, opts)
+    return model, opt
+
+
+def _set_moments(model, opt, m, v):
+    for name, b0, b1 in zip(model.group_names, model.group_begin[:-1], model.group_begin[1:]):
+        opt.exp_avg[b0:b1] = m[name].reshape(-1).to(opt.exp_avg.device)
+        opt.exp_avg_sq[b0:b1] = v[name].reshape(-1).to(opt.exp_avg.device)
+
+
+def _groups(model, buf):
+    return {name: buf[b0:b1].view(model.gauss_params[name].shape).detach().cpu()
+            for name, b0, b1 in zip(model.group_names, model.group_begin[:-1], model.group_begin[1:])}
+
+
+def _close_rel(a, b, tol=1e-5):
+    a, b = a.double(), b.double()
+    err = ((a - b).abs() / b.abs().clamp_min(1.0)).max()
+    assert float(err) <= tol, float(err)
+
+
+def _relocation_sources(p, seed):
+    """Per dead row a live source, with one source drawn 60 times (ratio clamped at 51), one 50 times (ratio 51), one
+    twice, the rest once or at random."""
+    g = torch.Generator().manual_seed(seed)
+    sig = torch.sigmoid(p["opacities"][:, 0].double())
+    dead = torch.nonzero(sig <= MIN_OP).reshape(-1)
+    alive = torch.nonzero(sig > MIN_OP).reshape(-1)
+    assert dead.numel() > 120
+    src = alive[torch.randint(0, alive.numel(), (dead.numel(),), generator=g)]
+    src[:60] = alive[0]
+    src[60:110] = alive[1]
+    src[110:112] = alive[2]
+    full = torch.full((sig.numel(),), -7, dtype=torch.int32)      # (alive rows: never read)
+    full[dead] = src.int()
+    return full
+
+
+# ---------------------------------------------------------------------------------------------------
+# GPU: relocation / add against the restatement
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_relocate_matches_reference(cuda):
+    from qed_splatter_amd.mcmc import McmcStrategy
+    n = 4000
+    p = _params(n, seed=1, dead_frac=0.1)
+    m, v = _moments(p, seed=2)
+    model, opt = _model(p, cuda)
+    _set_moments(model, opt, m, v)
+    strat = McmcStrategy(model, opt, seed=5)
+    sources = _relocation_sources(p, seed=3)
+    ptr_before = (model.flat_params.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr())
+    n_dead = strat.relocate(sources=sources.to(cuda))
+    torch.cuda.synchronize()
+    assert (model.flat_params.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr()) == ptr_before
+    rp, rm, rv, dead = R.relocate(p, m, v, sources, MIN_OP)
+    assert int(n_dead) == int(dead.sum())
+    gp, gm, gv = _groups(model, model.flat_params), _groups(model, opt.exp_avg), _groups(model, opt.exp_avg_sq)
+    src = sources.long()
+    drawn = torch.zeros(n, dtype=torch.bool)
+    drawn[src[dead]] = True
+    # new logits and log-scales of the sources within 1e-5 of fp64
+    _close_rel(gp["opacities"][drawn], rp["opacities"][drawn])
+    _close_rel(gp["scales"][drawn], rp["scales"][drawn])
+    # the ratio 51 sources: the clamp (60 draws) and the exact 51 (50 draws) give the same update
+    for name in PARAM_NAMES:
+        # copied groups are bit-equal to their source
+        assert torch.equal(gp[name][dead], gp[name][src[dead]]), name
+        # alive, non-drawn rows bit-unchanged
+        keep = ~dead & ~drawn
+        assert torch.equal(gp[name][keep], p[name][keep]), name
+        # source moments zero, dead-slot moments untouched
+        assert bool((gm[name][drawn] == 0).all()) and bool((gv[name][drawn] == 0).all()), name
+        assert torch.equal(gm[name][dead], m[name][dead]) and torch.equal(gv[name][dead], v[name][dead]), name
+        assert torch.equal(gm[name][keep], m[name][keep]), name
+    # unchanged groups of the sources
+    for name in ("means", "quats", "features_dc", "features_rest"):
+        assert torch.equal(gp[name][drawn], p[name][drawn]), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["flat", "qed"])
+def test_add_matches_reference(cuda, kind):
+    from qed_splatter_amd.mcmc import McmcConfig, McmcStrategy
+    n = 3000
+    p = _params(n, seed=4, dead_frac=0.0)
+    m, v = _moments(p, seed=5)
+    results = []
+    model, opt = _model(p, cuda, kind)
+    _set_moments(model, opt, m, v)
+    strat = McmcStrategy(model, opt, McmcConfig(cap_max=10 ** 6), seed=1)
+    n_add = int(1.05 * n) - n
+    g = torch.Generator().manual_seed(6)
+    sources = torch.randint(0, n, (n_add,), generator=g).int()
+    sources[:55] = 17                                         # one source drawn 55 times: ratio clamped at 51
+    added = strat.add(sources=sources.to(cuda))
+    torch.cuda.synchronize()
+    assert added == n_add and model.num_points == int(1.05 * n)
+    widths = [3, 3, 4, 1, 3, 45]
+    assert model.group_begin == [sum(w * model.num_points for w in widths[:i]) for i in range(7)]
+    rp, rm, rv = R.add(p, m, v, sources, MIN_OP)
+    gp, gm, gv = _groups(model, model.flat_params), _groups(model, opt.exp_avg), _groups(model, opt.exp_avg_sq)
+    drawn = torch.zeros(n, dtype=torch.bool)
+    drawn[sources.long()] = True
+    for name in PARAM_NAMES:
+        if name in ("opacities", "scales"):
+            _close_rel(gp[name], rp[name])
+        else:
+            assert torch.equal(gp[name], rp[name].float()), name
+        assert torch.equal(gp[name][n:], gp[name][sources.long()]), name     # appended rows: copies of the sources
+        assert bool((gm[name][n:] == 0).all()) and bool((gv[name][n:] == 0).all()), name
+        assert torch.equal(gm[name][:n], m[name]) and torch.equal(gv[name][:n], v[name]), name
+    # the optimiser took the new buffers and steps on
+    assert opt.exp_avg.numel() == model.flat_params.numel()
+    # at the cap: nothing appended, nothing swapped
+    strat.config.cap_max = model.num_points
+    ptrs = (model.flat_params.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr())
+    assert strat.add() == 0
+    assert (model.flat_params.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr()) == ptrs
+    results.append(model.flat_params.cpu())
+    if kind == "qed":                                         # same result as FlatAdam's route
+        model2, opt2 = _model(p, cuda, "flat")
+        _set_moments(model2, opt2, m, v)
+        McmcStrategy(model2, opt2, McmcConfig(cap_max=10 ** 6), seed=1).add(sources=sources.to(cuda))
+        assert torch.equal(model2.flat_params.cpu(), results[0])
+        assert torch.equal(opt2.exp_avg.cpu(), opt.exp_avg.cpu())
+
+
+# ---------------------------------------------------------------------------------------------------
+# GPU: sampler
+# ---------------------------------------------------------------------------------------------------
+def _chi2_sf(x: float, k: int) -> float:
+    """Upper tail of chi-square with k degrees of freedom (Wilson-Hilferty)."""
+    z = ((x / k) ** (1.0 / 3.0) - (1.0 - 2.0 / (9 * k))) / math.sqrt(2.0 / (9 * k))
+    return 0.5 * math.erfc(z / math.sqrt(2.0))
+
+
+@pytest.mark.gpu
+def test_sampler_distribution_and_determinism(cuda):
+    from qed_splatter_amd.mcmc import sample
+    g = torch.Generator().manual_seed(9)
+    n = 200
+    sig = torch.rand(n, generator=g).double() * 0.9 + 0.05
+    sig[::17] = 0.001                                             # dead (below min_opacity)
+    logits = torch.log(sig / (1 - sig)).float()
+    logits[5] = -float("inf")                                     # weight exactly 0
+    logits[6] = float("nan")                                      # not a live row either
+    draws = 1_000_000
+    a = sample(logits.to(cuda), draws, min_opacity=MIN_OP, seed=11, counter=3)
+    b = sample(logits.to(cuda), draws, min_opacity=MIN_OP, seed=11, counter=3)
+    c = sample(logits.to(cuda), draws, min_opacity=MIN_OP, seed=11, counter=4)
+    assert torch.equal(a, b) and not torch.equal(a, c)
+    counts = torch.bincount(a.long().cpu(), minlength=n).double()
+    live = (sig > MIN_OP) & torch.isfinite(logits.double())
+    live[5] = live[6] = False
+    assert float(counts[~live].sum()) == 0.0                      # dead / zero-weight rows never drawn
+    w = torch.sigmoid(logits.double())[live]
+    expected = w / w.sum() * draws
+    chi2 = float(((counts[live] - expected) ** 2 / expected).sum())
+    p = _chi2_sf(chi2, int(live.sum()) - 1)
+    assert p > 1e-3, (chi2, p)
+
+
+# ---------------------------------------------------------------------------------------------------
+# GPU: noise
+# ---------------------------------------------------------------------------------------------------
+def _noise_params(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    p = _params(n, seed, dead_frac=0.0)
+    p["means"] = torch.zeros(n, 3)                                # means' = delta exactly
+    q = torch.randn(n, 4, generator=g) * torch.tensor([3.0, 0.2, 1.0, 0.01])   # unnormalised
+    p["quats"] = q
+    ls = torch.rand(n, 3, generator=g) * 2 - 3
+    ls[::3] = torch.tensor([0.0, -7.0, -7.5])                     # needles
+    p["scales"] = ls
+    sig = torch.tensor([0.0005, 0.002, 0.004, 0.006, 0.02, 0.5])[torch.randint(0, 6, (n, 1), generator=g)]
+    p["opacities"] = torch.log(sig / (1 - sig))                   # gate from ~0.6 down to ~0
+    return p
+
+
+@pytest.mark.gpu
+def test_noise_with_supplied_eps_matches_reference(cuda):
+    from qed_splatter_amd.mcmc import McmcConfig, McmcStrategy
+    n = 5000
+    p = _noise_params(n, 1)
+    model, opt = _model(p, cuda)
+    strat = McmcStrategy(model, opt, McmcConfig(noise_lr=1000.0))
+    eps = torch.randn(n, 3, generator=torch.Generator().manual_seed(2))
+    strat.inject_noise(noise=eps.to(cuda), step=1)
+    lr = float(opt.lr[0])
+    ref, _, gate = R.noise_delta(p["scales"], p["quats"], p["opacities"], eps, lr, 1000.0)
+    got = model.means.detach().cpu().double()
+    # relative to the row's own scale max(s)^2 |eps| gate lr noise_lr: a needle whose long axis is nearly orthogonal to
+    # eps moves far less than that, and no fp32 evaluation of Sigma eps resolves the cancellation below it
+    s_max = torch.exp(p["scales"].double()).max(dim=1).values
+    scale = (s_max ** 2 * eps.double().norm(dim=1) * gate * lr * 1000.0).clamp_min(1e-300)[:, None]
+    live = gate > 1e-30
+    err = float(((got - ref).abs() / scale)[live].max())
+    assert err <= 1e-5, err
+    assert torch.equal(got[~live], torch.zeros_like(got[~live]))   # gate underflows to 0 in fp32 as well
+
+
+@pytest.mark.gpu
+def test_generated_noise_is_keyed_and_standard_normal(cuda):
+    from qed_splatter_amd.mcmc import McmcConfig, McmcStrategy
+    from qed_splatter_amd.rasterization import _workspace
+    n = 200_000
+    p = _params(n, seed=3, dead_frac=0.0)
+    p["means"] = torch.zeros(n, 3)
+    p["opacities"] = torch.full((n, 1), math.log(0.001 / 0.999))
+    p["scales"] = torch.rand(n, 3, generator=torch.Generator().manual_seed(4)) - 1.0
+    outs = []
+    for step in (7, 7, 8):
+        model, opt = _model(p, cuda)
+        McmcStrategy(model, opt, McmcConfig(noise_lr=1.0), seed=21).inject_noise(step=step)
+        outs.append(model.means.detach().cpu())
+    assert torch.equal(outs[0], outs[1]) and not torch.equal(outs[0], outs[2])
+    lr = float(opt.lr[0])
+    _, cov, gate = R.noise_delta(p["scales"], p["quats"], p["opacities"], torch.zeros(n, 3), lr, 1.0)
+    eps = torch.linalg.solve(cov, outs[0].double()[..., None])[..., 0] / (gate * lr)[:, None]
+    k = eps.numel()
+    assert abs(float(eps.mean())) < 5.0 / math.sqrt(k)
+    assert abs(float(eps.var()) - 1.0) < 5.0 * math.sqrt(2.0 / k)
+    # a skipped step (the binning overflow word set) adds nothing
+    model, opt = _model(p, cuda)
+    ws = _workspace(model.device)
+    ws.status[0] = 1
+    try:
+        McmcStrategy(model, opt, McmcConfig(noise_lr=1.0), seed=21).inject_noise(step=7)
+        torch.cuda.synchronize()
+    finally:
+        ws.status[0] = 0
+    assert bool((model.means.detach() == 0).all())
+
+
+# ---------------------------------------------------------------------------------------------------
+# GPU: regularisers on both loss routes
+# ---------------------------------------------------------------------------------------------------
+def _scene_model(dev, seed=21, n=3000, **cfg_kw):
+    from tests.test_gpu_parity import _model as parity_model
+    from tests.util import scene
+    sc = scene(n, 160, 112, seed=seed)
+    return parity_model(sc, dev, **cfg_kw)
+
+
+@pytest.mark.gpu
+def test_regularisers_on_get_loss_dict_route(cuda):
+    lo, ls = 3.0, 5.0
+    model, cam, batch = _scene_model(cuda, strategy="mcmc", mcmc_opacity_reg=lo, mcmc_scale_reg=ls)
+    losses = model.get_loss_dict(model.get_outputs(cam), batch)
+    assert list(losses) == ["main_loss", "scale_reg", "mcmc_opacity_reg", "mcmc_scale_reg", "depth_loss"]
+    op = model.opacities.detach().cpu().double().requires_grad_(True)
+    sc = model.scales.detach().cpu().double().requires_grad_(True)
+    r_o, r_s = R.regularisers(op, sc, lo, ls)
+    assert abs(float(losses["mcmc_opacity_reg"]) - float(r_o)) <= 1e-6 * float(r_o)
+    assert abs(float(losses["mcmc_scale_reg"]) - float(r_s)) <= 1e-6 * float(r_s)
+    (2.0 * losses["mcmc_opacity_reg"] + 0.5 * losses["mcmc_scale_reg"]).backward()
+    (2.0 * r_o + 0.5 * r_s).backward()
+    torch.testing.assert_close(model.opacities.grad.cpu().double(), op.grad, rtol=1e-5, atol=1e-12)
+    torch.testing.assert_close(model.scales.grad.cpu().double(), sc.grad, rtol=1e-5, atol=1e-12)
+    # keys only with strategy="mcmc" and a positive weight
+    model2, cam2, batch2 = _scene_model(cuda, strategy="mcmc", mcmc_opacity_reg=0.0)
+    assert list(model2.get_loss_dict(model2.get_outputs(cam2), batch2)) == \
+        ["main_loss", "scale_reg", "mcmc_scale_reg", "depth_loss"]
+    model3, cam3, batch3 = _scene_model(cuda)
+    assert list(model3.get_loss_dict(model3.get_outputs(cam3), batch3)) == ["main_loss", "scale_reg", "depth_loss"]
+    assert list(model3.fused_loss(cam3, batch3)) == ["loss", "main_loss", "depth_loss"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("how", ["backward_fused", "backward"])
+def test_fused_route_gradient_matches_get_loss_dict_route(cuda, how):
+    from tests.util import assert_close
+    kw = dict(strategy="mcmc", mcmc_opacity_reg=20.0, mcmc_scale_reg=2000.0)
+    model, cam, batch = _scene_model(cuda, **kw)
+    losses = model.get_loss_dict(model.get_outputs(cam), batch)
+    sum(losses.values()).backward()
+    ref = {k: model.gauss_params[k].grad.detach().clone() for k in PARAM_NAMES}
+    ref_vals = {k: float(v) for k, v in losses.items()}
+
+    model2, cam2, batch2 = _scene_model(cuda, **kw)
+    out = model2.fused_loss(cam2, batch2)
+    assert list(out) == ["loss", "main_loss", "mcmc_opacity_reg", "mcmc_scale_reg", "depth_loss"]
+    assert not out["mcmc_opacity_reg"].requires_grad and not out["mcmc_scale_reg"].requires_grad
+    for k in ("mcmc_opacity_reg", "mcmc_scale_reg"):
+        assert abs(float(out[k]) - ref_vals[k]) <= 1e-6 * abs(ref_vals[k])
+    total = float(out["main_loss"]) + float(out["mcmc_opacity_reg"]) + float(out["mcmc_scale_reg"]) + \
+        float(out["depth_loss"])
+    assert abs(float(out["loss"]) - total) <= 1e-6 * total
+    if how == "backward_fused":
+        model2.backward_fused(out)
+    else:
+        out["loss"].backward()
+    flat = model2.flat_grad()
+    assert flat is not None and flat.data_ptr() == model2.gauss_params["means"].grad.data_ptr()   # one allocation
+    for k in ("scales", "opacities"):
+        assert_close(model2.gauss_params[k].grad, ref[k], what=k)
+    # the terms matter at this weight: without them the scale / opacity gradients are far off
+    model3, cam3, batch3 = _scene_model(cuda)
+    model3.backward_fused(model3.fused_loss(cam3, batch3))
+    from tests.util import max_rel
+    assert max_rel(model3.scales.grad, ref["scales"]) > 1e-2
+    assert max_rel(model3.opacities.grad, ref["opacities"]) > 1e-3
+
+
+# ---------------------------------------------------------------------------------------------------
+# GPU: graph capture
+# ---------------------------------------------------------------------------------------------------
+def _graph_setup(dev, seed, cap_extra=0, **kw):
+    from qed_splatter_amd.mcmc import McmcConfig, McmcStrategy
+    from qed_splatter_amd.model import FlatAdam
+    model, cam, batch = _scene_model(dev, seed=seed, strategy="mcmc")
+    with torch.no_grad():                                         # some dead Gaussians for the relocation
+        model.opacities[::40] = -8.0
+    opt = FlatAdam(model, means_schedule=FlatAdam.MEANS_SCHEDULE)
+    strat = McmcStrategy(model, opt, McmcConfig(cap_max=model.num_points + cap_extra), seed=4)
+    return model, cam, batch, opt, strat
+
+
+def _close_fraction(a, b, rtol=2e-6, atol=2e-6):
+    """Share of elements outside the bound of tests/test_densify.py (Adam's first steps are ~sign(g) lr: an element whose
+    gradient sits at the last-bit noise of the atomics may flip)."""
+    bad = ((a - b).abs() > atol + rtol * b.abs()).double().mean()
+    return float(bad)
+
+
+@pytest.mark.gpu
+def test_graphed_step_with_noise(cuda):
+    from qed_splatter_amd.graph import GraphedTrainStep
+    stream = torch.cuda.Stream(device=cuda)
+    with torch.cuda.stream(stream):
+        # the noise launch alone: captured and eager from the same state write the same means
+        model, cam, batch, opt, strat = _graph_setup(cuda, 31)
+        opt.dev_state[0] = 5.0
+        opt.dev_lr[0] = 1e-3
+        p0 = model.flat_params.detach().clone()
+        strat.inject_noise(device_state=True)
+        eager = model.flat_params.detach().clone()
+        model.flat_params.copy_(p0)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            strat.inject_noise(device_state=True)
+        model.flat_params.copy_(p0)
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(model.flat_params, eager) and not torch.equal(eager, p0)
+
+        runs = []
+        for graphed in (False, True):
+            model, cam, batch, opt, strat = _graph_setup(cuda, 31)
+
+            def step():
+                for prm in model.parameters():
+                    prm.grad = None
+                losses = model.fused_loss(cam, batch, sync=False)
+                model.backward_fused(losses)
+                opt.step(device_state=True)
+                strat.inject_noise(device_state=True)
+                return losses
+
+            if graphed:
+                g = GraphedTrainStep(step, cuda, warmup=2, check_every=1)
+                for _ in range(3):
+                    g.replay()
+            else:
+                for _ in range(5):
+                    step()
+            torch.cuda.synchronize()
+            runs.append(model.flat_params.detach().clone())
+        assert _close_fraction(runs[1], runs[0]) <= 1e-3
+
+        # relocation at the cap: same buffers, the captured step replays on without recapture()
+        ptr = model.flat_params.data_ptr()
+        info_dead = strat.relocate()
+        assert strat.add() == 0 and model.flat_params.data_ptr() == ptr
+        torch.cuda.synchronize()
+        assert int(info_dead) > 0
+        before = model.flat_params.detach().clone()
+        for _ in range(3):
+            out = g.replay()
+        torch.cuda.synchronize()
+        assert torch.isfinite(out["loss"]) and bool(torch.isfinite(model.flat_params).all())
+        assert not torch.equal(before, model.flat_params)
+
+        # growth: new buffers, recaptured, trains on
+        strat.config.cap_max = int(1.05 * model.num_points) + 10
+        n0 = model.num_points
+        assert strat.add() == int(1.05 * n0) - n0
+        g.recapture()
+        for _ in range(2):
+            out = g.replay()
+        torch.cuda.synchronize()
+    assert torch.isfinite(out["loss"]) and model.gauss_params["means"].grad.shape == (model.num_points, 3)
+    assert bool(torch.isfinite(model.flat_params).all()) and opt.exp_avg.numel() == model.flat_params.numel()
+
+
+# ---------------------------------------------------------------------------------------------------
+# GPU: a short training run, and replica determinism
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_short_training_run_reaches_and_keeps_the_cap(cuda):
+    from qed_splatter_amd.mcmc import McmcConfig, McmcStrategy
+    from qed_splatter_amd.model import FlatAdam
+    model, cam, batch = _scene_model(cuda, seed=41, n=2000, strategy="mcmc")
+    opt = FlatAdam(model, means_schedule=FlatAdam.MEANS_SCHEDULE)
+    cap = 2400
+    strat = McmcStrategy(model, opt, McmcConfig(cap_max=cap, refine_start=0, refine_every=10, refine_stop=10 ** 6), seed=2)
+    losses, counts = [], []
+    for step in range(1, 301):
+        for prm in model.parameters():
+            prm.grad = None
+        out = model.fused_loss(cam, batch)
+        model.backward_fused(out)
+        opt.step()
+        info = strat.step_post_backward(step)
+        losses.append(float(out["loss"]))
+        counts.append(info["n_after"])
+    assert counts[-1] == cap and counts.index(cap) < 100 and all(c == cap for c in counts[counts.index(cap):])
+    assert sum(losses[-10:]) / 10 < 0.95 * sum(losses[:10]) / 10, (losses[:3], losses[-3:])
+    assert bool(torch.isfinite(model.flat_params).all()) and bool(torch.isfinite(opt.exp_avg).all())
+    sd = strat.state_dict()
+    assert sd["seed"] == 2 and sd["n_refinements"] == 30 + 4            # 30 relocations, 4 growth steps to the cap
+
+
+@pytest.mark.gpu
+def test_relocate_and_add_are_bit_identical_across_replicas(cuda):
+    from qed_splatter_amd.mcmc import McmcConfig, McmcStrategy
+    p = _params(20000, seed=8, dead_frac=0.05)
+    m, v = _moments(p, seed=9)
+    bufs = []
+    for _ in range(2):
+        model, opt = _model(p, cuda)
+        _set_moments(model, opt, m, v)
+        strat = McmcStrategy(model, opt, McmcConfig(cap_max=10 ** 6), seed=77)
+        n_dead = strat.relocate()
+        n_add = strat.add()
+        strat.inject_noise(step=3)
+        torch.cuda.synchronize()
+        bufs.append((model.flat_params.cpu(), opt.exp_avg.cpu(), opt.exp_avg_sq.cpu(), int(n_dead), n_add))
+    (a, am, av, ad, an), (b, bm, bv, bd, bn) = bufs
+    assert ad == bd > 0 and an == bn == 1000
+    assert torch.equal(a, b) and torch.equal(am, bm) and torch.equal(av, bv)
+    # every dead row took a live source: none is left below min_opacity (a source's new opacity is clamped to it)
+    assert bool((torch.sigmoid(model.opacities.detach().double()) >= MIN_OP * (1 - 1e-6)).all())
