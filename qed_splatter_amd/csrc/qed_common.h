@@ -268,7 +268,7 @@ struct AdamTick {
     float beta1, beta2;
     float* lr_slot;         // NULL, or the scheduled group's learning-rate slot (lr_exp_decay_kernel's formula)
     float log_init, log_final, inv_max_steps;
-    const int* skip;        // NULL, or the word that makes the step a no-op when non-zero (see adam_skipped, loss.hip)
+    const int* skip;        // NULL, or the word that makes the step a no-op when non-zero (see adam_skipped, adam.hip)
 };
 
 __device__ __forceinline__ void adam_tick(const AdamTick& t) {
@@ -483,6 +483,14 @@ inline TileOrderJob tile_order_job(const int* tile_cost, long long grid, int* or
         hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
         n_cu = 256;
     return TileOrderJob{tile_cost, (int)grid, order_ws, 1.0f, n_cu * 4 * QED_K7_WAVES, max_split_tiles(grid)};
+}
+
+// grid of a grid-stride streaming pass: one workgroup per 256 items, at most `cap` (256 CUs x 8 workgroups by default)
+inline unsigned stream_grid(long long n_items, long long cap = 2048) {
+    long long g = (n_items + 255) / 256;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (unsigned)g;
 }
 
 // grid of the two streaming loss passes (pass 2 reads pass 1's per-workgroup partials by index)

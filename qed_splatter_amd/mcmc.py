@@ -50,7 +50,7 @@ class McmcStrategy:
     exchanging anything."""
 
     def __init__(self, model, optimizer, config: Optional[McmcConfig] = None, seed: int = 0):
-        from .model import FlatAdam, QedAdamSet
+        from .optim import FlatAdam, QedAdamSet
         if getattr(model, "_flat", None) is None:
             raise RuntimeError("McmcStrategy needs the flat parameter layout: the model was built with separate_params=True")
         if getattr(model.config, "strategy", "default") != "mcmc":
@@ -150,7 +150,7 @@ class McmcStrategy:
         (seed, step, row), with the step from ``FlatAdam.dev_state`` under ``device_state=True`` (capturable), else
         ``step`` or this object's own count of calls; ``noise`` [N,3] (tests) replaces them.  A step whose frame
         overflowed its intersection buffer (the Adam skip word) adds no noise."""
-        from .model import FlatAdam, _skip_flag
+        from .optim import FlatAdam, _skip_flag
         m, opt = self.model, self.optimizer
         n = m.num_points
         if n == 0:

@@ -76,7 +76,7 @@ class _SegmentFn(torch.autograd.Function):
         # False), a second backward on retained outputs) are aliases of the static buffers the replay is about to overwrite:
         # the engine adopted them without a copy.  They are moved out first, so that AccumulateGrad adds the new gradients
         # to the old values and not to themselves.  (The flat layout of .grad is given up for that step.)
-        from .model import _RAW_GRAD, _raw_grad
+        from .optim import _RAW_GRAD, _raw_grad
         for p, g in zip(seg.params, grads):
             old = _raw_grad(p) if g is not None else None
             if old is not None and old.untyped_storage().data_ptr() == g.untyped_storage().data_ptr():

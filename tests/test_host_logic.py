@@ -259,3 +259,16 @@ def test_lazy_sh_gradients_are_off_whenever_a_c_level_reader_could_see_them(monk
     assert m._lazy_sh_wanted(3, None) is False
     h.remove()
     assert m._lazy_sh_wanted(3, None) is True
+
+
+def test_optimisers_live_in_optim_and_stay_importable_from_model():
+    """qed_splatter_amd.model re-exports the optimiser's public names (bench.py, the scripts and INTEGRATION.md import them
+    from there), and qed_splatter_amd.optim does not import the model when it loads."""
+    import subprocess
+    import sys
+    from qed_splatter_amd import model, optim
+    for name in ("FlatAdam", "QedAdam", "QedAdamSet", "exponential_decay_lr", "_raw_grad", "_FLAT_STATES"):
+        assert getattr(model, name) is getattr(optim, name), name
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = "import sys, qed_splatter_amd.optim; assert 'qed_splatter_amd.model' not in sys.modules"
+    subprocess.run([sys.executable, "-c", code], cwd=root, check=True, timeout=300)
