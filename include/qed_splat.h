@@ -502,6 +502,31 @@ int qed_backproject_depth(int32_t height, int32_t width, const float* depth, flo
                           int64_t capacity, float* points, int32_t* n_points, int32_t* workspace,
                           int32_t* status, void* stream);
 
+/* ---- colouring the initial point cloud (qed-init-pc --colorize; create_init_pointcloud.py:264-390) --------
+ * qed_colorize_accumulate: one batch of F >= 1 frames of one size height x width against N points.
+ *   points[N,3] float; depth[F,H,W] float, the RAW file values: the kernel multiplies by depth_unit_scale_factor in
+ *   fp32 and treats non-finite / <= 0 as "no measurement" (:310-312); color[F,H,W,3] uint8.
+ *   h_c2w_opengl: HOST pointer to F OpenGL camera-to-world poses as 4x4 row-major DOUBLES (transforms.json's
+ *   transform_matrix); the OpenCV world-to-camera matrix of _opengl_c2w_to_opencv_w2c (:59-68) is formed on the host
+ *   by flipping columns 1, 2 and inverting the 4x4 generally in float64, then cast to fp32 (a singular pose is refused).
+ *   h_intrinsics: HOST pointer to F x (fx, fy, cx, cy).
+ *   Per (point, frame): p = w2c [x y z 1] in fp32; z = p.z must be finite and > 1e-6; u = fx (p.x / z) + cx, v
+ *   likewise; finite u, v, z <= depth_max, -0.5 <= u < W - 0.5, -0.5 <= v < H - 0.5; ui = rint(u) (half to even), vi
+ *   likewise; measured = depth[vi, ui]; hit iff measured > 0 && |measured - z| <= max(depth_tolerance,
+ *   depth_tolerance_rel z).  A hit adds float(c / 255) per channel to color_sum[N,3] (float64) and 1 to
+ *   color_count[N] (int32); the caller zeroes both before the first batch.  Each point owns its accumulator and the
+ *   frames are taken in order, so any split of a frame sequence into batches gives bit-identical sums.
+ * qed_colorize_finalize: colors[N,3] uint8 = (uint8) clip(sum / count * 255, 0, 255) in float64, TRUNCATED as
+ *   NumPy's astype(uint8) does (:378-383); points never hit stay (0,0,0); n_colored[1] = number of points with count > 0.
+ * No allocation, no sync; capturable. */
+int qed_colorize_accumulate(int32_t N, const float* points, int32_t F, int32_t height, int32_t width,
+                            const float* depth, float depth_unit_scale_factor, const uint8_t* color,
+                            const double* h_c2w_opengl, const float* h_intrinsics, float depth_max,
+                            float depth_tolerance, float depth_tolerance_rel, double* color_sum,
+                            int32_t* color_count, void* stream);
+int qed_colorize_finalize(int32_t N, const double* color_sum, const int32_t* color_count, uint8_t* colors,
+                          int32_t* n_colored, void* stream);
+
 /* ---- fused multi-tensor Adam over one flat parameter buffer (config.py:44-68) --
  * n_groups contiguous segments; segment g covers elements [h_group_begin[g], h_group_begin[g+1])
  * and uses learning rate h_lr[g].  bias corrections use `step` (1-based).  The betas are doubles: 1 - beta is
