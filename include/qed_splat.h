@@ -527,6 +527,20 @@ int qed_colorize_accumulate(int32_t N, const float* points, int32_t F, int32_t h
 int qed_colorize_finalize(int32_t N, const double* color_sum, const int32_t* color_count, uint8_t* colors,
                           int32_t* n_colored, void* stream);
 
+/* ---- voxel down-sampling of a point cloud (qed-init-pc step 1: per frame, per merge, at the end) ------------
+ * One output point per occupied voxel: the mean of its members.  Voxel of a point = (floorf(x / v), floorf(y / v),
+ * floorf(z / v)) with v = voxel_size and a correctly rounded fp32 division; sums in float64, rounded to fp32 once.
+ * out_points[n,3] receives the means in ascending (ix, iy, iz) order, n_out[1] (device) their number.  The result
+ * is a pure function of the input (no floating-point atomics; a fixed combination order): bit-identical between
+ * calls, streams and occupancies.  A point with a non-finite coordinate is dropped.
+ * status[QED_STATUS_WORDS] (device): [0] = 1 when an axis spans more than 2^21 voxels (62 km at 3 cm): refused,
+ * n_out = 0; [1] = points dropped as non-finite; [2] = the widest axis span in voxels.
+ * Refused on the host: voxel_size not finite or <= 0, n < 0 or >= 2^30, null buffers, a workspace smaller than
+ * qed_voxel_workspace_bytes(n) (8-byte aligned).  n == 0 gives n_out = 0.  No allocation, no sync. */
+int64_t qed_voxel_workspace_bytes(int64_t n);
+int qed_voxel_down_sample(int32_t n, const float* points, float voxel_size, float* out_points, int32_t* n_out,
+                          void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
+
 /* ---- fused multi-tensor Adam over one flat parameter buffer (config.py:44-68) --
  * n_groups contiguous segments; segment g covers elements [h_group_begin[g], h_group_begin[g+1])
  * and uses learning rate h_lr[g].  bias corrections use `step` (1-based).  The betas are doubles: 1 - beta is

@@ -55,6 +55,8 @@ SIGNATURES = {
     "qed_backproject_depth": (C.c_int, [_I, _I, _P, _F, _F, _F, _F, _P, _F, _I, _L, _P, _P, _P, _P, _P]),
     "qed_colorize_accumulate": (C.c_int, [_I, _P, _I, _I, _I, _P, _F, _P, _P, _P, _F, _F, _F, _P, _P, _P]),
     "qed_colorize_finalize": (C.c_int, [_I, _P, _P, _P, _P, _P]),
+    "qed_voxel_workspace_bytes": (_L, [_L]),
+    "qed_voxel_down_sample": (C.c_int, [_I, _P, _F, _P, _P, _P, _L, _P, _P]),
     "qed_image_metrics": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _P, _P]),
     "qed_nanmean_exp": (C.c_int, [_I, _P, _I, _P, _P, _P]),
     "qed_step_metrics": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _I, _F, _P, _I, _I, _P, _F, _F, _F, _P, _P, _P, _P, _P]),

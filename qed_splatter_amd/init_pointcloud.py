@@ -1,11 +1,15 @@
-"""The initial point cloud: the reference's ``qed-init-pc`` tool on the GPU.
+"""The initial point cloud: the reference's ``qed-init-pc`` tool on the GPU, both steps, no Open3D.
 
-Step 1, geometry (create_init_pointcloud.py:148-196).  File handling (PLY caches, the pairwise on-disk merge of
-:100-145) stays with the reference tool; this module replaces the per-frame Open3D calls: ``backproject_depth`` for
-``create_from_depth_image`` and ``voxel_down_sample`` for the method of the same name.
+Step 1, geometry (create_init_pointcloud.py:83-261 and the branch of ``main`` without ``--colorize``):
+``create_pointcloud_from_transforms`` walks the frames of a transforms.json, back-projects each depth map
+(``backproject_depth``, csrc/backproject.hip, for Open3D's ``create_from_depth_image``), thins it with
+``voxel_down_sample`` (csrc/voxel.hip: sort by voxel + segmented float64 means, a pure function of its input, output
+in ascending voxel order) and merges the frames' clouds in the reference's pairwise tree (``tree_merge_pointclouds``,
+in memory: the reference's per-frame PLY cache and on-disk merge levels are not offered).
+``python -m qed_splatter_amd.init_pointcloud --data DIR`` writes the geometry-only ``sparse_pc.ply``.
 
-Step 2, colour (``--colorize``, :264-390), completely: ``PointColorizer`` (csrc/colorize.hip), ``colorize_pointcloud``
-(the reference's frame loop and file rules), a NumPy PLY reader / writer in place of the two ``o3d.t.io`` calls, and
+Step 2, colour (``--colorize``, :264-390): ``PointColorizer`` (csrc/colorize.hip), ``colorize_pointcloud`` (the
+reference's frame loop and file rules), a NumPy PLY reader / writer in place of the two ``o3d.t.io`` calls, and
 ``python -m qed_splatter_amd.init_pointcloud --data DIR --colorize``.
 """
 from __future__ import annotations
@@ -55,10 +59,8 @@ def backproject_depth(depth: Tensor, fx: float, fy: float, cx: float, cy: float,
     return pts[: int(n_pts)]
 
 
-@torch.no_grad()
-def voxel_down_sample(points: Tensor, voxel_size: float) -> Tensor:
-    """One point per occupied voxel: the mean of its members (Open3D semantics).  Device-side torch ops
-    (unique over voxel keys + index_add); offline tool, not a training hot path."""
+def _voxel_down_sample_torch(points: Tensor, voxel_size: float) -> Tensor:
+    """unique over voxel keys + index_add: the body CPU tensors take (on a GPU its sums depend on atomic order)."""
     if points.shape[0] == 0:
         return points
     keys = torch.floor(points / voxel_size).to(torch.int64)
@@ -69,6 +71,144 @@ def voxel_down_sample(points: Tensor, voxel_size: float) -> Tensor:
     out = torch.zeros(counts.shape[0], 3, dtype=points.dtype, device=points.device)
     out.index_add_(0, inv, points)
     return out / counts[:, None].to(points.dtype)
+
+
+@torch.no_grad()
+def voxel_down_sample(points: Tensor, voxel_size: float) -> Tensor:
+    """One point per occupied voxel: the mean of its members (Open3D semantics), in ascending (ix, iy, iz) order of
+    the voxels floor(p / voxel_size).  A tensor on the GPU goes to qed_voxel_down_sample (float64 sums, bit-identical
+    from run to run, points with a non-finite coordinate dropped; one host read: the count and the status words);
+    a CPU tensor to the torch body."""
+    if not points.is_cuda:
+        return _voxel_down_sample_torch(points, voxel_size)
+    lib = L.load()
+    assert points.dim() == 2 and points.shape[1] == 3
+    pts = points.to(torch.float32).contiguous()
+    n = int(pts.shape[0])
+    out = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
+    meta = torch.zeros(1 + L.STATUS_WORDS, dtype=torch.int32, device=pts.device)        # n_out, status[4]
+    ws_bytes = int(lib.qed_voxel_workspace_bytes(n))
+    if ws_bytes < 0:
+        raise L.QedSplatError(f"voxel_down_sample: {n} points are more than one call takes (2^30)")
+    work = torch.empty(ws_bytes // 8 + 1, dtype=torch.int64, device=pts.device)
+    L.check(lib.qed_voxel_down_sample(n, L.ptr(pts), float(voxel_size), L.ptr(out), L.ptr(meta), L.ptr(work),
+                                      work.numel() * 8, L.ptr(meta[1:]), torch.cuda.current_stream().cuda_stream),
+            "qed_voxel_down_sample")
+    n_out, refused, _n_dropped, span, _ = (int(v) for v in meta.tolist())
+    if refused:
+        raise L.QedSplatError(f"voxel_down_sample: the cloud spans {span} voxels of {float(voxel_size):g} m on one axis; "
+                              f"at most 2^21 = {1 << 21} are supported (62 km at 3 cm)")
+    res = out[:n_out]
+    return res.clone() if 2 * n_out < n else res          # (do not keep a frame-sized buffer alive behind a small cloud)
+
+
+# ---- step 1: the frame loop and the merge tree (create_init_pointcloud.py:83-261) --------------------------------------
+def _rows(cloud) -> int:
+    return int(cloud.shape[0])
+
+
+def _concat(left, right):
+    if torch.is_tensor(left):
+        return torch.cat([left, right], dim=0)
+    return np.concatenate([left, right], axis=0)
+
+
+class NoCloudsError(ValueError):
+    """tree_merge_pointclouds was given no cloud at all."""
+
+
+def tree_merge_pointclouds(clouds, voxel_size: float = 0.03, max_points: int = 2_000_000, down_sample_fn=None):
+    """The reference's pairwise merge tree (tree_merge_pointclouds_on_disk, :101-145), in memory: level by level cloud
+    2k (first in the concatenation) with cloud 2k + 1; the concatenation is down-sampled with ``voxel_size`` only if
+    it has more than ``max_points`` rows; an unpaired last cloud moves up unchanged; one cloud in, that cloud out.
+    ``clouds`` may be an iterator: a binary-counter stack (two clouds of one level merge as soon as both exist; at the
+    end the smallest is carried upwards) builds exactly that tree while holding O(log F) clouds."""
+    if down_sample_fn is None:
+        down_sample_fn = voxel_down_sample
+
+    def merge(left, right):
+        merged = _concat(left, right)
+        return down_sample_fn(merged, voxel_size) if _rows(merged) > max_points else merged
+
+    stack = []                                   # (level, cloud), levels strictly decreasing towards the top
+    for cloud in clouds:
+        level = 0
+        while stack and stack[-1][0] == level:
+            cloud = merge(stack.pop()[1], cloud)
+            level += 1
+        stack.append((level, cloud))
+    if not stack:
+        raise NoCloudsError("tree_merge_pointclouds: no clouds")
+    level, cloud = stack.pop()                   # the unpaired last cloud of its level: carried up to the next partner
+    while stack:
+        level, left = stack.pop()
+        cloud = merge(left, cloud)
+    return cloud
+
+
+def _backproject_on_gpu(device):
+    def fn(depth, fx, fy, cx, cy, c2w_opengl, depth_max, stride):
+        return backproject_depth(torch.from_numpy(depth).to(device), fx, fy, cx, cy,
+                                 torch.as_tensor(np.asarray(c2w_opengl, dtype=np.float64)), depth_max=depth_max,
+                                 stride=stride)
+    return fn
+
+
+def create_pointcloud_from_transforms(dataset_path, depth_unit_scale_factor: float = 0.001, voxel_size: float = 0.05,
+                                      merge_voxel_size: float = 0.03, frame_voxel_size=0.05,
+                                      max_points: int = 2_000_000, depth_max: float = 100.0, stride: int = 1,
+                                      device=None, backproject_fn=None, down_sample_fn=None,
+                                      verbose: bool = True) -> np.ndarray:
+    """The reference's create_pointcloud_from_transforms (:199-261) without its disk cache -> positions [n,3] float32.
+    Frames without ``depth_file_path`` are not used; depth = file * depth_unit_scale_factor in fp32 with non-finite
+    and <= 0 values zeroed; a frame with no positive depth or an empty cloud is skipped; each frame's cloud is thinned
+    with ``frame_voxel_size`` (None or <= 0: not), the clouds go through ``tree_merge_pointclouds`` with
+    ``merge_voxel_size`` / ``max_points``, and the result is ALWAYS down-sampled once more with ``voxel_size``.
+    ``backproject_fn(depth, fx, fy, cx, cy, c2w_opengl, depth_max, stride)`` and ``down_sample_fn(points, voxel_size)``
+    default to the GPU functions (tests substitute a NumPy oracle's)."""
+    dataset_path = Path(dataset_path)
+    contents = load_transforms(dataset_path)
+    say = print if verbose else (lambda *a, **k: None)
+    if backproject_fn is None:
+        backproject_fn = _backproject_on_gpu(torch.device(device if device is not None else "cuda"))
+    if down_sample_fn is None:
+        down_sample_fn = voxel_down_sample
+    n_used = [0]
+
+    def frame_clouds():
+        for frame in contents["frames"]:
+            if "depth_file_path" not in frame:
+                continue
+            depth_path = dataset_path / frame["depth_file_path"]
+            say(f"Backprojecting {depth_path}")
+            depth = load_depth(depth_path) * depth_unit_scale_factor
+            depth[~np.isfinite(depth)] = 0.0
+            depth[depth <= 0.0] = 0.0
+            depth = np.ascontiguousarray(depth, dtype=np.float32)
+            if not np.any(depth > 0.0):
+                say(f"  Skipping frame with no valid depth: {depth_path}")
+                continue
+            fx, fy, cx, cy = frame_intrinsics(contents, frame)
+            cloud = backproject_fn(depth, fx, fy, cx, cy, np.array(frame["transform_matrix"], dtype=np.float64),
+                                   depth_max, stride)
+            if _rows(cloud) == 0:
+                say(f"  Skipping empty point cloud for {depth_path}")
+                continue
+            if frame_voxel_size is not None and frame_voxel_size > 0:
+                cloud = down_sample_fn(cloud, frame_voxel_size)
+            say(f"  {_rows(cloud)} points")
+            n_used[0] += 1
+            yield cloud
+
+    try:
+        merged = tree_merge_pointclouds(frame_clouds(), voxel_size=merge_voxel_size, max_points=max_points,
+                                        down_sample_fn=down_sample_fn)
+    except NoCloudsError:
+        raise RuntimeError("No valid point clouds could be generated from the dataset.") from None
+    say(f"Merged {n_used[0]} frame point clouds: {_rows(merged)} points")
+    final = down_sample_fn(merged, voxel_size)
+    final = final.cpu().numpy() if torch.is_tensor(final) else np.asarray(final)
+    return np.ascontiguousarray(final, dtype=np.float32)
 
 
 # ---- step 2: colour (create_init_pointcloud.py:264-390) ----------------------------------------------------------------
@@ -283,7 +423,7 @@ def write_ply(path, positions: np.ndarray, colors: np.ndarray = None) -> None:
         f.write(rec.tobytes())
 
 
-# ---- the command line of the colourise branch (create_init_pointcloud.py:393-511) -------------------------------------
+# ---- the command line (create_init_pointcloud.py:393-511) ---------------------------------------------------------------
 def update_transforms_ply_path(dataset_path, output_name: str) -> None:
     transforms_path = Path(dataset_path) / "transforms.json"
     with open(transforms_path, encoding="utf-8") as f:
@@ -304,19 +444,35 @@ def resolve_dataset_path(data) -> Path:
     raise ValueError(f"Expected a dataset directory or transforms.json, got: {data}")
 
 
+def _optional_voxel(text: str):
+    """``--frame-voxel-size``: a size in metres; ``none`` or 0 turns the per-frame down-sampling off."""
+    if text.strip().lower() == "none":
+        return None
+    value = float(text)
+    return value if value > 0 else None
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m qed_splatter_amd.init_pointcloud",
-                                description="Colourise an initialisation point cloud from a dataset's RGB-D frames "
-                                            "(the --colorize step of qed-init-pc) on the GPU.")
+                                description="Build an initialisation point cloud from a dataset's depth frames (step "
+                                            "1), or with --colorize colour an existing one from its RGB-D frames "
+                                            "(step 2): qed-init-pc on the GPU.")
     p.add_argument("--data", type=Path, required=True, help="dataset directory, or path to transforms.json")
-    p.add_argument("--colorize", action="store_true", help="colourise an existing point cloud (the only step this tool has)")
-    p.add_argument("--input-name", default="sparse_pc.ply", help="input PLY inside the dataset directory")
+    p.add_argument("--colorize", action="store_true", help="colourise an existing point cloud instead of building one")
+    p.add_argument("--input-name", default="sparse_pc.ply", help="--colorize: input PLY inside the dataset directory")
     p.add_argument("--output-name", default="sparse_pc.ply", help="output PLY written into the dataset directory")
     p.add_argument("--depth-unit-scale-factor", type=float, default=0.001, help="raw depth -> metres (0.001: millimetres)")
-    p.add_argument("--depth-max", type=float, default=100.0, help="largest depth (metres) a colour check accepts")
-    p.add_argument("--depth-tolerance", type=float, default=0.05, help="absolute depth consistency tolerance, metres")
-    p.add_argument("--depth-tolerance-rel", type=float, default=0.02, help="relative tolerance (fraction of z)")
-    p.add_argument("--batch-frames", type=int, default=8, help="frames per kernel launch")
+    p.add_argument("--depth-max", type=float, default=100.0, help="largest depth (metres) that is used")
+    p.add_argument("--voxel-size", type=float, default=0.05, help="step 1: voxel size of the final down-sampling, metres")
+    p.add_argument("--merge-voxel-size", type=float, default=0.03,
+                   help="step 1: voxel size for merges that exceed --max-points")
+    p.add_argument("--frame-voxel-size", type=_optional_voxel, default=0.05,
+                   help="step 1: voxel size of the per-frame down-sampling ('none' or 0: off)")
+    p.add_argument("--max-points", type=int, default=2_000_000, help="step 1: a merge above this many points is down-sampled")
+    p.add_argument("--stride", type=int, default=4, help="step 1: use every stride-th pixel of a depth map")
+    p.add_argument("--depth-tolerance", type=float, default=0.05, help="--colorize: absolute depth consistency tolerance, metres")
+    p.add_argument("--depth-tolerance-rel", type=float, default=0.02, help="--colorize: relative tolerance (fraction of z)")
+    p.add_argument("--batch-frames", type=int, default=8, help="--colorize: frames per kernel launch")
     p.add_argument("--update-transforms", dest="update_transforms", action="store_true", default=True,
                    help="set transforms.json ply_file_path to the output PLY (default)")
     p.add_argument("--no-update-transforms", dest="update_transforms", action="store_false")
@@ -325,10 +481,18 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
-    if not args.colorize:
-        raise SystemExit("only --colorize is implemented here: back-project with backproject_depth / the reference "
-                         "tool first, then colourise")
     dataset_path = resolve_dataset_path(args.data)
+    output_path = dataset_path / args.output_name
+    if not args.colorize:
+        positions = create_pointcloud_from_transforms(
+            dataset_path, depth_unit_scale_factor=args.depth_unit_scale_factor, voxel_size=args.voxel_size,
+            merge_voxel_size=args.merge_voxel_size, frame_voxel_size=args.frame_voxel_size, max_points=args.max_points,
+            depth_max=args.depth_max, stride=args.stride)
+        print(f"Writing {positions.shape[0]} points to {output_path}")
+        write_ply(output_path, positions)
+        if args.update_transforms:
+            update_transforms_ply_path(dataset_path, args.output_name)
+        return
     input_path = dataset_path / args.input_name
     if not input_path.exists():
         raise FileNotFoundError(f"Input point cloud not found: {input_path}. Back-project depth first.")
@@ -338,7 +502,6 @@ def main(argv=None) -> None:
                                  depth_unit_scale_factor=args.depth_unit_scale_factor, depth_max=args.depth_max,
                                  depth_tolerance=args.depth_tolerance, depth_tolerance_rel=args.depth_tolerance_rel,
                                  batch_frames=args.batch_frames)
-    output_path = dataset_path / args.output_name
     print(f"Writing {positions.shape[0]} points with colors to {output_path}")
     write_ply(output_path, positions, colors)
     if args.update_transforms:
