@@ -541,6 +541,46 @@ int64_t qed_voxel_workspace_bytes(int64_t n);
 int qed_voxel_down_sample(int32_t n, const float* points, float voxel_size, float* out_points, int32_t* n_out,
                           void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
 
+/* ---- exact nearest neighbours between two point clouds, and PDMetrics' reductions (metrics.py:9-63) -------------
+ * For every query point: the distance to, and the row of, the nearest point of the target cloud (what cKDTree.query
+ * returns with k = 1).  Points are [n,3] fp32 and finite (the caller checks: a non-finite coordinate makes that row's
+ * result unspecified, though every access stays in bounds; status[1] of qed_nn_build counts the target's).
+ * The result is defined once: d2 = fma(dz, dz, fma(dy, dy, dx * dx)) on fp32 differences target - query, distance =
+ * sqrtf(d2), and among targets of equal fp32 d2 the smallest row wins.  The grid path and the brute-force path both
+ * return exactly that, bit for bit, whatever the cell size, max_rings, the order of the queries or of the launches'
+ * workgroups (integer min only; no floating-point atomics).
+ * qed_nn_build: a sparse uniform grid over the target in `workspace` (qed_nn_workspace_bytes(n_target,
+ *   n_query_capacity) bytes, 16-byte aligned; it also holds the scratch of qed_nn_query for up to n_query_capacity
+ *   queries).  cell_size > 0, or flags = QED_NN_AUTO_CELL: chosen on the device so that an occupied cell holds a
+ *   handful of points (cell_size is then ignored).  A cell size that would need more than 2^20 cells on an axis is
+ *   enlarged: no finite cloud is refused.  status[QED_STATUS_WORDS] (device): [1] = non-finite target points.
+ * qed_nn_query: the grid search.  Shells of cells of growing Chebyshev radius around the query's cell until the best
+ *   distance cannot be beaten from outside the visited box (exact).  A query not finished after max_rings shells is
+ *   NOT written; its row goes to fallback[1 ..], fallback[0] (device) = their number (fallback: 1 + n_query int32).
+ *   Pass that list to qed_nn_brute with the same dist / idx.  `target` is not needed: the index holds a copy.
+ *   flags: QED_NN_NATURAL_ORDER takes the queries in row order instead of the order of their cell in the target's grid.
+ * qed_nn_brute: every target against the rows of `rows` (rows[0] = count on the device, rows[1 ..] = row ids; the
+ *   other rows of dist / idx are left alone) or, rows == NULL, against all n_query rows.  workspace: 8 n_query bytes.
+ * qed_pd_reduce: count_under[0] (device int64) = number of dist[i] whose float64 value is < threshold; order_stats[2]
+ *   (device) = the k0-th and the min(k0 + 1, n - 1)-th smallest distance (0-based): the two NumPy's "linear" percentile
+ *   reads at k0 = floor((n - 1) p / 100).  workspace: qed_pd_workspace_bytes(n).
+ * Refused on the host: counts out of range (n_target < 1, n < 1, negative or >= 2^30), cell_size not finite or <= 0
+ * without QED_NN_AUTO_CELL, max_rings outside [0, 64], unknown flags, null buffers, a short workspace.
+ * No allocation, no sync. */
+#define QED_NN_NATURAL_ORDER 1
+#define QED_NN_AUTO_CELL 2
+int64_t qed_nn_workspace_bytes(int64_t n_target, int64_t n_query_capacity);
+int qed_nn_build(int32_t n_target, const float* target, float cell_size, int32_t flags, void* workspace,
+                 int64_t workspace_bytes, int64_t n_query_capacity, int32_t* status, void* stream);
+int qed_nn_query(int32_t n_query, const float* query, int32_t n_target, void* workspace, int64_t workspace_bytes,
+                 int64_t n_query_capacity, int32_t max_rings, int32_t flags, float* dist, int32_t* idx,
+                 int32_t* fallback, void* stream);
+int qed_nn_brute(int32_t n_query, const float* query, int32_t n_target, const float* target, const int32_t* rows,
+                 float* dist, int32_t* idx, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t qed_pd_workspace_bytes(int64_t n);
+int qed_pd_reduce(int32_t n, const float* dist, double threshold, int64_t k0, int64_t* count_under,
+                  float* order_stats, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- fused multi-tensor Adam over one flat parameter buffer (config.py:44-68) --
  * n_groups contiguous segments; segment g covers elements [h_group_begin[g], h_group_begin[g+1])
  * and uses learning rate h_lr[g].  bias corrections use `step` (1-based).  The betas are doubles: 1 - beta is

@@ -57,6 +57,12 @@ SIGNATURES = {
     "qed_colorize_finalize": (C.c_int, [_I, _P, _P, _P, _P, _P]),
     "qed_voxel_workspace_bytes": (_L, [_L]),
     "qed_voxel_down_sample": (C.c_int, [_I, _P, _F, _P, _P, _P, _L, _P, _P]),
+    "qed_nn_workspace_bytes": (_L, [_L, _L]),
+    "qed_nn_build": (C.c_int, [_I, _P, _F, _I, _P, _L, _L, _P, _P]),
+    "qed_nn_query": (C.c_int, [_I, _P, _I, _P, _L, _L, _I, _I, _P, _P, _P, _P]),
+    "qed_nn_brute": (C.c_int, [_I, _P, _I, _P, _P, _P, _P, _P, _L, _P]),
+    "qed_pd_workspace_bytes": (_L, [_L]),
+    "qed_pd_reduce": (C.c_int, [_I, _P, _D, _L, _P, _P, _P, _L, _P]),
     "qed_image_metrics": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _P, _P]),
     "qed_nanmean_exp": (C.c_int, [_I, _P, _I, _P, _P, _P]),
     "qed_step_metrics": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _I, _F, _P, _I, _I, _P, _F, _F, _F, _P, _P, _P, _P, _P]),
@@ -124,6 +130,7 @@ SH_JAC_FLOATS = 10            # QED_SH_JAC_FLOATS
 STATUS_WORDS = 4
 TILE = 16
 CL_TILE_WAVES, CL_QUADRANT_WAVES, CL_HALF_AND_HALF, CL_NO_CULL, CL_ORDER_READY = 1, 2, 3, 4, 8
+NN_NATURAL_ORDER, NN_AUTO_CELL = 1, 2
 BIN_AUTO, BIN_TWO_STAGE, BIN_TILE_SORT, BIN_BUCKET = 0, 1, 2, 3
 
 

@@ -8,8 +8,9 @@ the seven depth metrics, ``qed_ssim_fwd`` produces SSIM, and everything stays in
 caller decides to log it.
 
 LPIPS needs the pretrained AlexNet/VGG weights torchmetrics downloads; it is not provided and the
-``lpips`` slot is NaN.  The point-cloud metrics of metrics.py:10-63 (cKDTree, CPU, offline) are out
-of scope.
+``lpips`` slot is NaN.  The point-cloud metrics of metrics.py:9-63 (``PDMetrics``, ``calculate_accuracy``,
+``calculate_completeness``: cKDTree on the CPU in the reference) live in ``pointcloud_metrics.py`` on top of the
+nearest-neighbour kernels of ``csrc/nn.hip``; ``mean_angular_error`` (metrics.py:66-80) is below, as plain torch.
 """
 from __future__ import annotations
 
@@ -25,6 +26,13 @@ METRIC_NAMES = ("rgb_mse", "rgb_psnr", "depth_abs_rel", "depth_sq_rel", "depth_r
 
 
 _stream = L.current_stream
+
+
+def mean_angular_error(pred: Tensor, gt: Tensor) -> Tensor:
+    """Angle in radians between the rows of ``pred`` and ``gt`` ([B, C], unit vectors), one per row (metrics.py:66-80:
+    despite its name the reference returns the per-row angles, not their mean).  The dot product is clamped to
+    [-1, 1] first, so that one that rounds above 1 gives 0 and not NaN.  Elementwise: plain torch, no kernel."""
+    return torch.acos(torch.clamp(torch.sum(gt * pred, dim=1), -1.0, 1.0))
 
 
 def image_metrics(pred_rgb: Optional[Tensor], gt_rgb: Optional[Tensor], pred_depth: Optional[Tensor] = None,
