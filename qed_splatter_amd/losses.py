@@ -1,0 +1,349 @@
+"""The image losses of a training step as autograd nodes over the loss kernels: the stand-alone SSIM (``ssim``), the
+statements around the operator (``_PostProcess``), get_loss_dict's two terms (``_ImageLosses``), the fused step's K8 node
+(``_FusedImageLoss``) and splatfacto's MCMC regularisers (``_McmcReg``), with the helpers that prepare their inputs and
+scratch buffers.  Nothing in here touches the model: ``model.py`` and ``metrics.py`` call in, this module imports the
+library binding only."""
+from __future__ import annotations
+
+import os
+from typing import Dict
+
+import torch
+from torch import Tensor
+
+from . import _lib as L
+
+_stream = L.current_stream
+
+_UNIT_GRADS: Dict = {}
+
+
+def _unit_grad(device) -> Tensor:
+    """One cached 0-dim tensor 1.0 per device: the seed gradient of backward_fused()."""
+    one = _UNIT_GRADS.get(device)
+    if one is None:
+        one = _UNIT_GRADS[device] = torch.ones((), dtype=torch.float32, device=device)
+    return one
+
+
+def _ssim_n_out(H: int, W: int) -> float:
+    """The number of values of the valid-window SSIM map of an [H,W,3] image, which its mean divides by."""
+    return 3.0 * (H - 10) * (W - 10)
+
+
+def ssim_buffers(H: int, W: int, device, with_maps: bool = True):
+    """Scratch of one SSIM forward pass over an [H,W,3] image: (coefficient maps of the backward pass, or None without
+    ``with_maps``; per-workgroup map sums; n_out = the number of values of the valid-window map, which its mean divides by)."""
+    lib = L.load()
+    n_maps = lib.qed_ssim_maps_floats(H, W)
+    if n_maps < 0:
+        raise L.QedSplatError("image smaller than the 11 x 11 SSIM window")
+    maps = torch.empty(n_maps, dtype=torch.float32, device=device) if with_maps else None
+    ssum = torch.empty(lib.qed_ssim_sum_floats(H, W), dtype=torch.float32, device=device)
+    return maps, ssum, _ssim_n_out(H, W)
+
+
+class _SSIM(torch.autograd.Function):
+    """SSIM(pred, gt) of two [H,W,3] images with pytorch_msssim semantics (the parent's
+    ``self.ssim``), value + gradient w.r.t. pred from ssim.hip."""
+
+    @staticmethod
+    def forward(ctx, pred, gt):
+        lib = L.load()
+        H, W, _ = pred.shape
+        pred, gt = pred.contiguous(), gt.contiguous()
+        maps, ssum, n_out = ssim_buffers(H, W, pred.device)
+        L.check(lib.qed_ssim_fwd(H, W, 3, L.ptr(pred), None, None, L.ptr(gt), None, L.ptr(maps), L.ptr(ssum),
+                                 _stream()), "qed_ssim_fwd")
+        ctx.save_for_backward(pred, gt, maps)
+        return ssum.sum() / n_out
+
+    @staticmethod
+    def backward(ctx, v):
+        pred, gt, maps = ctx.saved_tensors
+        H, W, _ = pred.shape
+        v_pred = torch.empty_like(pred)
+        v = v.to(torch.float32).reshape(1).contiguous()            # upstream gradient, multiplied inside the kernel
+        L.check(L.load().qed_ssim_bwd(H, W, 3, L.ptr(pred), None, None, L.ptr(gt), None, L.ptr(maps),
+                                      1.0 / _ssim_n_out(H, W), L.ptr(v), L.ptr(v_pred), _stream()),
+                "qed_ssim_bwd")
+        return v_pred, None
+
+
+def ssim(pred: Tensor, gt: Tensor) -> Tensor:
+    """Mean SSIM of two float32 [H,W,3] images in [0,1] (differentiable in ``pred``)."""
+    assert pred.dim() == 3 and pred.shape[-1] == 3 and pred.shape == gt.shape
+    return _SSIM.apply(pred.to(torch.float32), gt.to(torch.float32))
+
+
+def _f32_image(t: Tensor, numel: int, what: str, dev) -> Tensor:
+    """A batch tensor as the kernels read it: float32, contiguous, on the model's device, ``numel`` elements
+    (bool masks and uint8 images are converted; anything of another size is refused before a launch)."""
+    if t.dtype == torch.uint8 and what != "mask":
+        t = t.float() / 255.0
+    t = t.to(device=dev, dtype=torch.float32).contiguous()
+    if t.numel() != numel:
+        raise L.QedSplatError(f"{what}: {tuple(t.shape)} holds {t.numel()} values, the render needs {numel}")
+    return t
+
+
+def _ssim_key(pred: Tensor, gt: Tensor):
+    """What identifies the inputs of an SSIM forward: address, version and shape of both images."""
+    return (pred.data_ptr(), pred._version, tuple(pred.shape), gt.data_ptr(), gt._version, tuple(gt.shape))
+
+
+class _PostProcess(torch.autograd.Function):
+    """model.py:295-297 + 304-306 as ONE node: rgb = clamp(render[..., :3] + (1 - alpha) background, 0, 1) and
+    depth = where(alpha > 0, render[..., 3:4], render[..., 3:4].detach().max())."""
+
+    @staticmethod
+    def forward(ctx, render, alpha, background):
+        lib = L.load()
+        ctx.set_materialize_grads(False)
+        if not render.is_cuda:
+            raise L.QedSplatError("get_outputs needs GPU tensors: there is no CPU path in the product")
+        C, H, W, CH = render.shape
+        dev = render.device
+        render, alpha = render.contiguous(), alpha.contiguous()
+        background = background.to(torch.float32).contiguous()
+        rgb = torch.empty(C, H, W, 3, dtype=torch.float32, device=dev)
+        depth = torch.empty(C, H, W, 1, dtype=torch.float32, device=dev) if CH == 4 else None
+        ws = torch.empty(L.LOSS_SUMS_FLOATS, dtype=torch.float32, device=dev) if CH == 4 else None
+        L.check(lib.qed_post_process_fwd(C * H * W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(rgb),
+                                         L.ptr(depth), L.ptr(ws), _stream()), "qed_post_process_fwd")
+        ctx.save_for_backward(render, alpha, background)
+        if depth is None:
+            return rgb
+        return rgb, depth
+
+    @staticmethod
+    def backward(ctx, v_rgb, v_depth=None):
+        render, alpha, background = ctx.saved_tensors
+        C, H, W, CH = render.shape
+        if v_rgb is None and v_depth is None:
+            return None, None, None
+        v_rgb = v_rgb.to(torch.float32).contiguous() if v_rgb is not None else None
+        v_depth = v_depth.to(torch.float32).contiguous() if v_depth is not None else None
+        v_render = torch.empty_like(render)
+        v_alpha = torch.empty_like(alpha)
+        L.check(L.load().qed_post_process_bwd(C * H * W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(v_rgb),
+                                              L.ptr(v_depth), L.ptr(v_render), L.ptr(v_alpha), _stream()),
+                "qed_post_process_bwd")
+        return v_render, v_alpha, None
+
+
+class _ImageLosses(torch.autograd.Function):
+    """get_loss_dict on the images get_outputs returned: the parent's main loss (1 - l) L1 + l (1 - SSIM) with the
+    mask multiplied into both images (behind model.py:83-85) and the masked depth-L1 term (model.py:87-116), as two
+    scalars.  The trainer sums the loss dict and differentiates, possibly with weights or a GradScaler: the backward
+    multiplies each term's gradient by its upstream gradient, read from device memory."""
+
+    @staticmethod
+    def forward(ctx, rgb, depth, gt_rgb, gt_depth, mask, ssim_lambda, depth_lambda, ssim_shared=None, loss_shared=None,
+                vsplat=None, grad_out=None):
+        lib = L.load()
+        ctx.set_materialize_grads(False)
+        # (holder, rows, static buffer | None): the compositing backward's accumulator, zeroed by this node's backward launch
+        ctx.vsplat = vsplat
+        ctx.grad_out = grad_out   # (v_rgb, v_depth) static buffers of a captured get_outputs segment, or None
+        if not rgb.is_cuda:
+            raise L.QedSplatError("get_loss_dict needs GPU tensors: there is no CPU path in the product")
+        H, W, _ = rgb.shape
+        dev = rgb.device
+        n_pix = H * W
+        rgb = rgb.contiguous()
+        depth = depth.contiguous() if depth is not None else None
+        st = _stream()
+        if loss_shared is not None and ssim_shared is not None:
+            # get_metrics_dict ran qed_step_metrics on these very images a moment ago: the sums and the two losses exist
+            sums, losses = loss_shared
+            maps = ssim_shared[0]
+            ctx.save_for_backward(rgb, depth, gt_rgb, gt_depth, mask, maps, sums)
+            ctx.lams = (float(ssim_lambda), float(depth_lambda))
+            return losses[0:1].view(()), losses[1:2].view(())
+        sums = torch.empty(L.LOSS_SUMS_FLOATS, dtype=torch.float32, device=dev)
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        maps = None
+        extra = (None, 0, 0.0, 0.0)
+        if ssim_lambda > 0.0:
+            if ssim_shared is not None:
+                # get_metrics_dict ran qed_ssim_fwd on these very images a moment ago (rgb_ssim, model.py:157-166) and
+                # kept the coefficient maps: the loss needs the same map sum and the same maps
+                maps, ssum = ssim_shared
+                n_out = _ssim_n_out(H, W)
+            else:
+                maps, ssum, n_out = ssim_buffers(H, W, dev)
+                L.check(lib.qed_ssim_fwd(H, W, 3, L.ptr(rgb), None, None, L.ptr(gt_rgb), L.ptr(mask), L.ptr(maps),
+                                         L.ptr(ssum), st), "qed_ssim_fwd")
+            extra = (L.ptr(ssum), ssum.numel(), -ssim_lambda / n_out, ssim_lambda)
+        L.check(lib.qed_image_losses_fwd(n_pix, L.ptr(rgb), L.ptr(depth), L.ptr(gt_rgb), L.ptr(gt_depth), L.ptr(mask),
+                                         1.0 - ssim_lambda, depth_lambda, *extra, L.ptr(sums), L.ptr(losses), st),
+                "qed_image_losses_fwd")
+        ctx.save_for_backward(rgb, depth, gt_rgb, gt_depth, mask, maps, sums)
+        ctx.lams = (float(ssim_lambda), float(depth_lambda))
+        return losses[0:1].view(()), losses[1:2].view(())
+
+    @staticmethod
+    def backward(ctx, g_main, g_depth):
+        lib = L.load()
+        rgb, depth, gt_rgb, gt_depth, mask, maps, sums = ctx.saved_tensors
+        ssim_lambda, depth_lambda = ctx.lams
+        H, W, _ = rgb.shape
+        st = _stream()
+
+        def scalar(g):
+            return None if g is None else g.to(torch.float32).reshape(1).contiguous()
+        g_main, g_depth = scalar(g_main), scalar(g_depth)
+        sv_rgb, sv_depth = ctx.grad_out if ctx.grad_out is not None else (None, None)
+
+        def out_like(t, static):
+            return static if (static is not None and static.shape == t.shape) else torch.empty_like(t)
+        v_rgb = out_like(rgb, sv_rgb) if (g_main is not None and ctx.needs_input_grad[0]) else None
+        v_depth = out_like(depth, sv_depth) if (g_depth is not None and depth is not None and ctx.needs_input_grad[1]) \
+            else None
+        if v_rgb is not None and ssim_lambda > 0.0:
+            # ONE launch: the L1 term joins the SSIM term inside the SSIM backward pass, the depth term rides along
+            n_out = _ssim_n_out(H, W)
+            zero = None
+            if ctx.vsplat is not None:
+                holder, rows, static = ctx.vsplat
+                zero = static if static is not None else \
+                    torch.empty(rows, L.VSPLAT_FLOATS, dtype=torch.float32, device=rgb.device)
+            L.check(lib.qed_image_losses_ssim_bwd(H, W, L.ptr(rgb), L.ptr(depth), L.ptr(gt_rgb), L.ptr(gt_depth),
+                                                  L.ptr(mask), L.ptr(maps), L.ptr(sums), 1.0 - ssim_lambda, depth_lambda,
+                                                  -ssim_lambda / n_out, L.ptr(g_main), L.ptr(g_depth), L.ptr(v_rgb),
+                                                  L.ptr(v_depth), L.ptr(zero), zero.numel() if zero is not None else 0, st),
+                    "qed_image_losses_ssim_bwd")
+            if zero is not None:
+                del holder[:]
+                holder.append(zero)
+        else:
+            L.check(lib.qed_image_losses_bwd(H * W, L.ptr(rgb), L.ptr(depth), L.ptr(gt_rgb), L.ptr(gt_depth), L.ptr(mask),
+                                             L.ptr(sums), 1.0 - ssim_lambda, depth_lambda, L.ptr(g_main), L.ptr(g_depth), 0,
+                                             L.ptr(v_rgb), L.ptr(v_depth), st), "qed_image_losses_bwd")
+        return v_rgb, v_depth, None, None, None, None, None, None, None, None, None
+
+
+class _FusedImageLoss(torch.autograd.Function):
+    """K8: composite + clamp + depth fix-up + L1 RGB + (1 - SSIM) + masked depth-L1, value and gradient
+    (model.py:295-297, 304-306, 87-116 and the parent's main loss behind :83-85)."""
+
+    @staticmethod
+    def forward(ctx, render, alpha, background, gt_rgb, gt_depth, mask, ssim_lambda, depth_lambda, vsplat_holder=None,
+                vsplat_rows=0, tick=None, tile_cost=None, order_buf=None):
+        import ctypes
+        lib = L.load()
+        ctx.set_materialize_grads(False)
+        C, H, W, CH = render.shape
+        assert C == 1, "one camera per training step (model.py:211)"
+        dev = render.device
+        n_pix = H * W
+        sums = torch.empty(L.LOSS_SUMS_FLOATS, dtype=torch.float32, device=dev)
+        losses = torch.empty(3, dtype=torch.float32, device=dev)       # rgb term, depth term, total
+        v_render = torch.empty_like(render)
+        v_alpha = torch.empty_like(alpha)
+        st = _stream()
+        args = (n_pix, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(gt_rgb), L.ptr(gt_depth), L.ptr(mask))
+        if ssim_lambda > 0.0:
+            # main = (1 - l) L1 + l (1 - SSIM): ONE launch forms the SSIM gradient w.r.t. the clamped colour and pushes
+            # it, with the L1 part and the depth term, through the clamp / background composite (qed_loss_grad_ssim)
+            # the same launch zeroes the accumulator the compositing backward will add into (no fill launch there)
+            vsplat = None
+            if vsplat_holder is not None and vsplat_rows > 0:
+                vsplat = torch.empty(vsplat_rows, L.VSPLAT_FLOATS, dtype=torch.float32, device=dev)
+            maps, ssum, n_out = ssim_buffers(H, W, dev)
+            # The SSIM forward launch carries two passengers that would otherwise be launches of their own on the step's
+            # critical chain: pass 1 of the image loss (qed_loss_reduce: ~9 us) and -- the forward pass's per-tile costs
+            # are known by now -- the compositing backward's launch order (~10 us in front of that kernel).
+            order_ws = None
+            if vsplat_holder is not None and tile_cost is not None:
+                # (the camera's persistent launch-order buffer when the caller keeps one: model.fused_loss, frame_key)
+                order_ws = order_buf if (order_buf is not None and order_buf.numel() == tile_cost.shape[0] + 1) else \
+                    torch.empty(tile_cost.shape[0] + 1, dtype=torch.int32, device=dev)
+            if os.environ.get("QED_STEP_PASSENGERS", "1") == "0":          # measurement hook: every job a launch of its own
+                L.check(lib.qed_loss_reduce(*args, L.ptr(sums), st), "qed_loss_reduce")
+                L.check(lib.qed_ssim_fwd(H, W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(gt_rgb),
+                                         L.ptr(mask), L.ptr(maps), L.ptr(ssum), st), "qed_ssim_fwd")
+                order_ws = None
+            else:
+                L.check(lib.qed_ssim_fwd_step(H, W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(gt_rgb),
+                                            L.ptr(mask), L.ptr(maps), L.ptr(ssum), L.ptr(tile_cost) if order_ws is not None else None,
+                                            tile_cost.shape[0] if order_ws is not None else 0, L.ptr(order_ws),
+                                            L.ptr(gt_depth), L.ptr(sums), st), "qed_ssim_fwd_step")
+            L.check(lib.qed_loss_grad_ssim(H, W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(gt_rgb),
+                                           L.ptr(gt_depth), L.ptr(mask), L.ptr(maps), L.ptr(sums), 1.0 - ssim_lambda,
+                                           depth_lambda, -ssim_lambda / n_out, L.ptr(v_render), L.ptr(v_alpha),
+                                           L.ptr(losses), L.ptr(ssum), ssum.numel(), ssim_lambda, L.ptr(vsplat),
+                                           vsplat.numel() if vsplat is not None else 0,
+                                           ctypes.addressof(tick) if tick is not None else None, st), "qed_loss_grad_ssim")
+            if vsplat is not None or order_ws is not None:
+                del vsplat_holder[:]
+                vsplat_holder.append({"vsplat": vsplat, "order_ws": order_ws})
+        else:
+            L.check(lib.qed_loss_reduce(*args, L.ptr(sums), st), "qed_loss_reduce")
+            L.check(lib.qed_loss_grad(*args, L.ptr(sums), 1.0, depth_lambda, L.ptr(v_render), L.ptr(v_alpha),
+                                      L.ptr(losses), None, None, 0, 0.0, 0.0, st), "qed_loss_grad")
+        ctx.save_for_backward(v_render, v_alpha)
+        total = losses[2:3].view(())
+        parts = losses[0:2]
+        ctx.mark_non_differentiable(parts)
+        return total, parts
+
+    @staticmethod
+    def backward(ctx, v_total, _v_parts):
+        if v_total is None:
+            return (None,) * 13
+        v_render, v_alpha = ctx.saved_tensors
+        # the kernel wrote d(total)/d(render, alpha).  The usual upstream gradient is the cached unit tensor of
+        # backward_fused() and needs no scaling pass; anything else (a weighted loss, a GradScaler) is applied
+        if v_total.data_ptr() != _unit_grad(v_total.device).data_ptr():
+            v_render, v_alpha = v_render * v_total, v_alpha * v_total
+        return v_render, v_alpha, None, None, None, None, None, None, None, None, None, None, None
+
+
+def _mcmc_reg_values(opacities: Tensor, scales: Tensor, lo: float, ls: float) -> Tensor:
+    """[3] device tensor (lo mean(sigmoid(opacities)), ls mean(exp(scales)), their sum): qed_mcmc_reg's deterministic fold."""
+    n = opacities.shape[0]
+    out = torch.empty(3, dtype=torch.float32, device=opacities.device)
+    ws = torch.empty(L.MCMC_REG_WS_DOUBLES, dtype=torch.float64, device=opacities.device)
+    L.check(L.load().qed_mcmc_reg(n, L.ptr(scales), L.ptr(opacities), lo, ls, L.ptr(out), None, None, None, None,
+                                  L.ptr(ws), _stream()), "qed_mcmc_reg")
+    return out
+
+
+def _mcmc_reg_grad_adder(opacities: Tensor, scales: Tensor, lo: float, ls: float):
+    """The projection backward's ``post_bwd`` of fused_loss: adds d(reg_o + reg_s) to the scale / opacity gradient rows."""
+    def add(v_scales: Tensor, v_opacities: Tensor) -> None:
+        L.check(L.load().qed_mcmc_reg(opacities.shape[0], L.ptr(scales), L.ptr(opacities), lo, ls, None, L.ptr(v_scales),
+                                      L.ptr(v_opacities), None, None, None, _stream()), "qed_mcmc_reg")
+    return add
+
+
+class _McmcReg(torch.autograd.Function):
+    """Splatfacto's MCMC regularisers (mcmc_opacity_reg, mcmc_scale_reg) of get_loss_dict: one pass for both values, one
+    for both gradients (scaled by the device-resident upstream gradients: no host sync)."""
+
+    @staticmethod
+    def forward(ctx, opacities, scales, lo, ls):
+        ctx.set_materialize_grads(False)
+        opacities, scales = opacities.detach().contiguous(), scales.detach().contiguous()
+        vals = _mcmc_reg_values(opacities, scales, lo, ls)
+        ctx.save_for_backward(opacities, scales)
+        ctx.lo, ctx.ls = lo, ls
+        return vals[0], vals[1]
+
+    @staticmethod
+    def backward(ctx, g_o, g_s):
+        opacities, scales = ctx.saved_tensors
+        lo = ctx.lo if g_o is not None else 0.0
+        ls = ctx.ls if g_s is not None else 0.0
+        v_opac = torch.zeros_like(opacities) if ctx.needs_input_grad[0] else None
+        v_scales = torch.zeros_like(scales) if ctx.needs_input_grad[1] else None
+        if v_opac is not None or v_scales is not None:
+            up_o = g_o.to(torch.float32).contiguous() if g_o is not None else None
+            up_s = g_s.to(torch.float32).contiguous() if g_s is not None else None
+            L.check(L.load().qed_mcmc_reg(opacities.shape[0], L.ptr(scales), L.ptr(opacities), lo, ls, None,
+                                          L.ptr(v_scales), L.ptr(v_opac), L.ptr(up_o), L.ptr(up_s), None, _stream()),
+                    "qed_mcmc_reg")
+        return v_opac, v_scales, None, None
+

@@ -20,6 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
+from .losses import _ssim_key, ssim_buffers
 
 METRIC_NAMES = ("rgb_mse", "rgb_psnr", "depth_abs_rel", "depth_sq_rel", "depth_rmse", "depth_rmse_log",
                 "depth_a1", "depth_a2", "depth_a3", "depth_n_valid")
@@ -35,6 +36,15 @@ def mean_angular_error(pred: Tensor, gt: Tensor) -> Tensor:
     return torch.acos(torch.clamp(torch.sum(gt * pred, dim=1), -1.0, 1.0))
 
 
+def _prep(t: Optional[Tensor], n_pix: int, last: int) -> Optional[Tensor]:
+    """An image as the kernels read it (float32, contiguous) with ``last`` values for each of ``n_pix`` pixels, or None."""
+    if t is None:
+        return None
+    t = t.to(torch.float32).contiguous()
+    assert t.numel() == n_pix * last, "shape mismatch between the images"
+    return t
+
+
 def image_metrics(pred_rgb: Optional[Tensor], gt_rgb: Optional[Tensor], pred_depth: Optional[Tensor] = None,
                   gt_depth: Optional[Tensor] = None, tolerance: float = 0.1) -> Tensor:
     """One pass over [H,W,3] colours and/or [H,W(,1)] depths -> float32[10] on the device, in the
@@ -43,15 +53,8 @@ def image_metrics(pred_rgb: Optional[Tensor], gt_rgb: Optional[Tensor], pred_dep
     ref = pred_rgb if pred_rgb is not None else pred_depth
     assert ref is not None, "nothing to measure"
     n_pix = ref.shape[0] * ref.shape[1]
-
-    def prep(t, last):
-        if t is None:
-            return None
-        t = t.to(torch.float32).contiguous()
-        assert t.numel() == n_pix * last, "shape mismatch between the images"
-        return t
-
-    pr, gr, pd, gd = prep(pred_rgb, 3), prep(gt_rgb, 3), prep(pred_depth, 1), prep(gt_depth, 1)
+    pr, gr = _prep(pred_rgb, n_pix, 3), _prep(gt_rgb, n_pix, 3)
+    pd, gd = _prep(pred_depth, n_pix, 1), _prep(gt_depth, n_pix, 1)
     work = torch.empty(L.METRICS_WS_DOUBLES, dtype=torch.float64, device=ref.device)
     out = torch.empty(10, dtype=torch.float32, device=ref.device)
     L.check(lib.qed_image_metrics(n_pix, L.ptr(pr), L.ptr(gr), L.ptr(pd), L.ptr(gd), float(tolerance), L.ptr(work),
@@ -81,19 +84,14 @@ def ssim_value(pred_rgb: Tensor, gt_rgb: Tensor, keep_maps: bool = False):
     lib = L.load()
     H, W, _ = pred_rgb.shape
     p, g = pred_rgb.to(torch.float32).contiguous(), gt_rgb.to(torch.float32).contiguous()
-    n_maps = lib.qed_ssim_maps_floats(H, W)
-    if n_maps < 0:
-        raise L.QedSplatError("image smaller than the 11 x 11 SSIM window")
-    ssum = torch.empty(lib.qed_ssim_sum_floats(H, W), dtype=torch.float32, device=p.device)
-    # maps = NULL: the value only (no 75 MB of backward coefficient maps at 1080p)
-    maps = torch.empty(n_maps, dtype=torch.float32, device=p.device) if keep_maps else None
+    # without keep_maps maps = NULL: the value only (no 75 MB of backward coefficient maps at 1080p)
+    maps, ssum, n_out = ssim_buffers(H, W, p.device, with_maps=keep_maps)
     L.check(lib.qed_ssim_fwd(H, W, 3, L.ptr(p), None, None, L.ptr(g), None, L.ptr(maps), L.ptr(ssum), _stream()),
             "qed_ssim_fwd")
-    value = ssum.sum() / (3.0 * (H - 10) * (W - 10))
+    value = ssum.sum() / n_out
     if not keep_maps:
         return value
-    key = (p.data_ptr(), p._version, tuple(p.shape), g.data_ptr(), g._version, tuple(g.shape))
-    return value, {"key": key, "maps_sum": (maps, ssum), "inputs": (p, g)}
+    return value, {"key": _ssim_key(p, g), "maps_sum": (maps, ssum), "inputs": (p, g)}
 
 
 @torch.no_grad()
@@ -108,22 +106,10 @@ def step_metrics(pred_rgb: Tensor, gt_rgb: Tensor, pred_depth: Optional[Tensor],
     H, W, _ = pred_rgb.shape
     n_pix = H * W
     dev = pred_rgb.device
-
-    def prep(t, last):
-        if t is None:
-            return None
-        t = t.to(torch.float32).contiguous()
-        assert t.numel() == n_pix * last, "shape mismatch between the images"
-        return t
-
-    p, g = prep(pred_rgb, 3), prep(gt_rgb, 3)
-    pd, gd = prep(pred_depth, 1), prep(gt_depth, 1)
-    n_maps = lib.qed_ssim_maps_floats(H, W)
-    if n_maps < 0:
-        raise L.QedSplatError("image smaller than the 11 x 11 SSIM window")
+    p, g = _prep(pred_rgb, n_pix, 3), _prep(gt_rgb, n_pix, 3)
+    pd, gd = _prep(pred_depth, n_pix, 1), _prep(gt_depth, n_pix, 1)
+    maps, ssum, n_out = ssim_buffers(H, W, dev)
     st = _stream()
-    ssum = torch.empty(lib.qed_ssim_sum_floats(H, W), dtype=torch.float32, device=dev)
-    maps = torch.empty(n_maps, dtype=torch.float32, device=dev)
     L.check(lib.qed_ssim_fwd(H, W, 3, L.ptr(p), None, None, L.ptr(g), None, L.ptr(maps), L.ptr(ssum), st), "qed_ssim_fwd")
     work = torch.empty(L.STEP_METRICS_WS_DOUBLES, dtype=torch.float64, device=dev)
     out = torch.empty(12, dtype=torch.float32, device=dev)
@@ -134,7 +120,7 @@ def step_metrics(pred_rgb: Tensor, gt_rgb: Tensor, pred_depth: Optional[Tensor],
         assert scales_last.dim() == 1 and scales_last.dtype == torch.float32
         n_sc, sc_stride = scales_last.numel(), (scales_last.stride(0) if scales_last.numel() > 1 else 1)
     L.check(lib.qed_step_metrics(n_pix, L.ptr(p), L.ptr(g), L.ptr(pd), L.ptr(gd), float(tolerance), L.ptr(ssum), ssum.numel(),
-                                 1.0 / (3.0 * (H - 10) * (W - 10)), L.ptr(scales_last) if n_sc else None, n_sc, sc_stride,
+                                 1.0 / n_out, L.ptr(scales_last) if n_sc else None, n_sc, sc_stride,
                                  None, 1.0 - ssim_lambda, float(depth_lambda), float(ssim_lambda), L.ptr(sums), L.ptr(losses),
                                  L.ptr(work), L.ptr(out), st), "qed_step_metrics")
     md = {"rgb_mse": out[0], "rgb_psnr": out[1], "rgb_ssim": out[10], "rgb_lpips": _nan(dev)}
@@ -142,8 +128,7 @@ def step_metrics(pred_rgb: Tensor, gt_rgb: Tensor, pred_depth: Optional[Tensor],
         md.update({n: out[i] for i, n in enumerate(METRIC_NAMES) if n.startswith("depth_") and n != "depth_n_valid"})
     if n_sc:
         md["avg_min_scale"] = out[11]
-    key = (p.data_ptr(), p._version, tuple(p.shape), g.data_ptr(), g._version, tuple(g.shape))
-    shared = {"key": key, "maps_sum": (maps, ssum), "inputs": (p, g, pd, gd), "loss": (sums, losses),
+    shared = {"key": _ssim_key(p, g), "maps_sum": (maps, ssum), "inputs": (p, g, pd, gd), "loss": (sums, losses),
               "depth_key": None if pd is None else (pd.data_ptr(), pd._version, gd.data_ptr(), gd._version),
               "lambdas": (float(ssim_lambda), float(depth_lambda))}
     return md, shared

@@ -20,6 +20,11 @@ Two ways to run a training step:
     (``rasterization(_post_background=...)``, ``_ImageLosses``);
   * fused: ``fused_loss`` = rasterization + the K8 loss / gradient kernels, ``backward_fused`` and ``FlatAdam`` -- one
     hipGraph-replayable step with the exp / sigmoid / cat of model.py:241,269-271 folded into the projection kernel.
+Both prepare the camera, the colours, the flags and the ground truth through the same private methods (``_camera_inputs``,
+``_color_inputs``, ``_base_flags``, ``_ground_truth``, ``_rasterize``).
+
+The autograd nodes of the image losses and their kernel bindings live in ``losses.py``, the optimisers in ``optim.py``; their
+names stay importable from here.
 """
 from __future__ import annotations
 
@@ -32,6 +37,9 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib as L
+from .losses import _FusedImageLoss, _ImageLosses, _McmcReg, _f32_image, _mcmc_reg_grad_adder, _mcmc_reg_values
+from .losses import _ssim_key, _unit_grad
+from .losses import _PostProcess, _SSIM, _UNIT_GRADS, ssim  # noqa: F401  (also importable from here)
 from .optim import FlatAdam, QedAdam, QedAdamSet, exponential_decay_lr  # noqa: F401  (also importable from here)
 from .optim import _RAW_GRAD, _all_groups_stepped_by_qed_adam, _raw_grad
 from .optim import _FLAT_STATES  # noqa: F401  (the registry object itself: tests stand in for QedAdam through it)
@@ -168,16 +176,6 @@ class PinholeCameras:
 
 GROUP_ORDER = ("means", "scales", "quats", "opacities", "features_dc", "features_rest")
 
-_UNIT_GRADS: Dict = {}
-
-
-def _unit_grad(device) -> Tensor:
-    """One cached 0-dim tensor 1.0 per device: the seed gradient of backward_fused()."""
-    one = _UNIT_GRADS.get(device)
-    if one is None:
-        one = _UNIT_GRADS[device] = torch.ones((), dtype=torch.float32, device=device)
-    return one
-
 
 def _refuse_overwritten(rgb: Tensor, who: str) -> None:
     """Outputs of a captured get_outputs segment live in static buffers: once a later get_outputs has replayed the segment
@@ -191,59 +189,6 @@ def _refuse_overwritten(rgb: Tensor, who: str) -> None:
 
 def _is_camera(obj) -> bool:
     return all(hasattr(obj, a) for a in ("camera_to_worlds", "get_intrinsics_matrices", "width", "height"))
-
-
-class _SSIM(torch.autograd.Function):
-    """SSIM(pred, gt) of two [H,W,3] images with pytorch_msssim semantics (the parent's
-    ``self.ssim``), value + gradient w.r.t. pred from ssim.hip."""
-
-    @staticmethod
-    def forward(ctx, pred, gt):
-        lib = L.load()
-        H, W, _ = pred.shape
-        pred, gt = pred.contiguous(), gt.contiguous()
-        n_maps = lib.qed_ssim_maps_floats(H, W)
-        if n_maps < 0:
-            raise L.QedSplatError("qed_ssim_maps_floats: image smaller than the 11 x 11 SSIM window")
-        maps = torch.empty(n_maps, dtype=torch.float32, device=pred.device)
-        ssum = torch.empty(lib.qed_ssim_sum_floats(H, W), dtype=torch.float32, device=pred.device)
-        L.check(lib.qed_ssim_fwd(H, W, 3, L.ptr(pred), None, None, L.ptr(gt), None, L.ptr(maps), L.ptr(ssum),
-                                 _stream()), "qed_ssim_fwd")
-        ctx.save_for_backward(pred, gt, maps)
-        return ssum.sum() / (3.0 * (H - 10) * (W - 10))
-
-    @staticmethod
-    def backward(ctx, v):
-        pred, gt, maps = ctx.saved_tensors
-        H, W, _ = pred.shape
-        v_pred = torch.empty_like(pred)
-        v = v.to(torch.float32).reshape(1).contiguous()            # upstream gradient, multiplied inside the kernel
-        L.check(L.load().qed_ssim_bwd(H, W, 3, L.ptr(pred), None, None, L.ptr(gt), None, L.ptr(maps),
-                                      1.0 / (3.0 * (H - 10) * (W - 10)), L.ptr(v), L.ptr(v_pred), _stream()),
-                "qed_ssim_bwd")
-        return v_pred, None
-
-
-def ssim(pred: Tensor, gt: Tensor) -> Tensor:
-    """Mean SSIM of two float32 [H,W,3] images in [0,1] (differentiable in ``pred``)."""
-    assert pred.dim() == 3 and pred.shape[-1] == 3 and pred.shape == gt.shape
-    return _SSIM.apply(pred.to(torch.float32), gt.to(torch.float32))
-
-
-def _f32_image(t: Tensor, numel: int, what: str, dev) -> Tensor:
-    """A batch tensor as the kernels read it: float32, contiguous, on the model's device, ``numel`` elements
-    (bool masks and uint8 images are converted; anything of another size is refused before a launch)."""
-    if t.dtype == torch.uint8 and what != "mask":
-        t = t.float() / 255.0
-    t = t.to(device=dev, dtype=torch.float32).contiguous()
-    if t.numel() != numel:
-        raise L.QedSplatError(f"{what}: {tuple(t.shape)} holds {t.numel()} values, the render needs {numel}")
-    return t
-
-
-def _ssim_key(pred: Tensor, gt: Tensor):
-    """What identifies the inputs of an SSIM forward: address, version and shape of both images."""
-    return (pred.data_ptr(), pred._version, tuple(pred.shape), gt.data_ptr(), gt._version, tuple(gt.shape))
 
 
 class StepContext:
@@ -306,221 +251,6 @@ class StepContext:
             return None
         bufs, self.static = self.static[:2], (None, None, self.static[2])
         return bufs
-
-
-class _PostProcess(torch.autograd.Function):
-    """model.py:295-297 + 304-306 as ONE node: rgb = clamp(render[..., :3] + (1 - alpha) background, 0, 1) and
-    depth = where(alpha > 0, render[..., 3:4], render[..., 3:4].detach().max())."""
-
-    @staticmethod
-    def forward(ctx, render, alpha, background):
-        lib = L.load()
-        ctx.set_materialize_grads(False)
-        if not render.is_cuda:
-            raise L.QedSplatError("get_outputs needs GPU tensors: there is no CPU path in the product")
-        C, H, W, CH = render.shape
-        dev = render.device
-        render, alpha = render.contiguous(), alpha.contiguous()
-        background = background.to(torch.float32).contiguous()
-        rgb = torch.empty(C, H, W, 3, dtype=torch.float32, device=dev)
-        depth = torch.empty(C, H, W, 1, dtype=torch.float32, device=dev) if CH == 4 else None
-        ws = torch.empty(L.LOSS_SUMS_FLOATS, dtype=torch.float32, device=dev) if CH == 4 else None
-        L.check(lib.qed_post_process_fwd(C * H * W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(rgb),
-                                         L.ptr(depth), L.ptr(ws), _stream()), "qed_post_process_fwd")
-        ctx.save_for_backward(render, alpha, background)
-        if depth is None:
-            return rgb
-        return rgb, depth
-
-    @staticmethod
-    def backward(ctx, v_rgb, v_depth=None):
-        render, alpha, background = ctx.saved_tensors
-        C, H, W, CH = render.shape
-        if v_rgb is None and v_depth is None:
-            return None, None, None
-        v_rgb = v_rgb.to(torch.float32).contiguous() if v_rgb is not None else None
-        v_depth = v_depth.to(torch.float32).contiguous() if v_depth is not None else None
-        v_render = torch.empty_like(render)
-        v_alpha = torch.empty_like(alpha)
-        L.check(L.load().qed_post_process_bwd(C * H * W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(v_rgb),
-                                              L.ptr(v_depth), L.ptr(v_render), L.ptr(v_alpha), _stream()),
-                "qed_post_process_bwd")
-        return v_render, v_alpha, None
-
-
-class _ImageLosses(torch.autograd.Function):
-    """get_loss_dict on the images get_outputs returned: the parent's main loss (1 - l) L1 + l (1 - SSIM) with the
-    mask multiplied into both images (behind model.py:83-85) and the masked depth-L1 term (model.py:87-116), as two
-    scalars.  The trainer sums the loss dict and differentiates, possibly with weights or a GradScaler: the backward
-    multiplies each term's gradient by its upstream gradient, read from device memory."""
-
-    @staticmethod
-    def forward(ctx, rgb, depth, gt_rgb, gt_depth, mask, ssim_lambda, depth_lambda, ssim_shared=None, loss_shared=None,
-                vsplat=None, grad_out=None):
-        lib = L.load()
-        ctx.set_materialize_grads(False)
-        # (holder, rows, static buffer | None): the compositing backward's accumulator, zeroed by this node's backward launch
-        ctx.vsplat = vsplat
-        ctx.grad_out = grad_out   # (v_rgb, v_depth) static buffers of a captured get_outputs segment, or None
-        if not rgb.is_cuda:
-            raise L.QedSplatError("get_loss_dict needs GPU tensors: there is no CPU path in the product")
-        H, W, _ = rgb.shape
-        dev = rgb.device
-        n_pix = H * W
-        rgb = rgb.contiguous()
-        depth = depth.contiguous() if depth is not None else None
-        st = _stream()
-        if loss_shared is not None and ssim_shared is not None:
-            # get_metrics_dict ran qed_step_metrics on these very images a moment ago: the sums and the two losses exist
-            sums, losses = loss_shared
-            maps = ssim_shared[0]
-            ctx.save_for_backward(rgb, depth, gt_rgb, gt_depth, mask, maps, sums)
-            ctx.lams = (float(ssim_lambda), float(depth_lambda))
-            return losses[0:1].view(()), losses[1:2].view(())
-        sums = torch.empty(L.LOSS_SUMS_FLOATS, dtype=torch.float32, device=dev)
-        losses = torch.empty(3, dtype=torch.float32, device=dev)
-        maps = None
-        extra = (None, 0, 0.0, 0.0)
-        if ssim_lambda > 0.0:
-            n_out = 3.0 * (H - 10) * (W - 10)
-            n_maps = lib.qed_ssim_maps_floats(H, W)
-            if n_maps < 0:
-                raise L.QedSplatError("image smaller than the 11 x 11 SSIM window")
-            if ssim_shared is not None:
-                # get_metrics_dict ran qed_ssim_fwd on these very images a moment ago (rgb_ssim, model.py:157-166) and
-                # kept the coefficient maps: the loss needs the same map sum and the same maps
-                maps, ssum = ssim_shared
-            else:
-                maps = torch.empty(n_maps, dtype=torch.float32, device=dev)
-                ssum = torch.empty(lib.qed_ssim_sum_floats(H, W), dtype=torch.float32, device=dev)
-                L.check(lib.qed_ssim_fwd(H, W, 3, L.ptr(rgb), None, None, L.ptr(gt_rgb), L.ptr(mask), L.ptr(maps),
-                                         L.ptr(ssum), st), "qed_ssim_fwd")
-            extra = (L.ptr(ssum), ssum.numel(), -ssim_lambda / n_out, ssim_lambda)
-        L.check(lib.qed_image_losses_fwd(n_pix, L.ptr(rgb), L.ptr(depth), L.ptr(gt_rgb), L.ptr(gt_depth), L.ptr(mask),
-                                         1.0 - ssim_lambda, depth_lambda, *extra, L.ptr(sums), L.ptr(losses), st),
-                "qed_image_losses_fwd")
-        ctx.save_for_backward(rgb, depth, gt_rgb, gt_depth, mask, maps, sums)
-        ctx.lams = (float(ssim_lambda), float(depth_lambda))
-        return losses[0:1].view(()), losses[1:2].view(())
-
-    @staticmethod
-    def backward(ctx, g_main, g_depth):
-        lib = L.load()
-        rgb, depth, gt_rgb, gt_depth, mask, maps, sums = ctx.saved_tensors
-        ssim_lambda, depth_lambda = ctx.lams
-        H, W, _ = rgb.shape
-        st = _stream()
-
-        def scalar(g):
-            return None if g is None else g.to(torch.float32).reshape(1).contiguous()
-        g_main, g_depth = scalar(g_main), scalar(g_depth)
-        sv_rgb, sv_depth = ctx.grad_out if ctx.grad_out is not None else (None, None)
-
-        def out_like(t, static):
-            return static if (static is not None and static.shape == t.shape) else torch.empty_like(t)
-        v_rgb = out_like(rgb, sv_rgb) if (g_main is not None and ctx.needs_input_grad[0]) else None
-        v_depth = out_like(depth, sv_depth) if (g_depth is not None and depth is not None and ctx.needs_input_grad[1]) \
-            else None
-        if v_rgb is not None and ssim_lambda > 0.0:
-            # ONE launch: the L1 term joins the SSIM term inside the SSIM backward pass, the depth term rides along
-            n_out = 3.0 * (H - 10) * (W - 10)
-            zero = None
-            if ctx.vsplat is not None:
-                holder, rows, static = ctx.vsplat
-                zero = static if static is not None else \
-                    torch.empty(rows, L.VSPLAT_FLOATS, dtype=torch.float32, device=rgb.device)
-            L.check(lib.qed_image_losses_ssim_bwd(H, W, L.ptr(rgb), L.ptr(depth), L.ptr(gt_rgb), L.ptr(gt_depth),
-                                                  L.ptr(mask), L.ptr(maps), L.ptr(sums), 1.0 - ssim_lambda, depth_lambda,
-                                                  -ssim_lambda / n_out, L.ptr(g_main), L.ptr(g_depth), L.ptr(v_rgb),
-                                                  L.ptr(v_depth), L.ptr(zero), zero.numel() if zero is not None else 0, st),
-                    "qed_image_losses_ssim_bwd")
-            if zero is not None:
-                del holder[:]
-                holder.append(zero)
-        else:
-            L.check(lib.qed_image_losses_bwd(H * W, L.ptr(rgb), L.ptr(depth), L.ptr(gt_rgb), L.ptr(gt_depth), L.ptr(mask),
-                                             L.ptr(sums), 1.0 - ssim_lambda, depth_lambda, L.ptr(g_main), L.ptr(g_depth), 0,
-                                             L.ptr(v_rgb), L.ptr(v_depth), st), "qed_image_losses_bwd")
-        return v_rgb, v_depth, None, None, None, None, None, None, None, None, None
-
-
-class _FusedImageLoss(torch.autograd.Function):
-    """K8: composite + clamp + depth fix-up + L1 RGB + (1 - SSIM) + masked depth-L1, value and gradient
-    (model.py:295-297, 304-306, 87-116 and the parent's main loss behind :83-85)."""
-
-    @staticmethod
-    def forward(ctx, render, alpha, background, gt_rgb, gt_depth, mask, ssim_lambda, depth_lambda, vsplat_holder=None,
-                vsplat_rows=0, tick=None, tile_cost=None, order_buf=None):
-        import ctypes
-        lib = L.load()
-        ctx.set_materialize_grads(False)
-        C, H, W, CH = render.shape
-        assert C == 1, "one camera per training step (model.py:211)"
-        dev = render.device
-        n_pix = H * W
-        sums = torch.empty(L.LOSS_SUMS_FLOATS, dtype=torch.float32, device=dev)
-        losses = torch.empty(3, dtype=torch.float32, device=dev)       # rgb term, depth term, total
-        v_render = torch.empty_like(render)
-        v_alpha = torch.empty_like(alpha)
-        st = _stream()
-        args = (n_pix, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(gt_rgb), L.ptr(gt_depth), L.ptr(mask))
-        if ssim_lambda > 0.0:
-            # main = (1 - l) L1 + l (1 - SSIM): ONE launch forms the SSIM gradient w.r.t. the clamped colour and pushes
-            # it, with the L1 part and the depth term, through the clamp / background composite (qed_loss_grad_ssim)
-            n_out = 3.0 * (H - 10) * (W - 10)
-            # the same launch zeroes the accumulator the compositing backward will add into (no fill launch there)
-            vsplat = None
-            if vsplat_holder is not None and vsplat_rows > 0:
-                vsplat = torch.empty(vsplat_rows, L.VSPLAT_FLOATS, dtype=torch.float32, device=dev)
-            maps = torch.empty(lib.qed_ssim_maps_floats(H, W), dtype=torch.float32, device=dev)
-            ssum = torch.empty(lib.qed_ssim_sum_floats(H, W), dtype=torch.float32, device=dev)
-            # The SSIM forward launch carries two passengers that would otherwise be launches of their own on the step's
-            # critical chain: pass 1 of the image loss (qed_loss_reduce: ~9 us) and -- the forward pass's per-tile costs
-            # are known by now -- the compositing backward's launch order (~10 us in front of that kernel).
-            order_ws = None
-            if vsplat_holder is not None and tile_cost is not None:
-                # (the camera's persistent launch-order buffer when the caller keeps one: model.fused_loss, frame_key)
-                order_ws = order_buf if (order_buf is not None and order_buf.numel() == tile_cost.shape[0] + 1) else \
-                    torch.empty(tile_cost.shape[0] + 1, dtype=torch.int32, device=dev)
-            if os.environ.get("QED_STEP_PASSENGERS", "1") == "0":          # measurement hook: every job a launch of its own
-                L.check(lib.qed_loss_reduce(*args, L.ptr(sums), st), "qed_loss_reduce")
-                L.check(lib.qed_ssim_fwd(H, W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(gt_rgb),
-                                         L.ptr(mask), L.ptr(maps), L.ptr(ssum), st), "qed_ssim_fwd")
-                order_ws = None
-            else:
-                L.check(lib.qed_ssim_fwd_step(H, W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(gt_rgb),
-                                            L.ptr(mask), L.ptr(maps), L.ptr(ssum), L.ptr(tile_cost) if order_ws is not None else None,
-                                            tile_cost.shape[0] if order_ws is not None else 0, L.ptr(order_ws),
-                                            L.ptr(gt_depth), L.ptr(sums), st), "qed_ssim_fwd_step")
-            L.check(lib.qed_loss_grad_ssim(H, W, CH, L.ptr(render), L.ptr(alpha), L.ptr(background), L.ptr(gt_rgb),
-                                           L.ptr(gt_depth), L.ptr(mask), L.ptr(maps), L.ptr(sums), 1.0 - ssim_lambda,
-                                           depth_lambda, -ssim_lambda / n_out, L.ptr(v_render), L.ptr(v_alpha),
-                                           L.ptr(losses), L.ptr(ssum), ssum.numel(), ssim_lambda, L.ptr(vsplat),
-                                           vsplat.numel() if vsplat is not None else 0,
-                                           ctypes.addressof(tick) if tick is not None else None, st), "qed_loss_grad_ssim")
-            if vsplat is not None or order_ws is not None:
-                del vsplat_holder[:]
-                vsplat_holder.append({"vsplat": vsplat, "order_ws": order_ws})
-        else:
-            L.check(lib.qed_loss_reduce(*args, L.ptr(sums), st), "qed_loss_reduce")
-            L.check(lib.qed_loss_grad(*args, L.ptr(sums), 1.0, depth_lambda, L.ptr(v_render), L.ptr(v_alpha),
-                                      L.ptr(losses), None, None, 0, 0.0, 0.0, st), "qed_loss_grad")
-        ctx.save_for_backward(v_render, v_alpha)
-        total = losses[2:3].view(())
-        parts = losses[0:2]
-        ctx.mark_non_differentiable(parts)
-        return total, parts
-
-    @staticmethod
-    def backward(ctx, v_total, _v_parts):
-        if v_total is None:
-            return (None,) * 13
-        v_render, v_alpha = ctx.saved_tensors
-        # the kernel wrote d(total)/d(render, alpha).  The usual upstream gradient is the cached unit tensor of
-        # backward_fused() and needs no scaling pass; anything else (a weighted loss, a GradScaler) is applied
-        if v_total.data_ptr() != _unit_grad(v_total.device).data_ptr():
-            v_render, v_alpha = v_render * v_total, v_alpha * v_total
-        return v_render, v_alpha, None, None, None, None, None, None, None, None, None, None, None
 
 
 def write_sh_grads(means: Tensor, viewmat: Tensor, sh_degree: int, v_color: Tensor, v_rest: Tensor) -> None:
@@ -868,7 +598,6 @@ class QEDSplatterModel(nn.Module):
     def _outputs_segment(self, W, H, render_mode, deg, flags, render_fn, cam_c2w, background):
         """The captured form of this call's device work (segments.OutputsSegment), or None while the shape is still being
         seen eagerly / after anything the capture was specialised on has changed."""
-        from .rasterization import _workspace
         from .segments import OutputsSegment, SegmentCache
         cache = self.__dict__.get("_segments")
         if cache is None:
@@ -896,6 +625,74 @@ class QEDSplatterModel(nn.Module):
             return seg
 
         return cache.capture(key, make, cam_c2w[0], cam_c2w[1], background)
+
+    # ---- what get_outputs -> get_loss_dict and fused_loss prepare in the same way ----
+    def _camera_inputs(self, camera, c2w: Tensor):
+        """(viewmat, K, cam_c2w, W, H) at the resolution schedule's size (model.py:244-250): the camera is downscaled, read
+        and restored, also when reading it raises.  A float32 GPU pose that nothing differentiates, of a camera with
+        ``intrinsics_fxfycxcy``, is left to the projection kernel (QED_F_CAMERA_C2W): ``cam_c2w`` = (pose, intrinsics), and
+        ``viewmat`` / ``K`` are the buffers the kernel fills for everything downstream -- instead of ~15 tiny eager launches.
+        Any other pose goes through get_viewmat / get_intrinsics_matrices (``cam_c2w`` = None), differentiable w.r.t. a
+        camera optimiser's pose; in fused_loss too a pose that requires grad takes this branch (the values are equal).
+        Both routes get the eager pair on the model's device as float32 and W, H from ``.item()`` (one camera)."""
+        d = self._get_downscale_factor()
+        if d != 1:                                    # (x 1.0 and back is exact: eight tiny launches saved per step)
+            camera.rescale_output_resolution(1 / d)
+        try:
+            intr = getattr(camera, "intrinsics_fxfycxcy", None)
+            if intr is not None and c2w.dtype == torch.float32 and not c2w.requires_grad and c2w.is_cuda:
+                C = c2w.shape[0]
+                viewmat = torch.empty(C, 4, 4, dtype=torch.float32, device=self.device)
+                K = torch.empty(C, 3, 3, dtype=torch.float32, device=self.device)
+                cam_c2w = (c2w.contiguous(), intr())
+            else:
+                viewmat = get_viewmat(c2w).to(self.device, torch.float32)
+                K = camera.get_intrinsics_matrices().to(self.device, torch.float32)
+                cam_c2w = None
+            W, H = int(camera.width.item()), int(camera.height.item())
+        finally:
+            if d != 1:
+                camera.rescale_output_resolution(d)
+        self.__dict__["last_size"] = (H, W)
+        return viewmat, K, cam_c2w, W, H
+
+    def _color_inputs(self, features_dc: Tensor, features_rest: Tensor):
+        """(sh_degree_to_use, colors, sh_rest, flag bits) of model.py:261-265: the SH schedule without the torch.cat of
+        model.py:241, or torch.sigmoid(colors) fused into the projection kernel."""
+        cfg = self.config
+        if cfg.sh_degree > 0:
+            return min(self.step // cfg.sh_degree_interval, cfg.sh_degree), features_dc, features_rest, 0
+        return None, features_dc, None, L.F_SIGMOID_COLORS
+
+    def _base_flags(self, W: int, H: int) -> int:
+        """exp / sigmoid fused (model.py:270-271); tight tile lists where the tile grid fits their packing: the lists in
+        ``info`` become subsets of gsplat's (no training path reads them), images, alphas and gradients are unchanged."""
+        flags = L.F_LOG_SCALES | L.F_LOGIT_OPAC
+        if self.config.tight_tile_lists and W <= 16 * 1023 and H <= 16 * 2047:
+            flags |= L.F_TIGHT_TILES
+        return flags
+
+    def _ground_truth(self, batch, background: Tensor, H: int, W: int):
+        """(gt_rgb, gt_depth, mask | None) as the loss kernels read them: uint8 -> float, downscaled, on the device, RGBA
+        composited onto ``background``; each checked against the render size BEFORE a kernel reads it by raw pointer."""
+        gt_rgb = self.composite_with_background(self.get_gt_img(batch["image"]), background)
+        mask = self._loss_mask(batch, (H, W))
+        gt_rgb = _f32_image(gt_rgb[..., :3] if gt_rgb.shape[-1] > 3 else gt_rgb, H * W * 3, "batch['image']", self.device)
+        gt_depth = _f32_image(self.get_gt_img(batch["depth_image"]), H * W, "batch['depth_image']", self.device)
+        return gt_rgb, gt_depth, mask
+
+    def _rasterize(self, **kw):
+        """rasterization(...) with the arguments model.py:267-288 never varies; the callers pass what differs."""
+        return rasterization(tile_size=16, packed=False, near_plane=0.01, far_plane=1e10, sparse_grad=False, absgrad=True,
+                             rasterize_mode=self.config.rasterize_mode, **kw)
+
+    @staticmethod
+    def _put_mcmc_regs(out: Dict[str, Tensor], lo: float, ls: float, regs) -> None:
+        """splatfacto (strategy="mcmc"): ``regs`` = (opacity, scale, ...) after scale_reg, before tv_loss / depth_loss."""
+        if lo > 0.0:
+            out["mcmc_opacity_reg"] = regs[0]
+        if ls > 0.0:
+            out["mcmc_scale_reg"] = regs[1]
 
     # ---- a2-a10: get_outputs (model.py:199-321) ----
     def get_outputs(self, camera) -> Dict[str, Union[Tensor, List]]:
@@ -931,32 +728,12 @@ class QEDSplatterModel(nn.Module):
             features_dc_crop, features_rest_crop = self.features_dc, self.features_rest
             scales_crop, quats_crop = self.scales, self.quats
 
-        BLOCK_WIDTH = 16                                                      # model.py:243
-        camera_scale_fac = self._get_downscale_factor()
-        if camera_scale_fac != 1:                     # (x 1.0 and back is exact: eight tiny launches saved per step)
-            camera.rescale_output_resolution(1 / camera_scale_fac)
-        intr = getattr(camera, "intrinsics_fxfycxcy", None)
-        if intr is not None and optimized_camera_to_world.dtype == torch.float32 \
-                and not optimized_camera_to_world.requires_grad and optimized_camera_to_world.is_cuda:
-            # get_viewmat + get_intrinsics_matrices inside the projection kernel (QED_F_CAMERA_C2W), which fills these
-            # two buffers for everything downstream -- instead of ~15 tiny eager launches, or one of qed_camera_setup
-            C = optimized_camera_to_world.shape[0]
-            viewmat = torch.empty(C, 4, 4, dtype=torch.float32, device=self.device)
-            K = torch.empty(C, 3, 3, dtype=torch.float32, device=self.device)
-            cam_c2w = (optimized_camera_to_world.contiguous(), intr())
-        else:
-            viewmat = get_viewmat(optimized_camera_to_world)
-            K = camera.get_intrinsics_matrices().to(self.device)
-            cam_c2w = None
-        W, H = int(camera.width.item()), int(camera.height.item())
+        viewmat, K, cam_c2w, W, H = self._camera_inputs(camera, optimized_camera_to_world)   # model.py:243-250
         attrs = self.__dict__            # (plain attributes: nn.Module.__setattr__ costs ~5 us apiece, a dozen per step)
-        attrs["last_size"] = (H, W)
         # what get_metrics_dict / get_loss_dict / backward share about THIS step lives in one object, replaced here: a
         # loader that refills its batch tensors in place without bumping their version counter must not be served last
         # step's conversion, and nothing of last step's outputs may reach this step's loss
         ctx = attrs["_step"] = StepContext()
-        if camera_scale_fac != 1:
-            camera.rescale_output_resolution(camera_scale_fac)
 
         if self.config.rasterize_mode not in ["antialiased", "classic"]:      # model.py:253-254
             raise ValueError("Unknown rasterize_mode: %s", self.config.rasterize_mode)
@@ -965,16 +742,8 @@ class QEDSplatterModel(nn.Module):
         else:
             render_mode = "RGB"
 
-        flags = L.F_LOG_SCALES | L.F_LOGIT_OPAC                               # exp / sigmoid fused (model.py:270-271)
-        if self.config.tight_tile_lists and W <= 16 * 1023 and H <= 16 * 2047:
-            flags |= L.F_TIGHT_TILES
-        if self.config.sh_degree > 0:                                         # model.py:261-265
-            sh_degree_to_use = min(self.step // self.config.sh_degree_interval, self.config.sh_degree)
-            colors, sh_rest = features_dc_crop, features_rest_crop            # no torch.cat (model.py:241)
-        else:
-            sh_degree_to_use = None
-            colors, sh_rest = features_dc_crop, None
-            flags |= L.F_SIGMOID_COLORS                                       # torch.sigmoid(colors) fused
+        sh_degree_to_use, colors, sh_rest, color_flags = self._color_inputs(features_dc_crop, features_rest_crop)
+        flags = self._base_flags(W, H) | color_flags
 
         # the SH gradients of this step may stay compact until somebody reads them (config.lazy_sh_grad)
         lazy = self._lazy_sh_wanted(sh_degree_to_use, crop_ids)
@@ -999,38 +768,17 @@ class QEDSplatterModel(nn.Module):
             if viewmats is None:
                 viewmats = torch.empty(C, 4, 4, dtype=torch.float32, device=self.device)
                 Ks = torch.empty(C, 3, 3, dtype=torch.float32, device=self.device)
-            return rasterization(
-                means=means_crop,
+            return self._rasterize(
+                means=means_crop, scales=scales_crop, opacities=opacities_crop, colors=colors,
                 quats=quats_crop,                       # normalised inside the projection kernel (model.py:269)
-                scales=scales_crop,
-                opacities=opacities_crop,
-                colors=colors,
-                viewmats=viewmats,
-                Ks=Ks,
-                width=W,
-                height=H,
-                tile_size=BLOCK_WIDTH,
-                packed=False,
-                near_plane=0.01,
-                far_plane=1e10,
-                render_mode=render_mode,
-                sh_degree=sh_degree_to_use,
-                sparse_grad=False,
-                absgrad=True,
-                rasterize_mode=self.config.rasterize_mode,
-                _flags=flags,
-                _sh_rest=sh_rest,
-                _sync=not (self.config.async_intersection_count and self.training),
-                _c2w=(c2w, intr) if c2w is not None else None,
-                _post_background=bg,
-                _vsplat_holder=hold,
+                viewmats=viewmats, Ks=Ks, width=W, height=H, render_mode=render_mode, sh_degree=sh_degree_to_use,
+                _flags=flags, _sh_rest=sh_rest, _sync=not (self.config.async_intersection_count and self.training),
+                _c2w=(c2w, intr) if c2w is not None else None, _post_background=bg, _vsplat_holder=hold,
                 _means2d_leaf=True,     # xys is only retained and read (below; densify.py): its gradient arrives as a view
-                _capture_slot=capture_slot,
-                _manual=manual,
+                _capture_slot=capture_slot, _manual=manual,
                 # (a captured backward pass always writes the compact form; _SegmentFn.backward asks per replay)
                 _lazy_sh=self._lazy_sh_begin if (lazy and manual is None) else None,
-                _tile_order=frame_slot if (manual is None and capture_slot is None) else None,
-            )
+                _tile_order=frame_slot if (manual is None and capture_slot is None) else None)
 
         seg = None
         if (self.training and self.config.graph_segments and cam_c2w is not None and crop_ids is None
@@ -1043,10 +791,10 @@ class QEDSplatterModel(nn.Module):
             background = seg.bg
         else:
             render, alpha, info = render_fn(cam_c2w[0] if cam_c2w else None, cam_c2w[1] if cam_c2w else None, background,
-                                            holder, viewmats=viewmat.to(torch.float32), Ks=K.to(torch.float32))
+                                            holder, viewmats=viewmat, Ks=K)
             # model.py:296-297 (composite + clamp) and :304-308 (depth fix-up) ran inside the compositing kernel, and
             # their backward runs inside the compositing backward (rasterization(_post_background=...)): no pass of its
-            # own over the image in either direction (_PostProcess above is the stand-alone form of the same statements)
+            # own over the image in either direction (losses._PostProcess is the stand-alone form of the same statements)
             rgb = info.pop("post_rgb")
             depth_im = info.pop("post_depth")
         # The frame BEFORE this one overflowed its intersection buffer (asynchronous count, one call late): it rendered
@@ -1137,10 +885,7 @@ class QEDSplatterModel(nn.Module):
         _refuse_overwritten(pred_img, "get_loss_dict")
         ctx = self.__dict__.get("_step")
         mine = ctx is not None and ctx.owns(outputs)          # these outputs are this step's (not kept from an earlier one)
-        gt_img = self.composite_with_background(self.get_gt_img(batch["image"]), outputs["background"])
-        mask = self._loss_mask(batch, pred_img.shape)
-        gt_img = _f32_image(gt_img[..., :3] if gt_img.shape[-1] > 3 else gt_img, H * W * 3, "batch['image']", self.device)
-        depth_batch = _f32_image(self.get_gt_img(batch["depth_image"]), H * W, "batch['depth_image']", self.device)
+        gt_img, depth_batch, mask = self._ground_truth(batch, outputs["background"], H, W)
         # the SSIM forward get_metrics_dict ran on the same two images (same storage, same version; the cache holds the
         # tensors, so neither address can have been recycled), no mask: not computed a second time
         shared = ctx.take_ssim() if mine else None
@@ -1163,12 +908,8 @@ class QEDSplatterModel(nn.Module):
                                          grad_out)
         out = {"main_loss": main, "scale_reg": self._scale_reg()}
         lo, ls = self._mcmc_reg_weights()
-        if lo > 0.0 or ls > 0.0:                 # splatfacto (strategy="mcmc"): after scale_reg, before tv_loss / depth_loss
-            reg_o, reg_s = _McmcReg.apply(self.opacities, self.scales, lo, ls)
-            if lo > 0.0:
-                out["mcmc_opacity_reg"] = reg_o
-            if ls > 0.0:
-                out["mcmc_scale_reg"] = reg_s
+        if lo > 0.0 or ls > 0.0:
+            self._put_mcmc_regs(out, lo, ls, _McmcReg.apply(self.opacities, self.scales, lo, ls))
         if self.training and cfg.use_bilateral_grid and self.bil_grids is not None:      # the parent's tv_loss
             from .bilagrid import total_variation_loss
             out["tv_loss"] = 10 * total_variation_loss(self.bil_grids.grids)
@@ -1232,7 +973,6 @@ class QEDSplatterModel(nn.Module):
         by the skip flag: the empty frame's zero gradients still make a momentum-only update -- can watch this count and
         drop the step when it moves.  The count of a frame arrives one call late (poll_pending).  (An attribute, not a
         key of the metrics dict: that dict keeps the reference's keys.)"""
-        from .rasterization import _workspace
         return _workspace(self.device).overflows
 
     def frame_overflowed(self) -> bool:
@@ -1292,52 +1032,20 @@ class QEDSplatterModel(nn.Module):
             self._materialise_sh_grads()          # (compact gradients of a get_outputs step nobody consumed: see there)
         cfg = self.config
         self.__dict__["_step"] = StepContext()   # (conversions of the batch are shared within a step, never across steps)
-        # the coarse-to-fine schedule of get_outputs (model.py:244-250): render at 1/d of the camera's resolution
-        d = self._get_downscale_factor()
-        if d > 1:
-            camera.rescale_output_resolution(1 / d)
-        try:
-            intr = getattr(camera, "intrinsics_fxfycxcy", None)
-            if intr is not None and camera.camera_to_worlds.dtype == torch.float32 and camera.camera_to_worlds.is_cuda:
-                # a1 + a3 inside the projection kernel (QED_F_CAMERA_C2W): it fills viewmat / K for what follows
-                viewmat = torch.empty(1, 4, 4, dtype=torch.float32, device=self.device)
-                K = torch.empty(1, 3, 3, dtype=torch.float32, device=self.device)
-                cam_c2w = (camera.camera_to_worlds.contiguous(), intr())
-            else:
-                viewmat = get_viewmat(camera.camera_to_worlds).to(self.device, torch.float32)
-                K = camera.get_intrinsics_matrices().to(self.device, torch.float32)
-                cam_c2w = None
-            W, H = int(camera.width[0]), int(camera.height[0])
-        finally:
-            if d > 1:
-                camera.rescale_output_resolution(d)
-        self.last_size = (H, W)
-        # tight tile lists: info["tiles_per_gauss"/"flatten_ids"/...] become subsets of gsplat's (nothing on the
-        # training path reads them); images, alphas and gradients are unchanged
-        flags = L.F_LOG_SCALES | L.F_LOGIT_OPAC | (L.F_TIGHT_TILES if cfg.tight_tile_lists else 0)
+        attrs = self.__dict__            # (plain attributes, as in get_outputs)
+        viewmat, K, cam_c2w, W, H = self._camera_inputs(camera, camera.camera_to_worlds)
+        deg, colors, sh_rest, color_flags = self._color_inputs(self.features_dc, self.features_rest)
+        flags = self._base_flags(W, H) | color_flags
         if compact_sh_grad and cfg.sh_degree > 0:
             # data parallel: features_dc.grad then holds the clamp-masked colour gradient and features_rest.grad
             # is not written; parallel.exchange_grads_compact() rebuilds both from all ranks' views
             flags |= L.F_SH_GRAD_COMPACT
-        self.last_viewmat = None
-        self.last_compact = bool(flags & L.F_SH_GRAD_COMPACT)
-        self.sh_views = None                  # set by parallel.exchange_grads_compact(rebuild=False)
-        if cfg.sh_degree > 0:
-            deg = min(self.step // cfg.sh_degree_interval, cfg.sh_degree)
-            colors, sh_rest = self.features_dc, self.features_rest
-        else:
-            deg, colors, sh_rest = None, self.features_dc, None
-            flags |= L.F_SIGMOID_COLORS
-        # ground truth exactly as get_loss_dict prepares it (uint8 -> float, downscaled, on the device), checked
-        # against the render size BEFORE any kernel reads it through a raw pointer
+        attrs["last_viewmat"] = None
+        attrs["last_compact"] = bool(flags & L.F_SH_GRAD_COMPACT)
+        attrs["sh_views"] = None              # set by parallel.exchange_grads_compact(rebuild=False)
         bg = (background if background is not None else self._get_background_color()).to(self.device, torch.float32)
-        gt_rgb = self.composite_with_background(self.get_gt_img(batch["image"]), bg)
-        gt_rgb = _f32_image(gt_rgb[..., :3] if gt_rgb.shape[-1] > 3 else gt_rgb, H * W * 3, "batch['image']", self.device)
-        gt_depth = _f32_image(self.get_gt_img(batch["depth_image"]), H * W, "batch['depth_image']", self.device)
-        mask = self._loss_mask(batch, (H, W))
+        gt_rgb, gt_depth, mask = self._ground_truth(batch, bg, H, W)           # exactly as get_loss_dict prepares it
         holder: list = []         # (the fused loss launch leaves the compositing backward's zeroed accumulator here)
-        # the launch-order buffer of this camera (see ``frame_key``): [C T + 1] int32, written by every training frame's
-        # loss launch, read by the next frame's compositing forward -- persistent, so that a captured step replays against it
         # strategy="mcmc": the two regularisers of get_loss_dict, folded into ``loss``; their gradient is added to the flat
         # gradient by the projection backward, right after it has written it (for an upstream gradient of 1, as above)
         lo, ls = self._mcmc_reg_weights()
@@ -1346,6 +1054,8 @@ class QEDSplatterModel(nn.Module):
             mcmc_vals = _mcmc_reg_values(self.opacities, self.scales, lo, ls)
             if torch.is_grad_enabled():
                 post_bwd = _mcmc_reg_grad_adder(self.opacities, self.scales, lo, ls)
+        # the launch-order buffer of this camera (see ``frame_key``): [C T + 1] int32, written by every training frame's
+        # loss launch, read by the next frame's compositing forward -- persistent, so that a captured step replays against it
         frame_slot, frame_order, frame_order_valid = None, None, False
         if frame_key is not None:
             frame_slot = self._frame_order_slot(frame_key, H, W)
@@ -1356,15 +1066,13 @@ class QEDSplatterModel(nn.Module):
         if optimizer is not None and torch.is_grad_enabled() and cfg.ssim_lambda > 0.0:
             tick = optimizer.take_tick()
         try:
-            render, alpha, self.info = rasterization(
+            render, alpha, info = self._rasterize(
                 means=self.means, quats=self.quats, scales=self.scales, opacities=self.opacities, colors=colors,
-                viewmats=viewmat, Ks=K, width=W, height=H, tile_size=16, packed=False, near_plane=0.01, far_plane=1e10,
-                render_mode="RGB+D", sh_degree=deg, sparse_grad=False, absgrad=True,
-                rasterize_mode=cfg.rasterize_mode, _flags=flags, _sh_rest=sh_rest, _sync=sync, _vsplat_holder=holder,
-                _c2w=cam_c2w, _tile_order=frame_order if frame_order_valid else None, _post_bwd=post_bwd)
-            self.xys = self.info["means2d"]
-            self.radii = self.info["radii"][0]
-            self.last_viewmat, self.last_sh_degree = viewmat, deg
+                viewmats=viewmat, Ks=K, width=W, height=H, render_mode="RGB+D", sh_degree=deg, _flags=flags,
+                _sh_rest=sh_rest, _sync=sync, _vsplat_holder=holder, _c2w=cam_c2w,
+                _tile_order=frame_order if frame_order_valid else None, _post_bwd=post_bwd)
+            attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
+            attrs["last_viewmat"], attrs["last_sh_degree"] = viewmat, deg
             # (the compositing node keeps the forward pass's per-tile costs: the loss launch sorts them for its backward)
             tile_cost = getattr(render.grad_fn, "tile_cost", None) if torch.is_grad_enabled() else None
             total, parts = _FusedImageLoss.apply(render, alpha, bg.contiguous(), gt_rgb, gt_depth, mask,
@@ -1383,56 +1091,6 @@ class QEDSplatterModel(nn.Module):
         if mcmc_vals is None:
             return {"loss": total, "main_loss": parts[0], "depth_loss": parts[1]}
         out = {"loss": total + mcmc_vals[2], "main_loss": parts[0]}
-        if lo > 0.0:
-            out["mcmc_opacity_reg"] = mcmc_vals[0]
-        if ls > 0.0:
-            out["mcmc_scale_reg"] = mcmc_vals[1]
+        self._put_mcmc_regs(out, lo, ls, mcmc_vals)
         out["depth_loss"] = parts[1]
         return out
-
-
-def _mcmc_reg_values(opacities: Tensor, scales: Tensor, lo: float, ls: float) -> Tensor:
-    """[3] device tensor (lo mean(sigmoid(opacities)), ls mean(exp(scales)), their sum): qed_mcmc_reg's deterministic fold."""
-    n = opacities.shape[0]
-    out = torch.empty(3, dtype=torch.float32, device=opacities.device)
-    ws = torch.empty(L.MCMC_REG_WS_DOUBLES, dtype=torch.float64, device=opacities.device)
-    L.check(L.load().qed_mcmc_reg(n, L.ptr(scales), L.ptr(opacities), lo, ls, L.ptr(out), None, None, None, None,
-                                  L.ptr(ws), _stream()), "qed_mcmc_reg")
-    return out
-
-
-def _mcmc_reg_grad_adder(opacities: Tensor, scales: Tensor, lo: float, ls: float):
-    """The projection backward's ``post_bwd`` of fused_loss: adds d(reg_o + reg_s) to the scale / opacity gradient rows."""
-    def add(v_scales: Tensor, v_opacities: Tensor) -> None:
-        L.check(L.load().qed_mcmc_reg(opacities.shape[0], L.ptr(scales), L.ptr(opacities), lo, ls, None, L.ptr(v_scales),
-                                      L.ptr(v_opacities), None, None, None, _stream()), "qed_mcmc_reg")
-    return add
-
-
-class _McmcReg(torch.autograd.Function):
-    """Splatfacto's MCMC regularisers (mcmc_opacity_reg, mcmc_scale_reg) of get_loss_dict: one pass for both values, one
-    for both gradients (scaled by the device-resident upstream gradients: no host sync)."""
-
-    @staticmethod
-    def forward(ctx, opacities, scales, lo, ls):
-        ctx.set_materialize_grads(False)
-        opacities, scales = opacities.detach().contiguous(), scales.detach().contiguous()
-        vals = _mcmc_reg_values(opacities, scales, lo, ls)
-        ctx.save_for_backward(opacities, scales)
-        ctx.lo, ctx.ls = lo, ls
-        return vals[0], vals[1]
-
-    @staticmethod
-    def backward(ctx, g_o, g_s):
-        opacities, scales = ctx.saved_tensors
-        lo = ctx.lo if g_o is not None else 0.0
-        ls = ctx.ls if g_s is not None else 0.0
-        v_opac = torch.zeros_like(opacities) if ctx.needs_input_grad[0] else None
-        v_scales = torch.zeros_like(scales) if ctx.needs_input_grad[1] else None
-        if v_opac is not None or v_scales is not None:
-            up_o = g_o.to(torch.float32).contiguous() if g_o is not None else None
-            up_s = g_s.to(torch.float32).contiguous() if g_s is not None else None
-            L.check(L.load().qed_mcmc_reg(opacities.shape[0], L.ptr(scales), L.ptr(opacities), lo, ls, None,
-                                          L.ptr(v_scales), L.ptr(v_opac), L.ptr(up_o), L.ptr(up_s), None, _stream()),
-                    "qed_mcmc_reg")
-        return v_opac, v_scales, None, None

@@ -202,7 +202,7 @@ def backward_with_early_gather(model, losses, world_size: int, group=None) -> No
     captured into a graph -- issued from the worker thread during a capture, its work object reaches the watchdog, which
     queries an event recorded on a capturing stream (hipErrorCapturedEvent) and aborts the process.  From the capturing
     thread itself the collectives are captured (bench.py --dp-one-graph)."""
-    from .model import _unit_grad
+    from .losses import _unit_grad
     from .rasterization import _VSPLAT_REGISTRY
     info = model.info
     names = ("means2d", "conics", "colors", "opacities", "depths")

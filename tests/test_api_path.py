@@ -350,6 +350,47 @@ def test_batch_validation_bool_mask_uint8_image_wrong_size(cuda):
         m.fused_loss(cam, dict(batch, mask=mask[: h - 1]))
 
 
+def test_fused_loss_refuses_an_image_smaller_than_the_ssim_window(cuda, monkeypatch):
+    """32 x 32 at the first stage of the resolution schedule is rendered at 8 x 8: below the 11 x 11 SSIM window.  With
+    ssim_lambda > 0 the fused loss raises QedSplatError on the host, before one of its kernels is launched."""
+    from qed_splatter_amd import _lib
+    sc = scene(40, 32, 32, seed=6)
+    m, cam, batch = _model(sc, cuda, step=0, num_downscales=2, resolution_schedule=3000, ssim_lambda=0.2)
+    assert m._get_downscale_factor() == 4
+    calls = []
+    lib = _lib.load()
+    for name in ("qed_loss_reduce", "qed_ssim_fwd", "qed_ssim_fwd_step", "qed_loss_grad_ssim", "qed_loss_grad"):
+        monkeypatch.setattr(lib, name, lambda *a, _n=name: calls.append(_n) or 0)
+    with pytest.raises(_lib.QedSplatError, match="smaller than the 11 x 11 SSIM window"):
+        m.fused_loss(cam, batch)
+    assert calls == [] and m.last_size == (8, 8)
+    assert int(cam.width[0]) == 32 and int(cam.height[0]) == 32
+
+
+def test_get_outputs_restores_the_camera_when_it_raises(cuda):
+    """At a downscale factor of 2 the camera is rescaled for the render: an exception on the way out of get_outputs -- an
+    unknown rasterize_mode, or one raised while the rescaled camera is being read -- leaves it at its own resolution."""
+    from qed_splatter_amd.model import PinholeCameras
+    sc = scene(40, 32, 32, seed=6)
+    m, cam, batch = _model(sc, cuda, step=0, num_downscales=1, resolution_schedule=3000, rasterize_mode="no such mode")
+    assert m._get_downscale_factor() == 2
+    fx = cam.fx.clone()
+    with pytest.raises(ValueError):
+        m.get_outputs(cam)
+    assert int(cam.width[0]) == 32 and int(cam.height[0]) == 32 and torch.equal(cam.fx, fx)
+
+    class Unreadable(PinholeCameras):
+        def get_intrinsics_matrices(self):
+            raise RuntimeError("no intrinsics")
+
+    K = sc["Ks"][0]
+    pose = sc["camera_to_worlds"][:1].to(cuda).requires_grad_(True)       # (a differentiated pose is read eagerly)
+    bad = Unreadable(pose, K[0, 0], K[1, 1], K[0, 2], K[1, 2], 32, 32)
+    with pytest.raises(RuntimeError, match="no intrinsics"):
+        m.get_outputs(bad)
+    assert int(bad.width[0]) == 32 and int(bad.height[0]) == 32 and torch.equal(bad.fx, fx)
+
+
 def test_scaled_loss_backward_through_the_fused_node(cuda):
     """(2 * loss).backward() gives 2 x the gradients (a weighted loss or a GradScaler upstream of the fused node)."""
     w, h, n = 96, 64, 800

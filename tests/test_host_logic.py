@@ -272,3 +272,18 @@ def test_optimisers_live_in_optim_and_stay_importable_from_model():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = "import sys, qed_splatter_amd.optim; assert 'qed_splatter_amd.model' not in sys.modules"
     subprocess.run([sys.executable, "-c", code], cwd=root, check=True, timeout=300)
+
+
+def test_loss_nodes_live_in_losses_and_stay_importable_from_model():
+    """qed_splatter_amd.model re-exports the loss nodes and their helpers (the tests and parallel.py knew them there), and
+    qed_splatter_amd.losses imports neither the model nor the operator when it loads (metrics -> losses -> _lib)."""
+    import subprocess
+    import sys
+    from qed_splatter_amd import losses, model
+    for name in ("_UNIT_GRADS", "_unit_grad", "_SSIM", "ssim", "_f32_image", "_ssim_key", "_PostProcess", "_ImageLosses",
+                 "_FusedImageLoss", "_mcmc_reg_values", "_mcmc_reg_grad_adder", "_McmcReg"):
+        assert getattr(model, name) is getattr(losses, name), name
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys, qed_splatter_amd.losses; "
+            "assert 'qed_splatter_amd.model' not in sys.modules and 'qed_splatter_amd.rasterization' not in sys.modules")
+    subprocess.run([sys.executable, "-c", code], cwd=root, check=True, timeout=300)
