@@ -12,8 +12,7 @@ from typing import Callable, Dict
 
 import torch
 
-from . import _lib as L
-from .rasterization import _workspace
+from .binning import _workspace
 
 
 class GraphedTrainStep:
@@ -51,7 +50,7 @@ class GraphedTrainStep:
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
         ws.poll_pending()
-        # (the captured buffers can never grow: the workspace keeps _Workspace.HEADROOM x the longest list seen)
+        # (the captured buffers can never grow: the workspace keeps binning._Workspace.HEADROOM x the longest list seen)
         self.graph = torch.cuda.CUDAGraph()
         # thread_local: HIP calls made by other threads (e.g. the RCCL watchdog polling its events in a
         # data-parallel job) must not invalidate this thread's capture
@@ -69,16 +68,11 @@ class GraphedTrainStep:
     def check(self) -> bool:
         """True when every replay since the last check had room for its list.  Otherwise: grow, re-capture, warn."""
         import warnings
-        status = self.ws.status.tolist()        # synchronises
-        if status[1]:
-            self.ws.status.zero_()
-            raise L.QedSplatError("radix-sort look-back watchdog fired")
-        if status[0]:
-            need, old = int(status[0]), self.ws.capacity
-            self.ws.status.zero_()
-            self.ws.overflows += 1
-            self.ws.capacity = max(self.ws.capacity, int(need * self.ws.HEADROOM) + 4096)
-            self.ws.force_sync = True           # the warm-up call of the re-capture reads M back
+        _, need, watchdog = self.ws.read_words()         # synchronises
+        if watchdog:
+            self.ws.watchdog_fired("radix-sort look-back watchdog fired")
+        if need:
+            old = self.ws.overflowed(need)      # (the warm-up call of the re-capture reads M back)
             warnings.warn(f"qed_splatter_amd: a graphed step needed {need} tile intersections, more than the captured "
                           f"capacity {old}; the frames since rendered empty and their optimiser steps were skipped on "
                           f"the device.  Re-captured with capacity {self.ws.capacity}.", RuntimeWarning, stacklevel=2)

@@ -43,7 +43,8 @@ from .losses import _PostProcess, _SSIM, _UNIT_GRADS, ssim  # noqa: F401  (also 
 from .optim import FlatAdam, QedAdam, QedAdamSet, exponential_decay_lr  # noqa: F401  (also importable from here)
 from .optim import _RAW_GRAD, _all_groups_stepped_by_qed_adam, _raw_grad
 from .optim import _FLAT_STATES  # noqa: F401  (the registry object itself: tests stand in for QedAdam through it)
-from .rasterization import rasterization, _stream, _workspace
+from .binning import _workspace
+from .rasterization import rasterization, _stream
 
 
 _FLIP_CACHE: Dict = {}
@@ -611,7 +612,7 @@ class QEDSplatterModel(nn.Module):
         # the count of the previous frame (eager or replayed) comes back here; an overflow drops every capture: their
         # buffers are too small, and the next call has to read M back
         ws.poll_pending()
-        if ws.force_sync or not ws.calibrated(shape_key) or not ws.host_words_ok:
+        if not ws.may_skip_readback(shape_key):
             cache.drop_all()
             return None
         seg = cache.get(key)

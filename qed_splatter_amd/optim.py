@@ -13,7 +13,8 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
-from .rasterization import _stream, _workspace
+from .binning import _workspace
+from .rasterization import _stream
 
 
 _RAW_GRAD = torch.Tensor.grad                 # the C-level descriptor: reads / writes the field without the subclass's hooks
@@ -24,7 +25,7 @@ def _raw_grad(p: Tensor) -> Optional[Tensor]:
 
 
 def _counted_step(opt, device) -> None:
-    """Tell the device's workspace that ``opt`` has counted a step behind the current frame (see _Workspace.counted_step)."""
+    """Tell the device's workspace that ``opt`` has counted a step behind the current frame (see binning._Workspace.counted_step)."""
     if device.type == "cuda":
         _workspace(device).counted_step(opt)
 
@@ -76,7 +77,7 @@ class FlatAdam:
 
     def on_skipped_step(self) -> None:
         """The device skipped the step this optimiser's host counter has already counted (the frame behind it overflowed its
-        intersection buffer: _Workspace.poll_pending): take it back, so that the bias corrections of the host-counter path
+        intersection buffer: binning._Workspace.poll_pending): take it back, so that the bias corrections of the host-counter path
         stay in step with the moments.  (The device-state path counts on the device, where the tick honours the skip.)
         Not in a data-parallel job: there the skip is collective (parallel.py) but only the rank whose frame overflowed
         hears of it on the host -- taking the step back here alone would make the replicas' bias corrections differ.  All

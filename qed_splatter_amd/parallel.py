@@ -451,8 +451,8 @@ def _local_overflow_word(device) -> torch.Tensor:
     buffer and is empty; what single-GPU optimiser launches take as ``skip_flag``)."""
     if device.type != "cuda":          # gloo rehearsals on CPU tensors (tests): no binning workspace; tests fill the word
         return _CPU_OVERFLOW_WORD
-    from .rasterization import _workspace
-    return _workspace(device).status[:1]
+    from .binning import _workspace
+    return _workspace(device).overflow_word
 
 
 _CPU_OVERFLOW_WORD = torch.zeros(1, dtype=torch.int32)

@@ -4,7 +4,7 @@ The reference-shaped route (Nerfstudio's trainer calling ``get_outputs`` -> ``ge
 ``backward`` -> one optimiser per group; /root/reference/qed_splatter/model.py:199-321, 73-118) enqueues ~25 launches per
 step from Python: three autograd nodes, ~40 allocations, one ctypes call per entry point.  On a slow host that bounds the
 step.  Nothing those launches are given depends on the step once the shape is fixed: the kernels read the intersection
-count from device memory and size their grids by a calibrated capacity (rasterization._Workspace), the parameters are
+count from device memory and size their grids by a calibrated capacity (binning._Workspace), the parameters are
 updated in place.  So once a shape has proved stable AND the host is the slower side (SegmentCache: a capture costs ~35 ms
 at 500 k Gaussians, a replay saves ~0.15 ms of host time and nothing while the device is the bottleneck) the device work
 behind ``get_outputs`` -- projection, binning, K6, the depth fix-up -- is captured into one graph, and its backward -- the
@@ -16,7 +16,7 @@ What the captured form gives up, and how it is guarded:
     Nerfstudio's trainer never reads them past the step; code that does gets an error from ``backward`` (generation
     check) instead of the wrong gradients, and ``config.graph_segments = False`` keeps every call's outputs;
   * the intersection buffer cannot grow inside a graph: the captured binning launch stores {M, overflow} into a pinned
-    word the next call looks at (exactly the eager asynchronous path, ``_Workspace.poll_pending``); an overflow renders
+    word the next call looks at (exactly the eager asynchronous path, ``binning._Workspace.poll_pending``); an overflow renders
     that frame empty, skips the optimiser launches on the device, and drops the segment -- the next calls run eagerly
     (regrown, re-calibrated) and capture again;
   * anything the capture was specialised on -- image size, number of Gaussians, SH degree in use, render / rasterize
@@ -34,7 +34,8 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
-from .rasterization import _workspace, manual_backward
+from .binning import _workspace, pinned_slot
+from .rasterization import manual_backward
 
 
 class _SegmentFn(torch.autograd.Function):
@@ -127,12 +128,8 @@ class OutputsSegment:
         self.generation = 0
         self.holder: list = []
         self._bwd: Dict[bool, Tuple] = {}
-        import ctypes
-        host = torch.zeros(4, dtype=torch.int32).pin_memory()
-        dptr = ctypes.c_void_p()                  # the device-side alias of the pinned word (rasterization._Workspace.host_slot)
-        L.check(L.load().qed_host_device_pointer(host.data_ptr(), ctypes.addressof(dptr)), "qed_host_device_pointer")
-        self.slot = (host.numpy(), dptr.value)
-        self._keep = host
+        words, address, self._keep = pinned_slot()    # what every replay's binning stores {M, overflow, watchdog} into
+        self.slot = (words, address)
         self._seen = [None, None, None]           # (source tensor, version) last copied into c2w / intr / bg
 
     # ---- capture ---------------------------------------------------------------------------------------------
@@ -214,7 +211,7 @@ class SegmentCache:
         the slower side.  So (i) ski rental: a key is captured only once it has been called as often as the capture costs
         in savings (~240 calls) -- a shape that densification replaces every 100 steps is never captured, a stable one is
         captured with at most twice the optimal overhead; and (ii) only if the host is the bottleneck: over those calls
-        it spent less than ``WAIT_FRAC`` of the wall time waiting for the device (``_Workspace.waited_s``: the host can
+        it spent less than ``WAIT_FRAC`` of the wall time waiting for the device (``binning._Workspace.waited_s``: the host can
         run at most one frame ahead).  A GPU-bound loop therefore stays eager, where a replay would buy nothing."""
 
     WARM_CALLS = 3
