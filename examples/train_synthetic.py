@@ -32,6 +32,9 @@ def main():
     ap.add_argument("--steps", type=int, default=700)
     ap.add_argument("--log-every", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--init-from-ply", metavar="PATH", default=None,
+                    help="start from the Gaussians QEDSplatterModel.from_ply seeds from this point cloud (the scene's "
+                         "camera and ground truth stay) instead of from the perturbed scene")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     L.load()
@@ -47,12 +50,16 @@ def main():
     with torch.no_grad():
         gt = gt_model.get_outputs(cam)
     batch = {"image": gt["rgb"].contiguous(), "depth_image": gt["depth"].contiguous()}
-    g = torch.Generator().manual_seed(a.seed + 1)
-    init = {k: sc[k].clone() for k in NAMES}
-    init["means"] += 0.01 * torch.randn(init["means"].shape, generator=g)
-    init["features_dc"] += 0.3 * torch.randn(init["features_dc"].shape, generator=g)
-    init["opacities"] -= 1.0
-    model = QEDSplatterModel(cfg, **{k: v.to(dev) for k, v in init.items()})
+    if a.init_from_ply:
+        model = QEDSplatterModel.from_ply(cfg, a.init_from_ply, seed=a.seed, device=dev)
+        print(f"seeded {model.num_points} Gaussians from {a.init_from_ply}")
+    else:
+        g = torch.Generator().manual_seed(a.seed + 1)
+        init = {k: sc[k].clone() for k in NAMES}
+        init["means"] += 0.01 * torch.randn(init["means"].shape, generator=g)
+        init["features_dc"] += 0.3 * torch.randn(init["features_dc"].shape, generator=g)
+        init["opacities"] -= 1.0
+        model = QEDSplatterModel(cfg, **{k: v.to(dev) for k, v in init.items()})
     model.step = 10_000
     opt = FlatAdam(model, means_schedule=FlatAdam.MEANS_SCHEDULE)
     dens = Densifier(model, opt, DensifyConfig(), num_train_data=1, seed=a.seed)

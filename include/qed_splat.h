@@ -581,6 +581,46 @@ int64_t qed_pd_workspace_bytes(int64_t n);
 int qed_pd_reduce(int32_t n, const float* dist, double threshold, int64_t k0, int64_t* count_under,
                   float* order_stats, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- exact k nearest neighbours on the index of qed_nn_build, and the seed initialisation of the Gaussians ----------
+ * Definition (the k = 1 definition above, applied k times): a candidate is the packed word bits(d2) << 32 | row with
+ * d2 = fma(dz, dz, fma(dy, dy, dx * dx)) on fp32 differences target - query; the answer of a query is its k smallest
+ * candidates in ascending order of the packed word (ascending d2, among equal d2 ascending row).  It is a pure
+ * function of the two fp32 clouds, bit for bit: it does not depend on the cell size, max_rings, the order of the
+ * queries (QED_NN_NATURAL_ORDER), the order of the workgroups or the path (grid or brute force).
+ * dist[n_query, k] = sqrtf(d2) and idx[n_query, k] (int32), row-major.  1 <= k <= 8.
+ * flags: QED_KNN_SKIP_FIRST computes the k + 1 smallest and drops the smallest (k_nearest_sklearn's [:, 1:]): for a cloud
+ *   queried against itself that removes the point itself, for duplicated points one of the zeros.
+ * qed_knn_query: the shell walk of qed_nn_query on the same workspace (built by qed_nn_build, same sizes); a query
+ *   stops once its list is full and its largest entry is closer than everything outside the visited box.  A query
+ *   not finished after max_rings shells is NOT written; its row goes to fallback[1 ..] as for qed_nn_query.
+ *   flags may also hold QED_NN_NATURAL_ORDER.
+ * qed_knn_brute: every target against the rows of `rows` (same convention as qed_nn_brute), one wave per query; no
+ *   workspace.
+ * Refused on the host: k outside [1, 8], n_target < k (k + 1 with QED_KNN_SKIP_FIRST), and what qed_nn_query /
+ * qed_nn_brute refuse (counts, max_rings, unknown flags, null buffers, a short workspace).
+ *
+ * qed_seed_gaussians: splatfacto's initialisation of five parameter groups from dist[n, k] (qed_knn_query on the cloud
+ *   itself with QED_KNN_SKIP_FIRST), one launch, written straight into the caller's (views of the flat) buffers:
+ *   scales[n,3] = logf(max(mean_j dist[i,j], min_distance)) in all three columns; quats[n,4] = (sqrt(1-u) sin 2 pi v,
+ *   sqrt(1-u) cos 2 pi v, sqrt(u) sin 2 pi w, sqrt(u) cos 2 pi w) with u, v, w in [0, 1) a function of (seed, row);
+ *   opacities[n] = logit(0.1); features_dc[n,3] = (c / 255 - 0.5) / 0.28209479177387814 for sh_coeffs > 1,
+ *   logit(c / 255, eps = 1e-10) for sh_coeffs == 1 (both in float64, rounded once), uniform [0, 1) for colors_u8 ==
+ *   NULL; features_rest[n, sh_coeffs - 1, 3] = 0 (may be NULL for sh_coeffs == 1).  status[QED_STATUS_WORDS]
+ *   (device, zeroed by the call): [0] = rows whose mean distance was below min_distance.  flags: 0.
+ * qed_seed_random_points: points[n,3] = (uniform [0, 1) - 0.5) * scale, a function of (seed, element).
+ * Refused on the host: n negative or >= 2^30, k outside [1, 8], sh_coeffs outside [1, 16], min_distance negative or not
+ * finite, unknown flags, null buffers.  No allocation, no sync. */
+#define QED_KNN_SKIP_FIRST 4
+int qed_knn_query(int32_t n_query, const float* query, int32_t n_target, void* workspace, int64_t workspace_bytes,
+                  int64_t n_query_capacity, int32_t k, int32_t max_rings, int32_t flags, float* dist, int32_t* idx,
+                  int32_t* fallback, void* stream);
+int qed_knn_brute(int32_t n_query, const float* query, int32_t n_target, const float* target, const int32_t* rows,
+                  int32_t k, int32_t flags, float* dist, int32_t* idx, void* stream);
+int qed_seed_gaussians(int32_t n, const float* dist, int32_t k, const uint8_t* colors_u8, int32_t sh_coeffs,
+                       uint64_t seed, float min_distance, int32_t flags, float* scales, float* quats, float* opacities,
+                       float* features_dc, float* features_rest, int32_t* status, void* stream);
+int qed_seed_random_points(int32_t n, uint64_t seed, float scale, float* points, void* stream);
+
 /* ---- fused multi-tensor Adam over one flat parameter buffer (config.py:44-68) --
  * n_groups contiguous segments; segment g covers elements [h_group_begin[g], h_group_begin[g+1])
  * and uses learning rate h_lr[g].  bias corrections use `step` (1-based).  The betas are doubles: 1 - beta is

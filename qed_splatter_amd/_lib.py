@@ -63,6 +63,10 @@ SIGNATURES = {
     "qed_nn_brute": (C.c_int, [_I, _P, _I, _P, _P, _P, _P, _P, _L, _P]),
     "qed_pd_workspace_bytes": (_L, [_L]),
     "qed_pd_reduce": (C.c_int, [_I, _P, _D, _L, _P, _P, _P, _L, _P]),
+    "qed_knn_query": (C.c_int, [_I, _P, _I, _P, _L, _L, _I, _I, _I, _P, _P, _P, _P]),
+    "qed_knn_brute": (C.c_int, [_I, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "qed_seed_gaussians": (C.c_int, [_I, _P, _I, _P, _I, _Q, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "qed_seed_random_points": (C.c_int, [_I, _Q, _F, _P, _P]),
     "qed_image_metrics": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _P, _P]),
     "qed_nanmean_exp": (C.c_int, [_I, _P, _I, _P, _P, _P]),
     "qed_step_metrics": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _I, _F, _P, _I, _I, _P, _F, _F, _F, _P, _P, _P, _P, _P]),
@@ -131,6 +135,7 @@ STATUS_WORDS = 4
 TILE = 16
 CL_TILE_WAVES, CL_QUADRANT_WAVES, CL_HALF_AND_HALF, CL_NO_CULL, CL_ORDER_READY = 1, 2, 3, 4, 8
 NN_NATURAL_ORDER, NN_AUTO_CELL = 1, 2
+KNN_SKIP_FIRST = 4
 BIN_AUTO, BIN_TWO_STAGE, BIN_TILE_SORT, BIN_BUCKET = 0, 1, 2, 3
 
 

@@ -23,20 +23,7 @@ constexpr int kMcmcNMax = 51;                 // gsplat's n_max: the ratio is cl
 constexpr int kMcmcRegBlocks = 1024;          // reg pass grid (block partials: 2 doubles each)
 static_assert(2 * kMcmcRegBlocks <= QED_MCMC_REG_WS_DOUBLES, "reg workspace");
 
-// generator streams: one per use, so that the draws of a relocation never correlate with the noise
-constexpr unsigned kRngRelocate = 1, kRngSample = 2, kRngNoise0 = 3, kRngNoise1 = 4;
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {       // splitmix64 finaliser
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ unsigned long long rng64(unsigned long long seed, unsigned long long counter,
-                                                    unsigned long long index, unsigned stream) {
-    return mix64(mix64(mix64(seed ^ ((unsigned long long)stream << 56)) ^ counter) ^ index);
-}
+// (the counter-based generator mix64 / rng64 and its stream numbers: qed_common.h)
 
 // sampling weight of a row: sigma 2^32 rounded, at least 1, for sigma > thresh; 0 otherwise (NaN included)
 __device__ __forceinline__ unsigned long long draw_weight(float logit, float thresh) {

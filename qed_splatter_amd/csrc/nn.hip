@@ -29,6 +29,9 @@
 // is the smallest squared distance and, among equals, the smallest row.  min is associative and commutative: both
 // paths return bit-identical (distance, index) whatever the cell size, max_rings, the slicing or the arrival order.
 // No floating-point atomics anywhere.
+//
+// k nearest neighbours (qed_knn_query, qed_knn_brute): the same index, the same walk and the same two paths with a sorted
+// list of the k smallest packed candidates per query in registers; see the section further down.
 #include "qed_common.h"
 
 #include <math.h>
@@ -460,6 +463,161 @@ nn_finish_kernel(int nq, const int* __restrict__ rows, const unsigned long long*
     }
 }
 
+// ---- k nearest neighbours (qed_knn_query, qed_knn_brute) -----------------------------------------------------------
+// The answer of a query is its KK smallest packed candidates in ascending order of the packed word (KK = k, or k + 1
+// with QED_KNN_SKIP_FIRST, of which the smallest is then dropped): the k = 1 definition applied KK times.  Both paths
+// look at every target at most once, so the list never holds a candidate twice, and "the KK smallest of a set" does not
+// depend on the order in which the set is walked or on how it is cut into parts that are merged later.
+// The list lives in registers: KK is a template parameter and every index is a compile-time constant.
+constexpr int kKnnMaxK = 8;                          // held: up to 9 words with QED_KNN_SKIP_FIRST
+constexpr int kKnnBruteMaxGrid = 4096;               // workgroups of the brute force (four queries each per round)
+
+// one compare-exchange per slot: the list stays ascending, the largest of the KK + 1 words falls off the end
+template <int KK>
+__device__ __forceinline__ void knn_insert(unsigned long long (&c)[KK], unsigned long long cand) {
+#pragma unroll
+    for (int j = 0; j < KK; ++j) {
+        const unsigned long long lo = cand < c[j] ? cand : c[j];
+        cand = cand < c[j] ? c[j] : cand;
+        c[j] = lo;
+    }
+}
+
+template <int KK>
+__device__ __forceinline__ void knn_write(const unsigned long long (&c)[KK], int skip, int k, long long row,
+                                          float* __restrict__ dist, int* __restrict__ idx) {
+#pragma unroll
+    for (int j = 0; j < KK; ++j)
+        if (j >= skip) {                                                       // (skip = KK - k: 0 or 1)
+            dist[row * k + (j - skip)] = nn_unpack_dist(c[j]);
+            idx[row * k + (j - skip)] = nn_unpack_row(c[j]);
+        }
+}
+
+template <int KK>
+__device__ __forceinline__ void knn_visit_run(int x, int y, int za, int zb, float qx, float qy, float qz, int n_cells,
+                                              const unsigned long long* __restrict__ cell_key, const int* __restrict__ cell_start,
+                                              const float4* __restrict__ sorted_pts, unsigned long long (&c)[KK]) {
+    const unsigned long long klo = nn_key(x, y, za), khi = nn_key(x, y, zb);
+    int j = nn_lower_bound(cell_key, n_cells, klo);
+    if (j >= n_cells || cell_key[j] > khi) return;
+    const int p0 = cell_start[j];
+    ++j;
+    while (j < n_cells && cell_key[j] <= khi) ++j;
+    const int p1 = cell_start[j];
+    for (int p = p0; p < p1; ++p) {
+        const float4 t = sorted_pts[p];
+        const unsigned long long cand = nn_pack(nn_dist2(qx, qy, qz, t.x, t.y, t.z), __float_as_int(t.w));
+        if (cand < c[KK - 1]) knn_insert<KK>(c, cand);
+    }
+}
+
+// nn_grid_query_kernel's walk (walls, caps, clipped box, face distance with its margin); a shell's cells are those at
+// Chebyshev distance exactly r, so every cell -- every target -- is visited once.  After shell r every unvisited point is
+// at least lb away: the list is final once it is full and its LARGEST entry is closer than that.
+template <int KK>
+__global__ void __launch_bounds__(kNnThreads)
+knn_grid_query_kernel(int nq, const float* __restrict__ query, const int* __restrict__ perm, const NnHeader* __restrict__ hdr,
+                      const unsigned long long* __restrict__ cell_key, const int* __restrict__ cell_start,
+                      const float4* __restrict__ sorted_pts, int max_rings, int k, float* __restrict__ dist,
+                      int* __restrict__ idx, int* __restrict__ fallback) {
+    const long long i = (long long)blockIdx.x * kNnThreads + threadIdx.x;
+    if (i >= nq) return;
+    int row = perm ? perm[i] : (int)i;
+    row = min(max(row, 0), nq - 1);
+    const float q[3] = {query[3 * (long long)row], query[3 * (long long)row + 1], query[3 * (long long)row + 2]};
+    const int n_cells = hdr->n_cells;
+    const float h = hdr->h, inv_h = hdr->inv_h, slop = hdr->slop;
+    const int dims[3] = {hdr->dims[0], hdr->dims[1], hdr->dims[2]};
+    float u[3];
+    int c[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        u[a] = nn_cell_coord(q[a], hdr->mn[a], inv_h);
+        c[a] = nn_cell_clamp(u[a], dims[a]);
+    }
+    unsigned long long best[KK];
+#pragma unroll
+    for (int j = 0; j < KK; ++j) best[j] = kNnNone;
+    bool done = false;
+    for (int r = 0; r < max_rings && !done; ++r) {
+        const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, dims[0] - 1);
+        const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, dims[1] - 1);
+        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, dims[2] - 1);
+        const int zl = c[2] - r, zh = c[2] + r;
+        for (int x = x0; x <= x1; ++x) {
+            const bool xb = x - c[0] == r || c[0] - x == r;
+            for (int y = y0; y <= y1; ++y) {
+                if (xb || y - c[1] == r || c[1] - y == r) {
+                    knn_visit_run<KK>(x, y, z0, z1, q[0], q[1], q[2], n_cells, cell_key, cell_start, sorted_pts, best);
+                } else {
+                    if (zl >= 0) knn_visit_run<KK>(x, y, zl, zl, q[0], q[1], q[2], n_cells, cell_key, cell_start, sorted_pts, best);
+                    if (zh < dims[2]) knn_visit_run<KK>(x, y, zh, zh, q[0], q[1], q[2], n_cells, cell_key, cell_start, sorted_pts, best);
+                }
+            }
+        }
+        bool covered = true;
+        float lb = INFINITY;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int lo = c[a] - r, hi = c[a] + r + 1;
+            if (lo > 0) { covered = false; lb = fminf(lb, fmaxf((u[a] - (float)lo) * h * (1.f - 1e-5f) - slop, 0.f)); }
+            if (hi < dims[a]) { covered = false; lb = fminf(lb, fmaxf(((float)hi - u[a]) * h * (1.f - 1e-5f) - slop, 0.f)); }
+        }
+        done = best[KK - 1] != kNnNone && (covered || __uint_as_float((unsigned)(best[KK - 1] >> 32)) < lb * lb);
+    }
+    if (done) {
+        knn_write<KK>(best, KK - k, k, row, dist, idx);
+    } else {
+        const int slot = atomicAdd(&fallback[0], 1);
+        if (slot < nq) fallback[1 + slot] = row;
+    }
+}
+
+// Brute force: one WAVE per query.  The target is cut into 64 interleaved slices, one per lane, each with a list of its
+// own; the lists meet in a butterfly of 64-bit shuffles (after a step a lane and its partner hold the same list, and
+// the next partner's list was built from other targets: still no candidate twice).  The four waves of a workgroup
+// share each LDS tile; consecutive lanes read consecutive float4s of it.
+template <int KK>
+__global__ void __launch_bounds__(kNnThreads)
+knn_brute_kernel(int nq, const float* __restrict__ query, int nt, const float* __restrict__ target,
+                 const int* __restrict__ rows, int k, float* __restrict__ dist, int* __restrict__ idx) {
+    __shared__ float4 tile[kBruteTile];
+    const int count = rows ? min(max(rows[0], 0), nq) : nq;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    constexpr int kWaves = kNnThreads / 64;
+    for (long long base = (long long)blockIdx.x * kWaves; base < count; base += (long long)gridDim.x * kWaves) {
+        const long long qi = base + wid;                                       // (base is the same for the whole workgroup)
+        const bool live = qi < count;
+        const long long row = live ? (rows ? min(max(rows[1 + qi], 0), nq - 1) : (int)qi) : 0;
+        const float qx = query[3 * row], qy = query[3 * row + 1], qz = query[3 * row + 2];
+        unsigned long long c[KK];
+#pragma unroll
+        for (int j = 0; j < KK; ++j) c[j] = kNnNone;
+        for (long long t0 = 0; t0 < nt; t0 += kBruteTile) {
+            const int cnt = (int)(nt - t0 < kBruteTile ? nt - t0 : kBruteTile);
+            __syncthreads();
+            for (int j = threadIdx.x; j < cnt; j += kNnThreads)
+                tile[j] = make_float4(target[3 * (t0 + j)], target[3 * (t0 + j) + 1], target[3 * (t0 + j) + 2], 0.f);
+            __syncthreads();
+            for (int j = lane; j < cnt; j += 64) {
+                const float4 t = tile[j];
+                const unsigned long long cand = nn_pack(nn_dist2(qx, qy, qz, t.x, t.y, t.z), (int)(t0 + j));
+                if (cand < c[KK - 1]) knn_insert<KK>(c, cand);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            unsigned long long other[KK];
+#pragma unroll
+            for (int j = 0; j < KK; ++j) other[j] = __shfl_xor(c[j], o, 64);
+#pragma unroll
+            for (int j = 0; j < KK; ++j) knn_insert<KK>(c, other[j]);
+        }
+        if (live && lane == 0) knn_write<KK>(c, KK - k, k, row, dist, idx);
+    }
+}
+
 // ---- PDMetrics' reductions ----------------------------------------------------------------------------------------
 // keys = the distances' bits (non-negative floats order like their bit patterns); count of distances under the threshold,
 // compared in float64 as the reference compares its float64 distances
@@ -669,4 +827,95 @@ extern "C" int qed_pd_reduce(int32_t n, const float* dist, double threshold, int
     hipLaunchKernelGGL(pd_pick_kernel, dim3(1), dim3(64), 0, st, n, (const unsigned long long*)(side ? w.keys_alt : w.keys),
                        (long long)k0, order_stats);
     return check_launch("qed_pd_reduce");
+}
+
+// ---- k nearest neighbours ----------------------------------------------------------------------------------------
+namespace qed {
+
+template <int KK>
+static void knn_launch_grid(unsigned grid_q, hipStream_t st, int nq, const float* query, const int* perm, const NnWorkspace& w,
+                            int max_rings, int k, float* dist, int* idx, int* fallback) {
+    hipLaunchKernelGGL(knn_grid_query_kernel<KK>, dim3(grid_q), dim3(kNnThreads), 0, st, nq, query, perm,
+                       (const NnHeader*)w.hdr, (const unsigned long long*)w.cell_key, (const int*)w.cell_start,
+                       (const float4*)w.sorted_pts, max_rings, k, dist, idx, fallback);
+}
+
+template <int KK>
+static void knn_launch_brute(unsigned grid, hipStream_t st, int nq, const float* query, int nt, const float* target,
+                             const int* rows, int k, float* dist, int* idx) {
+    hipLaunchKernelGGL(knn_brute_kernel<KK>, dim3(grid), dim3(kNnThreads), 0, st, nq, query, nt, target, rows, k, dist, idx);
+}
+
+#define QED_KNN_DISPATCH(held, fn, ...)                                                                      \
+    switch (held) {                                                                                          \
+        case 1: fn<1>(__VA_ARGS__); break;                                                                   \
+        case 2: fn<2>(__VA_ARGS__); break;                                                                   \
+        case 3: fn<3>(__VA_ARGS__); break;                                                                   \
+        case 4: fn<4>(__VA_ARGS__); break;                                                                   \
+        case 5: fn<5>(__VA_ARGS__); break;                                                                   \
+        case 6: fn<6>(__VA_ARGS__); break;                                                                   \
+        case 7: fn<7>(__VA_ARGS__); break;                                                                   \
+        case 8: fn<8>(__VA_ARGS__); break;                                                                   \
+        default: fn<9>(__VA_ARGS__); break;                                                                  \
+    }
+
+}  // namespace qed
+
+extern "C" int qed_knn_query(int32_t n_query, const float* query, int32_t n_target, void* workspace,
+                             int64_t workspace_bytes, int64_t n_query_capacity, int32_t k, int32_t max_rings,
+                             int32_t flags, float* dist, int32_t* idx, int32_t* fallback, void* stream) {
+    QED_REQUIRE(n_query >= 0 && n_query < (1 << 30), "n_query out of range");
+    QED_REQUIRE(k >= 1 && k <= kKnnMaxK, "k must be in [1, 8]");
+    QED_REQUIRE((flags & ~(QED_NN_NATURAL_ORDER | QED_KNN_SKIP_FIRST)) == 0, "unknown flags");
+    const int held = k + ((flags & QED_KNN_SKIP_FIRST) ? 1 : 0);
+    QED_REQUIRE(n_target >= held && n_target < (1 << 30),
+                "n_target out of range (at least k target points, k + 1 with QED_KNN_SKIP_FIRST)");
+    QED_REQUIRE(n_query_capacity >= n_query && n_query_capacity < (1ll << 30), "n_query_capacity out of range");
+    QED_REQUIRE(max_rings >= 0 && max_rings <= kNnMaxRings, "max_rings must be in [0, 64]");
+    QED_REQUIRE(fallback, "null buffers (fallback)");
+    hipStream_t st = (hipStream_t)stream;
+    if (n_query > 0) {
+        QED_REQUIRE(query && workspace && dist && idx, "null buffers");
+        if (workspace_bytes < nn_layout(nullptr, n_target, n_query_capacity).total_bytes) {
+            set_error("qed_knn_query: workspace too small (%lld < %lld)", (long long)workspace_bytes,
+                      nn_layout(nullptr, n_target, n_query_capacity).total_bytes);
+            return QED_E_WORKSPACE;
+        }
+        QED_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+    }
+    if (hipMemsetAsync(fallback, 0, sizeof(int32_t), st) != hipSuccess) {
+        set_error("qed_knn_query: memset failed");
+        return QED_E_LAUNCH;
+    }
+    if (n_query == 0) return QED_OK;
+    const NnWorkspace w = nn_layout(workspace, n_target, n_query_capacity);
+    const unsigned grid_q = (unsigned)(((long long)n_query + kNnThreads - 1) / kNnThreads);
+    const int* perm = nullptr;
+    if (!(flags & QED_NN_NATURAL_ORDER)) {
+        hipLaunchKernelGGL(nn_key_kernel, dim3(grid_q), dim3(kNnThreads), 0, st, n_query, query, (const NnHeader*)w.hdr,
+                           w.qkeys, w.qvals, w.q_n);
+        const int side = qed_sort_pairs((uint64_t*)w.qkeys, w.qvals, (uint64_t*)w.qkeys_alt, w.qvals_alt, w.q_n, n_query,
+                                        3 * kNnAxisBits, w.qsort_ws, w.qsort_ws_bytes, w.q_n + 4, stream);
+        if (side < 0) return side;
+        perm = side ? w.qvals_alt : w.qvals;
+    }
+    QED_KNN_DISPATCH(held, knn_launch_grid, grid_q, st, n_query, query, perm, w, max_rings, k, dist, idx, fallback);
+    return check_launch("qed_knn_query");
+}
+
+extern "C" int qed_knn_brute(int32_t n_query, const float* query, int32_t n_target, const float* target,
+                             const int32_t* rows, int32_t k, int32_t flags, float* dist, int32_t* idx, void* stream) {
+    QED_REQUIRE(n_query >= 0 && n_query < (1 << 30), "n_query out of range");
+    QED_REQUIRE(k >= 1 && k <= kKnnMaxK, "k must be in [1, 8]");
+    QED_REQUIRE((flags & ~QED_KNN_SKIP_FIRST) == 0, "unknown flags");
+    const int held = k + ((flags & QED_KNN_SKIP_FIRST) ? 1 : 0);
+    QED_REQUIRE(n_target >= held && n_target < (1 << 30),
+                "n_target out of range (at least k target points, k + 1 with QED_KNN_SKIP_FIRST)");
+    if (n_query == 0) return QED_OK;
+    QED_REQUIRE(query && target && dist && idx, "null buffers");
+    long long g = ((long long)n_query + kNnThreads / 64 - 1) / (kNnThreads / 64);
+    if (g > kKnnBruteMaxGrid) g = kKnnBruteMaxGrid;
+    QED_KNN_DISPATCH(held, knn_launch_brute, (unsigned)g, (hipStream_t)stream, n_query, query, n_target, target, rows, k,
+                     dist, idx);
+    return check_launch("qed_knn_brute");
 }

@@ -46,6 +46,24 @@ inline int check_launch(const char* what) {
 
 __device__ __forceinline__ float sigmoidf_dev(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
+// ---- the counter-based generator (mcmc.hip, seed.hip) ----------------------------------------------------------------
+// Every random number is a function of (seed, counter, index, stream).  One stream per use, so that the draws of one use
+// never correlate with those of another: 1-4 the MCMC strategy's, 5-9 the seed initialisation's.
+constexpr unsigned kRngRelocate = 1, kRngSample = 2, kRngNoise0 = 3, kRngNoise1 = 4;
+constexpr unsigned kRngSeedQuatU = 5, kRngSeedQuatV = 6, kRngSeedQuatW = 7, kRngSeedColor = 8, kRngSeedPoint = 9;
+
+__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {       // splitmix64 finaliser
+    z += 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ unsigned long long rng64(unsigned long long seed, unsigned long long counter,
+                                                    unsigned long long index, unsigned stream) {
+    return mix64(mix64(mix64(seed ^ ((unsigned long long)stream << 56)) ^ counter) ^ index);
+}
+
 // Row layout of the flat parameter / Adam-moment buffers: six groups in the order means, scales, quats, opacities,
 // features_dc, features_rest, each [N, width] (densify.hip, mcmc.hip).
 struct EmitLayout {

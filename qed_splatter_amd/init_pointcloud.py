@@ -354,9 +354,10 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "double": "f8", "float64": "f8"}
 
 
-def read_ply_positions(path) -> np.ndarray:
-    """The ``x y z`` of a PLY's vertex element as [N,3] (float32, or float64 if the file stores doubles).  ASCII and
-    binary little-endian; the vertex element must come first and have scalar properties only."""
+def _read_ply_vertex(path, optional=()):
+    """``(n, {name: column})`` of a PLY's vertex element: ``x y z`` and, when the file has all of them, the properties
+    named in ``optional``, each in its stored type.  ASCII and binary little-endian; the vertex element must come first
+    and have scalar properties only."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise RuntimeError(f"Failed to read point cloud: {path}")
@@ -385,17 +386,49 @@ def read_ply_positions(path) -> np.ndarray:
         names = [p[0] for p in props]
         if not seen_vertex or not all(k in names for k in "xyz"):
             raise RuntimeError(f"Failed to read point cloud (no x y z): {path}")
+        wanted = list("xyz") + (list(optional) if all(k in names for k in optional) else [])
         if fmt == "binary_little_endian":
             dt = np.dtype([(k, "<" + t) for k, t in props])
             rec = np.frombuffer(f.read(n * dt.itemsize), dtype=dt, count=n)
-            cols = [rec[k] for k in "xyz"]
+            cols = {k: rec[k] for k in wanted}
         elif fmt == "ascii":
             rows = np.loadtxt(f, dtype=np.float64, max_rows=n, ndmin=2) if n else np.zeros((0, len(props)))
-            cols = [rows[:, names.index(k)].astype(dict(props)[k]) for k in "xyz"]
+            cols = {k: rows[:, names.index(k)].astype(dict(props)[k]) for k in wanted}
         else:
             raise RuntimeError(f"unsupported PLY format {fmt!r}: {path}")
-    out_t = np.float64 if any(c.dtype == np.float64 for c in cols) else np.float32
-    return np.stack([c.astype(out_t) for c in cols], axis=1) if n else np.zeros((0, 3), dtype=out_t)
+    return n, cols
+
+
+def _stack_positions(n, cols) -> np.ndarray:
+    out_t = np.float64 if any(cols[k].dtype == np.float64 for k in "xyz") else np.float32
+    return np.stack([cols[k].astype(out_t) for k in "xyz"], axis=1) if n else np.zeros((0, 3), dtype=out_t)
+
+
+def read_ply_positions(path) -> np.ndarray:
+    """The ``x y z`` of a PLY's vertex element as [N,3] (float32, or float64 if the file stores doubles).  ASCII and
+    binary little-endian; the vertex element must come first and have scalar properties only."""
+    return _stack_positions(*_read_ply_vertex(path))
+
+
+def read_ply(path):
+    """``(positions, colors | None)`` of a PLY's vertex element: positions as ``read_ply_positions`` returns them,
+    colours [N,3] from the properties ``red green blue`` -- uint8 as stored (uchar), or float32 / float64 as Open3D's
+    tensor API writes them (the caller decides how to quantise) -- or None when the file has none.  Same supported
+    formats and the same refusals as ``read_ply_positions``."""
+    rgb = ("red", "green", "blue")
+    n, cols = _read_ply_vertex(path, rgb)
+    positions = _stack_positions(n, cols)
+    if rgb[0] not in cols:
+        return positions, None
+    kinds = {cols[k].dtype.kind for k in rgb}
+    if kinds == {"f"}:
+        col_t = np.float64 if any(cols[k].dtype == np.float64 for k in rgb) else np.float32
+    elif all(cols[k].dtype == np.uint8 for k in rgb):
+        col_t = np.uint8
+    else:
+        raise RuntimeError(f"unsupported PLY (red green blue must be uchar or float): {path}")
+    colors = np.stack([cols[k].astype(col_t) for k in rgb], axis=1) if n else np.zeros((0, 3), dtype=col_t)
+    return positions, colors
 
 
 def write_ply(path, positions: np.ndarray, colors: np.ndarray = None) -> None:

@@ -319,7 +319,9 @@ class QEDSplatterModel(nn.Module):
 
     def __init__(self, config: Optional[QEDSplatterModelConfig] = None, *, means: Tensor, scales: Tensor,
                  quats: Tensor, opacities: Tensor, features_dc: Tensor, features_rest: Tensor,
-                 separate_params: bool = False, num_train_data: Optional[int] = None):
+                 separate_params: bool = False, num_train_data: Optional[int] = None, flat: Optional[Tensor] = None):
+        """``flat``: the six tensors are already views, in GROUP_ORDER, of this one contiguous float32 buffer
+        (seed_init.seed_gaussians): it is adopted without a copy (``separate_params`` still clones)."""
         super().__init__()
         self.config = config or QEDSplatterModelConfig()
         # one bilateral grid per training image (splatfacto's bil_grids; its own optimiser group "bilateral_grid")
@@ -348,19 +350,64 @@ class QEDSplatterModel(nn.Module):
         # one allocation, so the data-parallel all-reduce and the fused Adam step each
         # touch a single contiguous range and nothing is ever concatenated.
         total = sum(srcs[n].numel() for n in self.group_names)
-        flat = torch.empty(total, dtype=torch.float32, device=means.device)
+        adopt = flat is not None
+        if adopt:
+            begins = [sum(srcs[n].numel() for n in self.group_names[:g]) for g in range(len(self.group_names))]
+            # (a group without elements -- features_rest with sh_degree 0 -- has no address to compare: torch gives
+            # every empty tensor the data_ptr 0)
+            if not (flat.dtype == torch.float32 and flat.is_contiguous() and flat.numel() == total and all(
+                    srcs[n].dtype == torch.float32 and srcs[n].is_contiguous() and srcs[n].device == flat.device
+                    and (srcs[n].numel() == 0 or srcs[n].data_ptr() == flat.data_ptr() + 4 * b)
+                    for n, b in zip(self.group_names, begins))):
+                raise ValueError("flat= needs the six tensors to be float32 views of it in GROUP_ORDER")
+        else:
+            flat = torch.empty(total, dtype=torch.float32, device=means.device)
         self.group_begin: List[int] = [0]
         params = {}
         off = 0
         for name in self.group_names:
             src = srcs[name]
             n = src.numel()
-            flat[off:off + n] = src.reshape(-1).to(torch.float32)
+            if not adopt:
+                flat[off:off + n] = src.reshape(-1).to(torch.float32)
             params[name] = self._make_param(name, flat[off:off + n].view(src.shape))
             off += n
             self.group_begin.append(off)
         self._flat = flat
         self.gauss_params = nn.ParameterDict(params)          # same container name as SplatfactoModel
+
+    @classmethod
+    def from_seed_points(cls, config: Optional[QEDSplatterModelConfig], points, colors=None, *, random_init: bool = False,
+                         num_random: int = 50_000, random_scale: float = 10.0, seed: int = 0, k: int = 3,
+                         min_distance: float = 1e-7, device=None, **model_kw) -> "QEDSplatterModel":
+        """splatfacto's ``populate_modules`` on the GPU (seed_init.py): the Gaussians of a seed point cloud -- means = the
+        points, scales from the mean distance to the 3 nearest neighbours, random rotations, opacity 0.1, colours as SH
+        (``colors`` uint8 [N,3]; None: random).  ``random_init=True`` or no points: ``num_random`` points in a cube of
+        side ``random_scale``.  ``device``: where the model is built (None: the points' device, else the current one).
+        The model adopts the flat buffer the kernels wrote (no copy)."""
+        from . import seed_init as S
+        config = config or QEDSplatterModelConfig()
+        if device is None and isinstance(points, Tensor) and points.is_cuda:
+            device = points.device
+        with torch.cuda.device(device):              # (None: the current device; host points are uploaded to it)
+            if random_init or points is None or len(points) == 0:
+                here = torch.device("cuda", torch.cuda.current_device())
+                points, colors = S.random_points(num_random, random_scale, seed, here), None
+            g = S.seed_gaussians(points, colors, sh_degree=config.sh_degree, k=k, seed=seed, min_distance=min_distance)
+        return cls(config, **{n: g[n] for n in GROUP_ORDER}, flat=g["flat"], **model_kw)
+
+    @classmethod
+    def from_ply(cls, config: Optional[QEDSplatterModelConfig], ply_path, transform_matrix=None, scale_factor: float = 1.0,
+                 **kw) -> "QEDSplatterModel":
+        """``from_seed_points`` on what the reference's dataparser loads from ``sparse_pc.ply`` (``load_3d_points``):
+        positions through ``transform_matrix`` [3,4] (None: identity) and ``scale_factor``, colours as uint8."""
+        from . import seed_init as S
+        if transform_matrix is None:
+            transform_matrix = torch.eye(4, dtype=torch.float32)[:3]
+        loaded = S.load_3d_points(ply_path, transform_matrix, scale_factor)
+        if loaded is None:
+            return cls.from_seed_points(config, None, None, **kw)
+        return cls.from_seed_points(config, loaded["points3D_xyz"], loaded["points3D_rgb"], **kw)
 
     def _make_param(self, name: str, view: Tensor) -> nn.Parameter:
         """A leaf view of the flat buffer; the two SH groups can hold their gradient in compact form (lazy_sh_grad)."""

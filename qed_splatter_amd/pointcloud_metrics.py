@@ -37,7 +37,10 @@ from . import _lib as L
 # Shells the grid search visits before a query is handed to the brute-force kernel.  With the automatic cell size a
 # surface point finds its neighbour within two or three shells; shell r costs about 2 (2 r + 1)^2 cell look-ups, so a
 # query that is still open after 8 shells (some 1 300 look-ups) is cheaper to finish against the whole cloud
-# (profiles/pd_metrics.txt has the measured split between index build, grid query and fallback).
+# (profiles/pd_metrics.txt has the measured split between index build, grid query and fallback).  The k-NN search of
+# seed_init.py keeps the value.  Its fallback (qed_knn_brute) takes one wave per open query: measured at 2 M points, 1 000
+# open queries cost 4.5 ms and every further thousand 0.6 ms (profiles/seed_init.txt), so it suits the floaters of a real
+# cloud and not a cloud where most queries stay open (an explicit cell_size far too small, or max_rings = 1).
 DEFAULT_MAX_RINGS = 8
 
 
@@ -131,6 +134,36 @@ class NNIndex:
                 rows = L.ptr(fallback)
             L.check(lib.qed_nn_brute(nq, L.ptr(query), self.n, L.ptr(self.target), rows, L.ptr(dist), L.ptr(idx),
                                      L.ptr(brute_ws), brute_ws.numel() * 8, st), "qed_nn_brute")
+        return dist, idx, fallback
+
+    def knn(self, query: Tensor, k: int, max_rings: int = DEFAULT_MAX_RINGS, force_brute: bool = False,
+            natural_order: bool = False, skip_first: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+        """(dist float32[Nq,k], idx int32[Nq,k], fallback int32[1 + Nq]): the ``k`` nearest targets of every query in
+        ascending order of (squared distance, row) -- ``qed_knn_query`` finished by ``qed_knn_brute``; with
+        ``skip_first`` the nearest of ``k + 1`` is dropped (a cloud queried against itself: the point itself).  No host
+        synchronisation."""
+        lib = L.load()
+        assert query.is_cuda and query.dtype == torch.float32 and query.is_contiguous()
+        nq, k = int(query.shape[0]), int(k)
+        if nq > self.capacity:
+            raise ValueError(f"the index was built for {self.capacity} queries, got {nq}")
+        dev = query.device
+        dist = torch.empty(nq, k, dtype=torch.float32, device=dev)
+        idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
+        fallback = torch.zeros(1 + nq, dtype=torch.int32, device=dev)
+        skip = L.KNN_SKIP_FIRST if skip_first else 0
+        with torch.cuda.device(dev):
+            st = L.current_stream()
+            if force_brute:
+                fallback[0] = nq
+                rows = 0
+            else:
+                L.check(lib.qed_knn_query(nq, L.ptr(query), self.n, L.ptr(self.work), self.work.numel() * 8, self.capacity,
+                                          k, int(max_rings), skip | (L.NN_NATURAL_ORDER if natural_order else 0),
+                                          L.ptr(dist), L.ptr(idx), L.ptr(fallback), st), "qed_knn_query")
+                rows = L.ptr(fallback)
+            L.check(lib.qed_knn_brute(nq, L.ptr(query), self.n, L.ptr(self.target), rows, k, skip, L.ptr(dist),
+                                      L.ptr(idx), st), "qed_knn_brute")
         return dist, idx, fallback
 
 
