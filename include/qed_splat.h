@@ -428,7 +428,7 @@ int qed_image_losses_bwd(int32_t n_pix, const float* rgb, const float* depth, co
  * when pred_rgb/gt_rgb are NULL.  pred_rgb, gt_rgb: [n_pix,3]; depths: [n_pix]; valid depth =
  * finite(pred) & finite(gt) & gt > tolerance (0.1 in the reference).  workspace: QED_METRICS_WS_DOUBLES
  * doubles (per-workgroup partial sums; no zeroing needed).
- * rgb_ssim is qed_ssim_fwd's value; LPIPS (pretrained network) is not provided. */
+ * rgb_ssim is qed_ssim_fwd's value; rgb_lpips is the qed_lpips_* entry points' (weights are supplied by the caller). */
 int qed_image_metrics(int32_t n_pix, const float* pred_rgb, const float* gt_rgb, const float* pred_depth,
                       const float* gt_depth, float tolerance, double* workspace, float* out, void* stream);
 /* Everything get_metrics_dict (model.py:120-197) needs from one training step's images in ONE streaming pass + ONE fold,
@@ -450,6 +450,35 @@ int qed_step_metrics(int32_t n_pix, const float* pred_rgb, const float* gt_rgb, 
 /* out[0] = nanmean_i exp(x[i * stride]), i < n (NaN when nothing is left) -- the "avg_min_scale" entry of
  * get_metrics_dict (model.py:192-194).  workspace: QED_METRICS_WS_DOUBLES doubles. */
 int qed_nanmean_exp(int32_t n, const float* x, int32_t stride, double* workspace, float* out, void* stream);
+
+/* ---- LPIPS (AlexNet) from user-supplied weights: the rgb_lpips entry (metrics.py:83-112) ------------------------------
+ * The two images travel as a batch of two; feature maps are NHWC, float32[2][h][w][C].  Layers l = 0..4:
+ *   Cin -> Cout  3 -> 64, 64 -> 192, 192 -> 384, 384 -> 256, 256 -> 256;  kernel 11, 5, 3, 3, 3;  stride 4, 1, 1, 1, 1;
+ *   padding 2, 2, 1, 1, 1.  Output size of a layer: (in + 2 pad - kernel) / stride + 1.
+ * qed_lpips_conv: out[2][ho][wo][Cout] = relu(bias + conv(in)), in0 / in1 = the two inputs [in_h][in_w][Cin] (for l > 0
+ *   the two halves of the previous map).  l = 0 applies the input scaling (x - shift) / scale to the taps inside the
+ *   image; a padded tap is 0.  weights: the layer's filters packed as [Kp][Np], row k = (kh * kernel + kw) * Cin + c,
+ *   column = output channel, Kp = K rounded up to QED_LPIPS_TILE_K, Np = Cout rounded up to QED_LPIPS_TILE_N, zero in the
+ *   padding (qed_lpips_packed_floats(l) = Kp * Np; host arithmetic).  float32 in, float32 accumulation in the order
+ *   k = 0, 1, 2, ... (the f32-input matrix instruction): the same input gives the same bits.
+ * qed_lpips_pool: 3x3 max-pool, stride 2, no padding, floor, of in[2][in_h][in_w][channels]; in front of l = 1 and l = 2.
+ * qed_lpips_distance: layer l's map feat[2][height][width][Cout] and its lin[Cout] -> per-workgroup partial sums of
+ *   sum_c lin[c] (f0[c] / sqrt(eps + |f0|^2) - f1[c] / sqrt(eps + |f1|^2))^2, eps = 1e-8, in its fifth of `workspace`
+ *   (QED_LPIPS_WS_DOUBLES doubles, no zeroing needed).
+ * qed_lpips_finalize: after the five distance launches; n_pix0..4 = height * width of the five maps.  out[6] (device) =
+ *   {the LPIPS value, the five per-layer means}; folded in float64 in a fixed order, no atomics, no host synchronisation.
+ * Refused on the host: a layer outside 0..4, sizes below the window or beyond 32768, null buffers. */
+#define QED_LPIPS_TILE_K 16
+#define QED_LPIPS_TILE_N 64
+#define QED_LPIPS_WS_DOUBLES (5 * 256)
+int64_t qed_lpips_packed_floats(int32_t layer);
+int qed_lpips_conv(int32_t layer, int32_t in_h, int32_t in_w, const float* in0, const float* in1, const float* weights,
+                   const float* bias, float* out, void* stream);
+int qed_lpips_pool(int32_t channels, int32_t in_h, int32_t in_w, const float* in, float* out, void* stream);
+int qed_lpips_distance(int32_t layer, int32_t height, int32_t width, const float* feat, const float* lin,
+                       double* workspace, void* stream);
+int qed_lpips_finalize(int64_t n_pix0, int64_t n_pix1, int64_t n_pix2, int64_t n_pix3, int64_t n_pix4,
+                       const double* workspace, float* out, void* stream);
 
 /* ---- densification / culling ---------------------------------------------------
  * GPU side of the parent class's callbacks that consume model.py:249,289-292 (self.xys.absgrad,

@@ -70,6 +70,11 @@ SIGNATURES = {
     "qed_image_metrics": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _P, _P]),
     "qed_nanmean_exp": (C.c_int, [_I, _P, _I, _P, _P, _P]),
     "qed_step_metrics": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _I, _F, _P, _I, _I, _P, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "qed_lpips_packed_floats": (_L, [_I]),
+    "qed_lpips_conv": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "qed_lpips_pool": (C.c_int, [_I, _I, _I, _P, _P, _P]),
+    "qed_lpips_distance": (C.c_int, [_I, _I, _I, _P, _P, _P, _P]),
+    "qed_lpips_finalize": (C.c_int, [_L, _L, _L, _L, _L, _P, _P, _P]),
     "qed_ssim_maps_floats": (C.c_int64, [_I, _I]),
     "qed_ssim_sum_floats": (C.c_int64, [_I, _I]),
     "qed_ssim_fwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -120,6 +125,8 @@ METRICS_WS_DOUBLES = 10 * 1024           # QED_METRICS_WS_DOUBLES
 STEP_METRICS_WS_DOUBLES = 16 * 1024      # QED_STEP_METRICS_WS_DOUBLES
 BILAGRID_TV_WS_DOUBLES = 1024            # QED_BILAGRID_TV_WS_DOUBLES
 MCMC_REG_WS_DOUBLES = 2048               # QED_MCMC_REG_WS_DOUBLES
+LPIPS_WS_DOUBLES = 5 * 256               # QED_LPIPS_WS_DOUBLES
+LPIPS_TILE_K, LPIPS_TILE_N = 16, 64      # QED_LPIPS_TILE_K, QED_LPIPS_TILE_N
 F_ANTIALIASED = 1
 F_LOG_SCALES = 2
 F_LOGIT_OPAC = 4

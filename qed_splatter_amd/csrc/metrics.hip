@@ -9,7 +9,7 @@
 //         rmse_log = sqrt(nanmean (log gt - log pred)^2), a_k = mean [max(gt/pred, pred/gt) < 1.25^k];
 //         all NaN when no pixel is valid (metrics.py:134-143).
 //   SSIM  is qed_ssim_fwd's value (torchmetrics' reflect-pad + crop equals the unpadded "valid"
-//         window sums); LPIPS needs pretrained network weights and is out of scope.
+//         window sums); LPIPS is lpips.hip's, from weights the caller supplies (none are shipped).
 #include "qed_common.h"
 
 namespace qed {

@@ -7,13 +7,15 @@ synchronisations per step.  Here one streaming kernel (``qed_image_metrics``) pr
 the seven depth metrics, ``qed_ssim_fwd`` produces SSIM, and everything stays in device memory until the
 caller decides to log it.
 
-LPIPS needs the pretrained AlexNet/VGG weights torchmetrics downloads; it is not provided and the
-``lpips`` slot is NaN.  The point-cloud metrics of metrics.py:9-63 (``PDMetrics``, ``calculate_accuracy``,
+LPIPS needs the pretrained AlexNet weights torchmetrics downloads.  They are not shipped and never fetched: given the
+two weight files (``lpips_weights``, or the environment variable ``QED_LPIPS_WEIGHTS`` for ``RGBMetrics``) the ``lpips``
+slot is computed by ``lpips.py`` / ``csrc/lpips.hip``; without them it is NaN.  The point-cloud metrics of metrics.py:9-63 (``PDMetrics``, ``calculate_accuracy``,
 ``calculate_completeness``: cKDTree on the CPU in the reference) live in ``pointcloud_metrics.py`` on top of the
 nearest-neighbour kernels of ``csrc/nn.hip``; ``mean_angular_error`` (metrics.py:66-80) is below, as plain torch.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -65,8 +67,16 @@ def image_metrics(pred_rgb: Optional[Tensor], gt_rgb: Optional[Tensor], pred_dep
 _NANS: Dict[torch.device, Tensor] = {}
 
 
+def _lpips_or_nan(pred_rgb: Tensor, gt_rgb: Tensor, lpips_weights) -> Tensor:
+    """The ``rgb_lpips`` entry: lpips.lpips on the images the other metrics were taken from, or the cached NaN."""
+    if lpips_weights is None:
+        return _nan(pred_rgb.device)
+    from .lpips import lpips
+    return lpips(pred_rgb, gt_rgb, lpips_weights)
+
+
 def _nan(device) -> Tensor:
-    """LPIPS needs pretrained weights that are not here: one cached NaN scalar per device instead of a fill per step."""
+    """LPIPS without weights (none were supplied): one cached NaN scalar per device instead of a fill per step."""
     t = _NANS.get(device)
     if t is None:
         t = _NANS[device] = torch.full((), float("nan"), device=device)
@@ -96,12 +106,14 @@ def ssim_value(pred_rgb: Tensor, gt_rgb: Tensor, keep_maps: bool = False):
 
 @torch.no_grad()
 def step_metrics(pred_rgb: Tensor, gt_rgb: Tensor, pred_depth: Optional[Tensor], gt_depth: Optional[Tensor],
-                 scales_last: Optional[Tensor], ssim_lambda: float, depth_lambda: float, tolerance: float = 0.1):
+                 scales_last: Optional[Tensor], ssim_lambda: float, depth_lambda: float, tolerance: float = 0.1,
+                 lpips_weights=None):
     """The whole of get_metrics_dict's image arithmetic for one TRAINING step in three launches -- qed_ssim_fwd (with the
     coefficient maps the loss's backward pass needs) + qed_step_metrics (one streaming pass, one fold): MSE / PSNR, the
     seven depth metrics, the SSIM value, avg_min_scale, and the loss sums get_loss_dict would compute from the same images
     a moment later.  Returns (metrics dict, shared) where ``shared`` is what QEDSplatterModel.get_loss_dict takes over:
-    {"key", "maps_sum", "inputs", "loss": (sums, losses), "depth_key"}."""
+    {"key", "maps_sum", "inputs", "loss": (sums, losses), "depth_key"}.  ``lpips_weights`` (a lpips.LpipsWeights): fill
+    ``rgb_lpips`` from the same two images, after these launches and without touching what they share."""
     lib = L.load()
     H, W, _ = pred_rgb.shape
     n_pix = H * W
@@ -123,7 +135,7 @@ def step_metrics(pred_rgb: Tensor, gt_rgb: Tensor, pred_depth: Optional[Tensor],
                                  1.0 / n_out, L.ptr(scales_last) if n_sc else None, n_sc, sc_stride,
                                  None, 1.0 - ssim_lambda, float(depth_lambda), float(ssim_lambda), L.ptr(sums), L.ptr(losses),
                                  L.ptr(work), L.ptr(out), st), "qed_step_metrics")
-    md = {"rgb_mse": out[0], "rgb_psnr": out[1], "rgb_ssim": out[10], "rgb_lpips": _nan(dev)}
+    md = {"rgb_mse": out[0], "rgb_psnr": out[1], "rgb_ssim": out[10], "rgb_lpips": _lpips_or_nan(p, g, lpips_weights)}
     if pd is not None:
         md.update({n: out[i] for i, n in enumerate(METRIC_NAMES) if n.startswith("depth_") and n != "depth_n_valid"})
     if n_sc:
@@ -158,13 +170,26 @@ def _to_hwc(img: Tensor) -> Tensor:
 
 
 class RGBMetrics(torch.nn.Module):
-    """Mirror of metrics.py:84-112: ``forward(pred, gt) -> (psnr, ssim, lpips)`` as 0-dim device tensors."""
+    """Mirror of metrics.py:84-112: ``forward(pred, gt) -> (psnr, ssim, lpips)`` as 0-dim device tensors.
+
+    ``lpips_weights``: a path (one merged file, or a pair as a sequence or joined by ``os.pathsep``) or a
+    ``lpips.LpipsWeights``.  With None the environment variable ``QED_LPIPS_WEIGHTS`` is looked at, once, here; with
+    neither the third value is NaN."""
+
+    def __init__(self, lpips_weights=None):
+        super().__init__()
+        from .lpips import ENV_VAR, resolve_weights
+        if lpips_weights is None:
+            lpips_weights = os.environ.get(ENV_VAR) or None
+        self._lpips = resolve_weights(lpips_weights, "cpu")          # moved to the images' device at the first call
 
     @torch.no_grad()
     def forward(self, pred: Tensor, gt: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
         p, g = _to_hwc(pred), _to_hwc(gt)
         m = image_metrics(p, g)
-        return m[1], ssim_value(p, g), _nan(p.device)
+        if self._lpips is not None:
+            self._lpips = self._lpips.to(p.device)
+        return m[1], ssim_value(p, g), _lpips_or_nan(p, g, self._lpips)
 
 
 class DepthMetrics(torch.nn.Module):
@@ -184,13 +209,14 @@ class DepthMetrics(torch.nn.Module):
 
 @torch.no_grad()
 def metrics_dict(pred_rgb: Tensor, gt_rgb: Tensor, pred_depth: Optional[Tensor], gt_depth: Optional[Tensor],
-                 tolerance: float = 0.1, keep_ssim_maps: bool = False) -> Dict[str, Tensor]:
+                 tolerance: float = 0.1, keep_ssim_maps: bool = False, lpips_weights=None) -> Dict[str, Tensor]:
     """The image part of get_metrics_dict (model.py:152-182) in two launches, values left on the device.
-    ``keep_ssim_maps``: the entry "_ssim_shared" carries the SSIM forward for a loss on the same images (ssim_value)."""
+    ``keep_ssim_maps``: the entry "_ssim_shared" carries the SSIM forward for a loss on the same images (ssim_value).
+    ``lpips_weights`` (a lpips.LpipsWeights): fill ``rgb_lpips`` instead of leaving it NaN."""
     m = image_metrics(pred_rgb, gt_rgb, pred_depth, gt_depth, tolerance)
     ssim = ssim_value(pred_rgb, gt_rgb, keep_maps=keep_ssim_maps)
     out = {"rgb_mse": m[0], "rgb_psnr": m[1], "rgb_ssim": ssim[0] if keep_ssim_maps else ssim,
-           "rgb_lpips": _nan(m.device)}
+           "rgb_lpips": _lpips_or_nan(pred_rgb, gt_rgb, lpips_weights)}
     if keep_ssim_maps:
         out["_ssim_shared"] = ssim[1]
     if pred_depth is not None:

@@ -119,6 +119,9 @@ class QEDSplatterModelConfig:
     # place (_LazySHGradParameter); after QedAdam has consumed the compact form it is None (as after zero_grad()).  False:
     # always write the full gradients
     lazy_sh_grad: bool = True
+    # LPIPS weights for the rgb_lpips entry of get_metrics_dict (lpips.py): one merged file, or AlexNet's and the lin
+    # layers' files joined by os.pathsep.  None: the entry stays NaN.  Nothing is ever fetched
+    lpips_weights: Optional[str] = None
 
     @classmethod
     def synthetic(cls, **kw) -> "QEDSplatterModelConfig":
@@ -969,7 +972,8 @@ class QEDSplatterModel(nn.Module):
         """Same keys as the reference, but every value is a 0-dim DEVICE tensor (or an int for
         ``gaussian_count``): the reference's ``float(...)``/``.item()`` per entry (model.py:160-182)
         is a device synchronisation each, which caps iterations/s regardless of kernel speed; the
-        caller converts when (and if) it logs.  ``rgb_lpips`` is NaN (no pretrained weights here)."""
+        caller converts when (and if) it logs.  ``rgb_lpips`` is NaN unless ``config.lpips_weights`` names the weight
+        files (none are shipped); with them it is lpips.lpips of the same two images, launched after the others."""
         from .metrics import metrics_dict as _image_metrics, nanmean_exp
         d = self._get_downscale_factor()
 
@@ -994,6 +998,7 @@ class QEDSplatterModel(nn.Module):
         # backward pass: compute that form once here and leave it for get_loss_dict (which checks that it is handed the
         # same tensors before using it)
         ctx = self.__dict__.get("_step")
+        lpips_w = self._lpips_weights()
         keep = (self.training and torch.is_grad_enabled() and self.config.ssim_lambda > 0.0 and d <= 1
                 and pred_rgb.is_cuda and pred_rgb.dtype == torch.float32 and ctx is not None and ctx.owns(outputs))
         with torch.no_grad():
@@ -1001,18 +1006,31 @@ class QEDSplatterModel(nn.Module):
                 # a training step: the metrics, and what the loss that follows needs from the same images, in one pass
                 from .metrics import step_metrics
                 out, shared = step_metrics(pred_rgb.detach(), gt_rgb, outputs["depth"].detach(), gt_depth,
-                                           self.scales[..., -1], float(self.config.ssim_lambda), float(self.config.depth_lambda))
+                                           self.scales[..., -1], float(self.config.ssim_lambda), float(self.config.depth_lambda),
+                                           lpips_weights=lpips_w)
                 ctx.ssim = shared
                 out["gaussian_count"] = self.num_points
                 return _reference_key_order(out)
             out = dict(_image_metrics(pred_rgb.detach(), gt_rgb, outputs["depth"].detach() if has_depth else None, gt_depth,
-                                      keep_ssim_maps=keep))
+                                      keep_ssim_maps=keep, lpips_weights=lpips_w))
             kept = out.pop("_ssim_shared", None)
             if keep:
                 ctx.ssim = kept
             out["gaussian_count"] = self.num_points
             out["avg_min_scale"] = nanmean_exp(self.scales[..., -1])                  # model.py:192-194
         return _reference_key_order(out)
+
+    def _lpips_weights(self):
+        """config.lpips_weights, loaded and packed once per device (None when it is not set)."""
+        spec = getattr(self.config, "lpips_weights", None)
+        if spec is None:
+            return None
+        cached = self.__dict__.get("_lpips_cache")
+        if cached is None or cached[0] != spec or cached[1].device != self.device:
+            from .lpips import resolve_weights
+            cached = (spec, resolve_weights(spec, self.device))
+            self.__dict__["_lpips_cache"] = cached
+        return cached[1]
 
     @property
     def intersection_overflows(self) -> int:
