@@ -6,7 +6,10 @@ culling on the reference's schedule, and evaluation metrics without per-step hos
     python examples/train_synthetic.py --gaussians 20000 --width 640 --height 360 --steps 700
 
 The scene is the synthetic generator of SURVEY 8(d); the ground truth is rendered from the scene itself
-and training starts from perturbed parameters, so the loss has somewhere to go.
+and training starts from perturbed parameters, so the loss has somewhere to go.  The same loop over a dataset
+directory (a different camera and cached uint8 frame every step) is the package's trainer:
+
+    python -m qed_splatter_amd.train --data DIR --steps 30000 --eval-every 5000 --save ckpt.pt
 """
 import argparse
 import os

@@ -767,6 +767,24 @@ int qed_mcmc_reg(int32_t N, const float* scales, const float* opacities, float o
                  float* out, float* grad_scales, float* grad_opacities, const float* v_opacity_reg,
                  const float* v_scale_reg, double* workspace, void* stream);
 
+/* ---- the ground truth of one training frame, from a cached dataset frame (csrc/ingest.hip) ------------------------
+ * What the parent's get_gt_img + composite_with_background and the loss mask (model.py:88-97) make of batch["image"],
+ * batch["depth_image"] and batch["mask"], in ONE launch: d x d box means (d in 1..8; Ho = height / d, Wo = width / d,
+ * the remainder rows and columns dropped).
+ *   image  [height,width,channels], channels 3 or 4: uint8 (scaled by 1/255) or, with image_is_f32, float32
+ *   depth  [height,width]: uint16 (times depth_scale) or, with depth_is_f32, float32 (depth_scale is not read); NULL:
+ *          no depth plane (gt_depth is not written)
+ *   mask   [height,width] bytes, non-zero = 1, or NULL;  background[3] floats
+ *   gt_rgb [Ho,Wo,3]: the channel means, with 4 channels composited AFTER averaging: a rgb + (1 - a) background
+ *   gt_depth [Ho,Wo]: the mean, zeros included;  gt_mask [Ho,Wo] (NULL without mask): the mean of 0 / 1
+ * Integer inputs are summed exactly and scaled once (uint8: sum * (1.0f / (255 d^2)); uint16: sum * (depth_scale / d^2));
+ * float inputs are summed in row-major block order and multiplied by 1 / d^2.  At d = 1 float inputs pass through.
+ * Refused on the host: d outside 1..8, channels not 3 or 4, an empty output, NULL buffers.  No allocation, no sync. */
+int qed_ingest_ground_truth(int32_t height, int32_t width, int32_t d, const void* image, int32_t channels,
+                            int32_t image_is_f32, const void* depth, int32_t depth_is_f32, float depth_scale,
+                            const uint8_t* mask, const float* background, float* gt_rgb, float* gt_depth,
+                            float* gt_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

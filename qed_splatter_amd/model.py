@@ -725,12 +725,55 @@ class QEDSplatterModel(nn.Module):
 
     def _ground_truth(self, batch, background: Tensor, H: int, W: int):
         """(gt_rgb, gt_depth, mask | None) as the loss kernels read them: uint8 -> float, downscaled, on the device, RGBA
-        composited onto ``background``; each checked against the render size BEFORE a kernel reads it by raw pointer."""
+        composited onto ``background``; each checked against the render size BEFORE a kernel reads it by raw pointer.
+        A datamanager.GpuBatch (the cached frame as stored) whose tensors are contiguous and on this device takes ONE
+        launch for all of it (_ingest_ground_truth); any other batch the eager chain below."""
+        if type(batch) is not dict:
+            fused = self._ingest_ground_truth(batch, background, H, W)
+            if fused is not None:
+                return fused
         gt_rgb = self.composite_with_background(self.get_gt_img(batch["image"]), background)
         mask = self._loss_mask(batch, (H, W))
         gt_rgb = _f32_image(gt_rgb[..., :3] if gt_rgb.shape[-1] > 3 else gt_rgb, H * W * 3, "batch['image']", self.device)
         gt_depth = _f32_image(self.get_gt_img(batch["depth_image"]), H * W, "batch['depth_image']", self.device)
         return gt_rgb, gt_depth, mask
+
+    def _ingest_ground_truth(self, batch, background: Tensor, H: int, W: int):
+        """``_ground_truth`` of a datamanager.GpuBatch in one launch (qed_ingest_ground_truth): uint8 / RGBA colour, uint16 or
+        float32 depth and the bool mask as the cache stores them -> the three float32 images at this step's downscale
+        factor, composited onto this step's background.  None when the batch does not qualify (not a GpuBatch, tensors
+        that are not contiguous or not on the model's device, other dtypes): the caller then takes the eager chain.  A
+        frame whose size does not give the render's is refused before the launch.  The outputs are fresh allocations (the
+        autograd nodes of the loss keep them for the backward pass), with one exception: a float32 depth map at full
+        resolution is its own ground truth, and the batch's tensor itself is returned for it, as on the eager chain.
+        Nothing writes into it."""
+        from .datamanager import GpuBatch, ingest_ground_truth
+        if not isinstance(batch, GpuBatch):
+            return None
+        dev = self.device
+        image, depth = batch.raw("image"), batch.raw("depth_image")
+        mask = batch.raw("mask") if "mask" in batch else None
+        d = self._get_downscale_factor()
+        if dev.type != "cuda" or not 1 <= d <= 8 or background.numel() != 3:
+            return None
+        for t in (image, depth, mask):
+            if t is not None and not (torch.is_tensor(t) and t.device == dev and t.is_contiguous()):
+                return None
+        if image.dtype not in (torch.uint8, torch.float32) or image.dim() != 3 or image.shape[2] not in (3, 4) \
+                or depth.dtype not in (torch.uint16, torch.float32) or (mask is not None and mask.dtype != torch.bool):
+            return None
+        h, w, ch = image.shape
+        if (h // d, w // d) != (H, W):
+            raise L.QedSplatError(f"batch['image']: {tuple(image.shape)} at downscale factor {d} gives "
+                                  f"{h // d}x{w // d}, the render is {H}x{W}")
+        for name, t in (("depth_image", depth), ("mask", mask)):
+            if t is not None and t.numel() != h * w:
+                raise L.QedSplatError(f"batch['{name}']: {tuple(t.shape)} holds {t.numel()} values, its image has {h * w} pixels")
+        # (a float32 depth map at full resolution is its own ground truth, as on the eager route: not copied)
+        keep_depth = d == 1 and depth.dtype == torch.float32
+        gt_rgb, gt_depth, gt_mask = ingest_ground_truth(image, None if keep_depth else depth, mask, background.detach(), d,
+                                                        float(batch.raw("depth_scale")) if "depth_scale" in batch else 1.0)
+        return gt_rgb, (depth if keep_depth else gt_depth), gt_mask
 
     def _rasterize(self, **kw):
         """rasterization(...) with the arguments model.py:267-288 never varies; the callers pass what differs."""
