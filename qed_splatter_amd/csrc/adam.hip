@@ -211,7 +211,7 @@ adam_sh_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__
                     float dir[3];
 #pragma unroll
                     for (int j = 0; j < 3; ++j)                                      // campos = -R^T t
-                        dir[j] = mean[j] + (vm[0 + j] * vm[3] + vm[4 + j] * vm[7] + vm[8 + j] * vm[11]);
+                        dir[j] = mean[j] - campos_component(vm[0 + j], vm[4 + j], vm[8 + j], vm[3], vm[7], vm[11]);
                     const float inorm = rsqrtf(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
                     float b[K];
                     sh_basis<DEG>(dir[0] * inorm, dir[1] * inorm, dir[2] * inorm, b);

@@ -32,7 +32,7 @@ __device__ __forceinline__ Cam load_cam(const float* __restrict__ viewmats, cons
     // camera position = -R^T t  (translation of the inverse view matrix)
 #pragma unroll
     for (int j = 0; j < 3; ++j)
-        cam.campos[j] = -(cam.R[0 + j] * cam.t[0] + cam.R[3 + j] * cam.t[1] + cam.R[6 + j] * cam.t[2]);
+        cam.campos[j] = campos_component(cam.R[0 + j], cam.R[3 + j], cam.R[6 + j], cam.t[0], cam.t[1], cam.t[2]);
     return cam;
 }
 
@@ -60,7 +60,7 @@ __device__ __forceinline__ Cam load_cam_c2w(const float* __restrict__ c2w, const
     cam.fx = intr[4 * c]; cam.fy = intr[4 * c + 1]; cam.cx = intr[4 * c + 2]; cam.cy = intr[4 * c + 3];
 #pragma unroll
     for (int j = 0; j < 3; ++j)                          // as load_cam derives it from the view matrix (bit for bit)
-        cam.campos[j] = -(cam.R[0 + j] * cam.t[0] + cam.R[3 + j] * cam.t[1] + cam.R[6 + j] * cam.t[2]);
+        cam.campos[j] = campos_component(cam.R[0 + j], cam.R[3 + j], cam.R[6 + j], cam.t[0], cam.t[1], cam.t[2]);
     if (V_out != nullptr) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -864,7 +864,7 @@ project_bwd_kernel(int N, int C, const float* __restrict__ means, const float* _
             vq[0] += vqn[0]; vq[1] += vqn[1]; vq[2] += vqn[2]; vq[3] += vqn[3];
 
             if (v_viewmats != nullptr) {
-                // v_R = v_meanc mean^T + v_W M^T ; v_t = v_meanc ; campos = -R^T t feeds the SH direction
+                // v_R = v_meanc mean^T + v_W M^T ; v_t = v_meanc ; plus what the SH direction passes on (below)
                 const float vmc[3] = {vx, vy, vz};
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
@@ -875,15 +875,17 @@ project_bwd_kernel(int N, int C, const float* __restrict__ means, const float* _
                     }
                     vt[i] = vmc[i];
                 }
-                // dir = mean - campos, campos_j = -sum_i R_ij t_i  ->  v_campos = -v_dir
-                // v_R_ij += -v_campos_j * t_i = v_dir_j * t_i ;  v_t_i += sum_j v_dir_j R_ij
+                // dir = mean - campos.  The VALUE of campos is -R^T t (load_cam); its DERIVATIVE is that of the translation
+                // of inverse(viewmat), as gsplat forms it (torch.inverse, the inverse of a GENERAL matrix):
+                // d campos = R^-1 dR R^-1 t - R^-1 dt, at a rotation R^T dR R^T t - R^T dt.  With v_campos = -v_dir:
+                // v_R += (R v_dir) campos^T ;  v_t += R v_dir.  (Differentiating -R^T t itself gives the same along rotations
+                // but v_dir t^T across them, which is not what autograd hands the reference's camera optimiser at t != 0)
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
+                    const float rv = cam.R[3 * i] * vdir[0] + cam.R[3 * i + 1] * vdir[1] + cam.R[3 * i + 2] * vdir[2];
 #pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        vR[3 * i + j] += vdir[j] * cam.t[i];
-                        vt[i] += vdir[j] * cam.R[3 * i + j];
-                    }
+                    for (int j = 0; j < 3; ++j) vR[3 * i + j] += rv * cam.campos[j];
+                    vt[i] += rv;
                 }
             }
         }
@@ -966,7 +968,7 @@ sh_grad_from_views_kernel(int N, int n_views, const float* __restrict__ means, c
         float dir[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j)                                      // campos = -R^T t, as load_cam
-            dir[j] = mean[j] + (vm[0 + j] * vm[3] + vm[4 + j] * vm[7] + vm[8 + j] * vm[11]);
+            dir[j] = mean[j] - campos_component(vm[0 + j], vm[4 + j], vm[8 + j], vm[3], vm[7], vm[11]);
         const float inorm = rsqrtf(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]);
         float b[K];
         sh_basis<DEG>(dir[0] * inorm, dir[1] * inorm, dir[2] * inorm, b);

@@ -209,6 +209,14 @@ __device__ __forceinline__ int xcd_remap(int b, int n) {
 constexpr float SH_C0 = 0.28209479177387814f;
 constexpr float SH_C1 = 0.4886025119029199f;
 
+// Component j of the camera position -R^T t (the translation of the inverse view matrix); r0, r1, r2 = column j of R.
+// The SH direction mean - campos is formed by the projection (forward and backward), by qed_sh_grad_from_views and by
+// qed_adam_step_sh, and next to the camera the rounding of campos is amplified by |campos| / |mean - campos| in it: the
+// fmas are written out so that every kernel rounds it the same way, whatever the compiler contracts around the call.
+__device__ __forceinline__ float campos_component(float r0, float r1, float r2, float t0, float t1, float t2) {
+    return -__fmaf_rn(r0, t0, __fmaf_rn(r1, t1, r2 * t2));
+}
+
 // basis values b[0..K) for unit direction (x,y,z)
 template <int DEG>
 __device__ __forceinline__ void sh_basis(float x, float y, float z, float* b) {
