@@ -785,6 +785,31 @@ int qed_ingest_ground_truth(int32_t height, int32_t width, int32_t d, const void
                             const uint8_t* mask, const float* background, float* gt_rgb, float* gt_depth,
                             float* gt_mask, void* stream);
 
+/* ---- a distorted dataset frame resampled to a pinhole (csrc/undistort.hip) -----------------------------------------
+ * What nerfstudio's datamanager does on the CPU to every frame of a camera with distortion, while the image cache is
+ * filled: ONE launch over all planes of a frame.  The definitions are written out in qed_splatter_amd/undistort.py.
+ * Per output pixel (j, i): x = (j + 0.5 - cx') / fx', y likewise under new_K; (xd, yd) = distort(x, y);
+ * (u, v) = (fx xd + cx, fy yd + cy) under src_K -- evaluated in float64 from the float32 parameters, the blend in float32.
+ *   model  0: OPENCV  rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3, xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2),
+ *             yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y  (k4 must be 0)
+ *          1: OPENCV_FISHEYE  t = atan(r), td = t (1 + k1 t^2 + k2 t^4 + k3 t^6 + k4 t^8), (xd, yd) = (td / r)(x, y),
+ *             the identity at r = 0  (p1, p2 must be 0)
+ *   src_K[4], new_K[4] = (fx, fy, cx, cy), dist[6] = (k1, k2, k3, k4, p1, p2): HOST arrays, read during the call and
+ *          passed to the kernel by value
+ *   image  [height,width,channels] uint8, channels 3 or 4 -> out_image, same shape: bilinear at (u - 0.5, v - 0.5),
+ *          taps outside the source read 0, floor(value + 0.5); alpha is interpolated like any channel
+ *   depth  [height,width] uint16 or, with depth_is_f32, float32 -> out_depth, same type: the nearest tap
+ *          (floor(u), floor(v)), 0 outside the source; both NULL: no depth plane
+ *   mask   [height,width] bytes -> out_mask, 0 / 1 bytes: (nearest tap != 0), 0 outside; both NULL: no mask
+ *   out_coords [height,width,2] float32 = (u, v), or NULL (for tests and diagnosis)
+ * Outputs must not alias inputs.  Refused on the host: channels not 3 or 4, a frame smaller than 2 x 2 or larger than
+ * qed_ingest_ground_truth's limit, an unknown model, coefficients the model does not have, non-positive focal lengths,
+ * NULL buffers.  No allocation, no sync, nothing is read back. */
+int qed_undistort_frame(int32_t height, int32_t width, const uint8_t* image, int32_t channels, const void* depth,
+                        int32_t depth_is_f32, const uint8_t* mask, const float* src_K, const float* new_K,
+                        const float* dist, int32_t model, uint8_t* out_image, void* out_depth, uint8_t* out_mask,
+                        float* out_coords, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

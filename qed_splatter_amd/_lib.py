@@ -102,6 +102,7 @@ SIGNATURES = {
     "qed_mcmc_noise": (C.c_int, [_I, _P, _P, _P, _P, _P, _F, _P, _F, _L, _P, _Q, _P, _P]),
     "qed_mcmc_reg": (C.c_int, [_I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
     "qed_ingest_ground_truth": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "qed_undistort_frame": (C.c_int, [_I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
 }
 
 class Post(C.Structure):

@@ -12,10 +12,17 @@ other reader -- ``get_metrics_dict``, ``get_loss_dict`` on a batch that does not
 indexes the batch, and ``batch["depth_image"]`` (and ``.get``) hand out a float32 view in metres, made on first use
 and kept for the life of the batch object (one step): ``uint16.float() * depth_scale``, which is also, bit for bit,
 what the kernel computes at full resolution.  ``items()`` / ``values()`` show the stored tensors.
+
+Distorted cameras (``DataparserConfig.undistort``).  A frame with non-zero coefficients or the fisheye model is
+resampled to the dataparser's new pinhole once, by ``undistort_frame`` (csrc/undistort.hip, one launch over all of its
+planes on the compute device), before it enters the cache; a ``device="cpu"`` cache gets the result copied back.  The
+cached planes keep their dtypes (uint16 depth stays uint16).  Frames without distortion take the path they always
+took.  There is no CPU implementation: without a GPU a distorted frame raises ``QedSplatError``.
 """
 from __future__ import annotations
 
 import copy
+import ctypes
 from pathlib import Path
 from typing import Iterator, List, Optional, Tuple
 
@@ -27,6 +34,7 @@ from . import _lib as L
 from .dataparser import DataparserConfig, DataparserOutputs, parse_dataset
 from .init_pointcloud import load_color_u8, load_depth
 from .model import PinholeCameras
+from .undistort import is_distorted, model_code
 
 
 class GpuBatch(dict):
@@ -88,6 +96,34 @@ def ingest_ground_truth(image: Tensor, depth: Tensor, mask: Optional[Tensor], ba
         int(depth is not None and depth.dtype == torch.float32), float(depth_scale), L.ptr(mask), L.ptr(bg), L.ptr(gt_rgb),
         L.ptr(gt_depth), L.ptr(gt_mask), L.current_stream()), "qed_ingest_ground_truth")
     return gt_rgb, gt_depth, gt_mask
+
+
+def undistort_frame(image: Tensor, depth: Optional[Tensor], mask: Optional[Tensor], src_K, new_K, dist, model,
+                    return_coords: bool = False):
+    """(image, depth, mask) of a distorted frame resampled to the pinhole ``new_K``, in one launch (qed_undistort_frame,
+    csrc/undistort.hip; the map is defined in undistort.py).  ``image`` [H,W,3|4] uint8: bilinear with zeros outside the
+    source, rounded half up; ``depth`` [H,W(,1)] uint16 or float32 and ``mask`` [H,W(,1)] bool, or None: the nearest tap,
+    0 / False outside.  ``src_K`` / ``new_K`` = (fx, fy, cx, cy) and ``dist`` = (k1, k2, k3, k4, p1, p2) are host values,
+    rounded to float32; ``model`` is the camera_model string.  Contiguous tensors on one GPU, launched on the current
+    stream of the current device; shapes and dtypes are kept.  ``return_coords``: a fourth result, the source position
+    (u, v) of every output pixel [H,W,2] float32."""
+    dev = image.device
+    if not (image.is_cuda and image.is_contiguous() and image.dim() == 3 and image.dtype == torch.uint8):
+        raise ValueError("image: a contiguous uint8 [H,W,C] tensor on the GPU")
+    h, w, ch = image.shape
+    for name, t, dtypes in (("depth", depth, (torch.uint16, torch.float32)), ("mask", mask, (torch.bool,))):
+        if t is not None and not (t.device == dev and t.is_contiguous() and t.dtype in dtypes and t.numel() == h * w):
+            raise ValueError(f"{name}: a contiguous tensor of {h * w} values on {dev}, one of {dtypes}")
+    arrays = [(ctypes.c_float * n)(*(float(v) for v in vals)) for n, vals in ((4, src_K), (4, new_K), (6, dist))]
+    out_image = torch.empty_like(image)
+    out_depth = torch.empty_like(depth) if depth is not None else None
+    out_mask = torch.empty_like(mask) if mask is not None else None
+    coords = torch.empty(h, w, 2, dtype=torch.float32, device=dev) if return_coords else None
+    L.check(L.load().qed_undistort_frame(
+        h, w, L.ptr(image), ch, L.ptr(depth), int(depth is not None and depth.dtype == torch.float32), L.ptr(mask),
+        *arrays, model_code(model), L.ptr(out_image), L.ptr(out_depth), L.ptr(out_mask), L.ptr(coords),
+        L.current_stream()), "qed_undistort_frame")
+    return (out_image, out_depth, out_mask, coords) if return_coords else (out_image, out_depth, out_mask)
 
 
 def _load_image(path: Path) -> np.ndarray:
@@ -168,6 +204,8 @@ class FullImageDatamanager:
                     raise ValueError(f"{out.mask_filenames[k]}: mask is {mask.shape[1]}x{mask.shape[0]}, its image is "
                                      f"{img.shape[1]}x{img.shape[0]} (resizing is not offered)")
                 frame["mask"] = torch.from_numpy(np.ascontiguousarray(mask))[..., None]
+            if out.distortion_params is not None and is_distorted(out.distortion_params[k], out.camera_models[k]):
+                self._undistort(frame, k)
             for key in ("image", "depth_image", "mask"):
                 if key in frame:
                     t = frame[key].to(self.device)
@@ -181,6 +219,20 @@ class FullImageDatamanager:
         c2w = out.camera_to_worlds.to(self.compute_device)
         self._train_cameras = [self._camera(c2w, k, j) for j, k in enumerate(self.i_train)]
         self._eval_cameras = [self._camera(c2w, k, j) for j, k in enumerate(self.i_eval)]
+
+    def _undistort(self, frame: dict, k: int) -> None:
+        """The planes of frame ``k``, as loaded, replaced by their resampling to the dataparser's new pinhole."""
+        o = self.outputs
+        if self.compute_device.type != "cuda":
+            raise L.QedSplatError(f"{o.image_filenames[k]}: a distorted frame is undistorted on the GPU and there is none "
+                                  "(there is no CPU path)")
+        planes = [frame[key].to(self.compute_device) if key in frame else None for key in ("image", "depth_image", "mask")]
+        with torch.cuda.device(self.compute_device):
+            planes = undistort_frame(*planes, o.src_intrinsics[k], (o.fx[k], o.fy[k], o.cx[k], o.cy[k]),
+                                     o.distortion_params[k], o.camera_models[k])
+        for key, t in zip(("image", "depth_image", "mask"), planes):
+            if t is not None:
+                frame[key] = t
 
     def _camera(self, c2w: Tensor, k: int, idx: int) -> PinholeCameras:
         o = self.outputs

@@ -6,8 +6,17 @@ Nerfstudio is not a dependency of this package and is not installed where this w
 RESTATED FROM MEMORY of nerfstudio 1.1.x, not checked against it.  Each is written out in the docstring of the function
 that implements it, and tests/test_dataparser_cpu.py pins the stated properties.
 
-Not offered: distorted or fisheye cameras (there is no undistortion here: such a dataset is refused), the other
-orientation / centre methods, the other split modes.
+Distorted cameras.  By default a file or frame with non-zero ``k1 k2 k3 k4 p1 p2``, or with ``camera_model:
+OPENCV_FISHEYE``, is refused.  With ``DataparserConfig.undistort`` such cameras are accepted: ``fx fy cx cy`` then hold
+the NEW pinhole ``K'`` (``undistort.optimal_new_intrinsics`` of the file's values; the distortion model, ``K'`` and the
+resampling are defined in undistort.py), ``src_intrinsics`` / ``distortion_params`` / ``camera_models`` keep the file's,
+and the datamanager resamples every such frame on the GPU before it enters the cache (csrc/undistort.hip).  The output
+has the size of the input.  Two deviations from nerfstudio, which only crops the depth map (leaving it distorted) and
+blends masks before testing non-zero: here depth and mask are resampled with the nearest tap through the same map as
+the colour, so that a depth value supervises the pixel it belongs to.
+
+Not offered: the other camera models, ``k4`` with OPENCV, tangential coefficients with the fisheye, resizing of depth
+images, the other orientation / centre methods, the other split modes.
 """
 from __future__ import annotations
 
@@ -21,8 +30,9 @@ import torch
 from torch import Tensor
 
 from .init_pointcloud import frame_intrinsics, load_transforms
+from .undistort import (DISTORTION_KEYS, check_coefficients, distort_points, is_distorted,  # noqa: F401 (public here too)
+                        optimal_new_intrinsics, undistort_points)
 
-DISTORTION_KEYS = ("k1", "k2", "k3", "k4", "p1", "p2")
 CAMERA_MODELS = (None, "OPENCV", "PINHOLE")
 
 
@@ -36,6 +46,7 @@ class DataparserConfig:
     scale_factor: float = 1.0
     train_split_fraction: float = 0.9
     depth_unit_scale_factor: float = 0.001   # integer depth files are in millimetres
+    undistort: bool = False                  # accept distorted OPENCV / OPENCV_FISHEYE cameras (see the module docstring)
 
 
 @dataclass
@@ -63,6 +74,11 @@ class DataparserOutputs:
     # applied_transform only matters for mapping results back to the ORIGINAL coordinates; nothing here does that.)
     ply_file_path: Optional[Path] = None
     config: DataparserConfig = field(default_factory=DataparserConfig)
+    # With ``undistort``: the file's (fx, fy, cx, cy) [n,4] and (k1, k2, k3, k4, p1, p2) [n,6] and camera_model of every
+    # frame, while fx fy cx cy above are the new pinhole's.  None without ``undistort``.
+    src_intrinsics: Optional[np.ndarray] = None
+    distortion_params: Optional[np.ndarray] = None
+    camera_models: Optional[List[Optional[str]]] = None
 
     def __len__(self) -> int:
         return len(self.image_filenames)
@@ -125,6 +141,15 @@ def _check_undistorted(meta: dict, where: str) -> None:
                                   "(undistort the images first)")
 
 
+def _frame_distortion(contents: dict, frame: dict, where: str):
+    """(coefficients in DISTORTION_KEYS order, camera_model): the frame's values win over the file's, as for the
+    intrinsics.  Refuses what undistort.py does not define."""
+    model = frame.get("camera_model", contents.get("camera_model"))
+    dist = tuple(float(frame.get(k, contents.get(k, 0.0))) for k in DISTORTION_KEYS)
+    check_coefficients(dist, model, where)
+    return dist, model
+
+
 def _frame_size(contents: dict, frame: dict, image_path: Path):
     """(w, h): the frame's values win over the file's; a dataset that stores neither has its image header read."""
     w = frame.get("w", contents.get("w"))
@@ -140,11 +165,13 @@ def parse_dataset(data_dir, config: Optional[DataparserConfig] = None, verbose: 
     """Reads ``data_dir/transforms.json``.  Frames are sorted by ``file_path``; frames without ``depth_file_path`` are
     skipped (their number is reported); ``mask_path`` is optional.  Intrinsics and sizes are the frame's, else the
     file's.  Poses go through ``orient_and_center`` and are then scaled by ``scale_factor / max |origin coordinate|``
-    (``auto_scale_poses``) or by ``scale_factor``."""
+    (``auto_scale_poses``) or by ``scale_factor``.  With ``config.undistort`` the intrinsics of a distorted frame are
+    replaced by ``optimal_new_intrinsics`` of the frame's own (see the module docstring)."""
     cfg = config or DataparserConfig()
     data_dir = Path(data_dir)
     contents = load_transforms(data_dir)
-    _check_undistorted(contents, "transforms.json")
+    if not cfg.undistort:
+        _check_undistorted(contents, "transforms.json")
     frames = sorted(contents["frames"], key=lambda f: f["file_path"])
     with_depth = [f for f in frames if "depth_file_path" in f]
     n_skipped = len(frames) - len(with_depth)
@@ -153,14 +180,26 @@ def parse_dataset(data_dir, config: Optional[DataparserConfig] = None, verbose: 
     if not with_depth:
         raise ValueError(f"{data_dir}: no frame of transforms.json has a depth_file_path")
     images, depths, masks, poses, intr, sizes = [], [], [], [], [], []
+    src_intr, dists, models, new_K = [], [], [], {}
     for f in with_depth:
-        _check_undistorted(f, f"frame {f['file_path']}")
+        if not cfg.undistort:
+            _check_undistorted(f, f"frame {f['file_path']}")
         images.append(data_dir / f["file_path"])
         depths.append(data_dir / f["depth_file_path"])
         masks.append(data_dir / f["mask_path"] if "mask_path" in f else None)
         poses.append(np.asarray(f["transform_matrix"], dtype=np.float64))
         intr.append(frame_intrinsics(contents, f))
         sizes.append(_frame_size(contents, f, images[-1]))
+        if cfg.undistort:
+            dist, model = _frame_distortion(contents, f, f"frame {f['file_path']}")
+            src_intr.append(intr[-1])
+            dists.append(dist)
+            models.append(model)
+            if is_distorted(dist, model):
+                key = (intr[-1], dist, model, sizes[-1])                 # K' is computed once per distinct camera
+                if key not in new_K:
+                    new_K[key] = optimal_new_intrinsics(intr[-1], dist, model, *sizes[-1])
+                intr[-1] = new_K[key]
     c2w = np.stack([p[:3] for p in poses])                                     # [n,3,4]
     c2w, transform = orient_and_center(c2w, cfg.orientation_method, cfg.center_method)
     scale = float(cfg.scale_factor)
@@ -177,4 +216,7 @@ def parse_dataset(data_dir, config: Optional[DataparserConfig] = None, verbose: 
         camera_to_worlds=torch.from_numpy(c2w).to(torch.float32), fx=intr[:, 0], fy=intr[:, 1], cx=intr[:, 2],
         cy=intr[:, 3], widths=sizes[:, 0], heights=sizes[:, 1], i_train=i_train, i_eval=i_eval,
         dataparser_transform=transform_t, dataparser_scale=scale, depth_unit_scale_factor=float(cfg.depth_unit_scale_factor),
-        n_skipped=n_skipped, ply_file_path=ply, config=cfg)
+        n_skipped=n_skipped, ply_file_path=ply, config=cfg,
+        src_intrinsics=np.asarray(src_intr, dtype=np.float64) if cfg.undistort else None,
+        distortion_params=np.asarray(dists, dtype=np.float64) if cfg.undistort else None,
+        camera_models=models if cfg.undistort else None)

@@ -5,7 +5,8 @@
 The dataset is read by ``dataparser.parse_dataset``, cached by ``datamanager.FullImageDatamanager`` (uint8 images on
 the GPU), and every step takes the next training camera and its frame through the eager fused route: ``fused_loss``
 (which makes the step's ground truth in one launch, csrc/ingest.hip) -> ``backward_fused`` -> ``FlatAdam.step`` ->
-``Densifier``.  The captured hipGraph step (graph.py) is not used: it replays ONE camera and ONE ground truth.
+``Densifier``.  ``--undistort`` accepts datasets whose cameras carry OPENCV or OPENCV_FISHEYE distortion: their frames are
+resampled to a pinhole on the GPU while the cache is filled (dataparser.py, csrc/undistort.hip).  The captured hipGraph step (graph.py) is not used: it replays ONE camera and ONE ground truth.
 
 The Gaussians are seeded from the dataset's ``ply_file_path`` (``--init-from-ply`` overrides it) in the frame of the
 cameras, or from random points when there is none.  Every ``--eval-every`` steps and at the end the evaluation split
@@ -132,6 +133,8 @@ def main(argv=None) -> Dict:
     ap.add_argument("--resolution-schedule", type=int, default=3000, help="steps per halving")
     ap.add_argument("--background-color", choices=("random", "black", "white"), default="random")
     ap.add_argument("--sh-degree", type=int, default=3)
+    ap.add_argument("--undistort", action="store_true",
+                    help="accept OPENCV / OPENCV_FISHEYE distortion: undistort the frames on the GPU while caching them")
     ap.add_argument("--cache-device", default=None, help="'cpu' keeps the image cache in pinned host memory")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -141,7 +144,8 @@ def main(argv=None) -> Dict:
     dp_cfg = DataparserConfig(orientation_method=a.orientation_method, center_method=a.center_method,
                               auto_scale_poses=a.auto_scale_poses == "True",
                               depth_unit_scale_factor=a.depth_unit_scale_factor,
-                              train_split_fraction=a.train_split_fraction, scale_factor=a.scale_factor)
+                              train_split_fraction=a.train_split_fraction, scale_factor=a.scale_factor,
+                              undistort=a.undistort)
     dm = FullImageDatamanager(a.data, dp_cfg, device=a.cache_device, seed=a.seed)
     config = QEDSplatterModelConfig(num_downscales=a.num_downscales, resolution_schedule=a.resolution_schedule,
                                     background_color=a.background_color, sh_degree=a.sh_degree)
