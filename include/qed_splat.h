@@ -810,6 +810,38 @@ int qed_undistort_frame(int32_t height, int32_t width, const uint8_t* image, int
                         const float* dist, int32_t model, uint8_t* out_image, void* out_depth, uint8_t* out_mask,
                         float* out_coords, void* stream);
 
+/* ---- trained Gaussians to and from the rows of a 3DGS PLY file (csrc/export.hip) -------------------------------------
+ * The file format is stated in qed_splatter_amd/gaussian_ply.py.  A row of color_mode 0 (sh_coeffs) is 17 + 3 K floats,
+ * K = (sh_degree + 1)^2 - 1:  x y z  nx ny nz (zeros)  f_dc[3]  f_rest[3 K] (channel-major: features_rest[N,K,3]
+ * transposed)  opacity (logit)  scale[3] (log)  rot[4] (wxyz, as stored).  A row of color_mode 1 (rgb) is 59 bytes: the
+ * three colour bytes clamp(SH_C0 f_dc + 0.5, 0, 1) * 255 truncated (sh_degree 0: the sigmoid of f_dc) stand where f_dc
+ * and f_rest stood, and features_rest is not read.
+ * qed_pack_gaussians drops a row if one of its values (rgb mode: f_dc instead of the bytes) is not finite, else if its
+ * opacity is below -5.5373f = logit(1 / 255); the rows kept are written to `rows` in input order without gaps.
+ *   counts[3] (device): rows written, dropped as non-finite, dropped as transparent
+ *   rows      16-byte aligned, room for N rows; bytes behind the last kept row are not written
+ *   workspace qed_pack_workspace_bytes(N)
+ * Three launches (count, scan of the per-workgroup counts, pack): a row's position does not depend on scheduling.
+ * qed_unpack_gaussians reads N rows of row_bytes bytes each: h_offsets[14 + 3 K] (HOST) holds the byte offset inside a
+ * row of every float32 column, in the order means[3] scales[3] quats[4] opacity f_dc[3] features_rest[K][3] -- the
+ * caller finds the columns by name, so a file may order them freely and carry others.  At least 4 readable bytes behind
+ * every offset; no alignment is asked of rows, row_bytes or the offsets.
+ * Both take an optional similarity p' = s (R p + t): h_similarity[17] (HOST doubles) = R (row-major), t, s, the
+ * quaternion of R (wxyz), and h_sh[83] = the band matrices of R, 3 x 3, 5 x 5 and 7 x 7 row-major, for which
+ * c'_band = D_band c_band.  Means go through the map, log-scales get + log s, quaternions are left-multiplied, the
+ * coefficients of bands 1-3 are multiplied per channel; each new value is accumulated in float64 and rounded once.
+ * Both NULL: every value is moved bit for bit.  (pack classifies the values AFTER the map.)
+ * Refused on the host: N < 1, sh_degree outside 0..3, NULL buffers, a scale that is not positive and finite, an offset
+ * outside the row.  No allocation, no sync, nothing is read back. */
+int64_t qed_pack_workspace_bytes(int64_t N);
+int qed_pack_gaussians(int32_t N, int32_t sh_degree, int32_t color_mode, const float* means, const float* scales,
+                       const float* quats, const float* opacities, const float* features_dc, const float* features_rest,
+                       const double* h_similarity, const double* h_sh, uint8_t* rows, int32_t* counts, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int qed_unpack_gaussians(int32_t N, int32_t sh_degree, const uint8_t* rows, int64_t row_bytes, const int32_t* h_offsets,
+                         const double* h_similarity, const double* h_sh, float* means, float* scales, float* quats,
+                         float* opacities, float* features_dc, float* features_rest, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

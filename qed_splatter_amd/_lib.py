@@ -103,6 +103,9 @@ SIGNATURES = {
     "qed_mcmc_reg": (C.c_int, [_I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
     "qed_ingest_ground_truth": (C.c_int, [_I, _I, _I, _P, _I, _I, _P, _I, _F, _P, _P, _P, _P, _P, _P]),
     "qed_undistort_frame": (C.c_int, [_I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "qed_pack_workspace_bytes": (_L, [_L]),
+    "qed_pack_gaussians": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "qed_unpack_gaussians": (C.c_int, [_I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 class Post(C.Structure):

@@ -354,35 +354,42 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "double": "f8", "float64": "f8"}
 
 
+def _read_ply_header(f, path, what: str = "point cloud"):
+    """``(format, n, [(name, numpy type)], vertex element seen)`` of the PLY open at ``f``, which is left at the first
+    byte of the body.  The vertex element must come first and have scalar properties only."""
+    if f.readline().strip() != b"ply":
+        raise RuntimeError(f"Failed to read {what}: {path}")
+    fmt, n, props, in_vertex, seen_vertex = None, 0, [], False, False
+    while True:
+        line = f.readline()
+        if not line:
+            raise RuntimeError(f"Failed to read {what} (no end_header): {path}")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            in_vertex = tok[1] == "vertex" and not seen_vertex
+            if in_vertex:
+                n, seen_vertex = int(tok[2]), True
+            elif not seen_vertex:
+                raise RuntimeError(f"unsupported PLY (an element before 'vertex'): {path}")
+        elif tok[0] == "property" and in_vertex:
+            if tok[1] == "list":
+                raise RuntimeError(f"unsupported PLY (list property on vertices): {path}")
+            props.append((tok[2], _PLY_TYPES[tok[1]]))
+        elif tok[0] == "end_header":
+            break
+    return fmt, n, props, seen_vertex
+
+
 def _read_ply_vertex(path, optional=()):
     """``(n, {name: column})`` of a PLY's vertex element: ``x y z`` and, when the file has all of them, the properties
     named in ``optional``, each in its stored type.  ASCII and binary little-endian; the vertex element must come first
     and have scalar properties only."""
     with open(path, "rb") as f:
-        if f.readline().strip() != b"ply":
-            raise RuntimeError(f"Failed to read point cloud: {path}")
-        fmt, n, props, in_vertex, seen_vertex = None, 0, [], False, False
-        while True:
-            line = f.readline()
-            if not line:
-                raise RuntimeError(f"Failed to read point cloud (no end_header): {path}")
-            tok = line.decode("ascii", "replace").split()
-            if not tok or tok[0] in ("comment", "obj_info"):
-                continue
-            if tok[0] == "format":
-                fmt = tok[1]
-            elif tok[0] == "element":
-                in_vertex = tok[1] == "vertex" and not seen_vertex
-                if in_vertex:
-                    n, seen_vertex = int(tok[2]), True
-                elif not seen_vertex:
-                    raise RuntimeError(f"unsupported PLY (an element before 'vertex'): {path}")
-            elif tok[0] == "property" and in_vertex:
-                if tok[1] == "list":
-                    raise RuntimeError(f"unsupported PLY (list property on vertices): {path}")
-                props.append((tok[2], _PLY_TYPES[tok[1]]))
-            elif tok[0] == "end_header":
-                break
+        fmt, n, props, seen_vertex = _read_ply_header(f, path)
         names = [p[0] for p in props]
         if not seen_vertex or not all(k in names for k in "xyz"):
             raise RuntimeError(f"Failed to read point cloud (no x y z): {path}")

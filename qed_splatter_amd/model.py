@@ -412,6 +412,22 @@ class QEDSplatterModel(nn.Module):
             return cls.from_seed_points(config, None, None, **kw)
         return cls.from_seed_points(config, loaded["points3D_xyz"], loaded["points3D_rgb"], **kw)
 
+    @classmethod
+    def from_gaussian_ply(cls, config: Optional[QEDSplatterModelConfig], path, transform_matrix=None,
+                          scale_factor: float = 1.0, device=None, **model_kw) -> "QEDSplatterModel":
+        """The model of a 3DGS PLY file (gaussian_ply.py: this package's export, ``ns-export gaussian-splat``, another
+        trainer's ``point_cloud.ply``), unpacked on the GPU.  ``transform_matrix`` [3,4] / ``scale_factor``: the
+        dataparser's, for a file in the dataset's frame (means, log-scales, quaternions and SH coefficients follow).
+        The SH degree is the file's (its number of ``f_rest_*`` columns) and replaces ``config.sh_degree``; a file
+        exported with ``color_mode="rgb"`` is refused."""
+        import dataclasses
+        from . import gaussian_ply as G
+        g = G.load_gaussians(path, transform_matrix, scale_factor, device)
+        config = config or QEDSplatterModelConfig()
+        if config.sh_degree != g["sh_degree"]:
+            config = dataclasses.replace(config, sh_degree=g["sh_degree"])
+        return cls(config, **{n: g[n] for n in GROUP_ORDER}, flat=g["flat"], **model_kw)
+
     def _make_param(self, name: str, view: Tensor) -> nn.Parameter:
         """A leaf view of the flat buffer; the two SH groups can hold their gradient in compact form (lazy_sh_grad)."""
         if name not in ("features_dc", "features_rest"):

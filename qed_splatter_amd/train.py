@@ -1,6 +1,7 @@
 """Train on a dataset directory -- what ``ns-train qed-splatter --data PATH`` does in the reference, on one GPU:
 
     python -m qed_splatter_amd.train --data DIR --steps 30000 [--save ckpt.pt] [--resume ckpt.pt]
+                                     [--export-ply splat.ply [--export-frame dataset]]
 
 The dataset is read by ``dataparser.parse_dataset``, cached by ``datamanager.FullImageDatamanager`` (uint8 images on
 the GPU), and every step takes the next training camera and its frame through the eager fused route: ``fused_loss``
@@ -87,12 +88,25 @@ class Trainer:
         return out
 
     def save(self, path) -> None:
+        """The six tensors, the step, the optimiser state -- and the dataparser's transform and scale and the SH degree,
+        so that ``python -m qed_splatter_amd.gaussian_ply export --frame dataset`` works from the file alone."""
+        out = self.datamanager.outputs
         torch.save({"params": {n: self.model.gauss_params[n].detach().clone() for n in GROUP_ORDER}, "step": self.step,
-                    "optimizer": self.optimizer.state_dict()}, path)
+                    "optimizer": self.optimizer.state_dict(),
+                    "dataparser_transform": out.dataparser_transform.detach().cpu().clone(),
+                    "dataparser_scale": float(out.dataparser_scale), "sh_degree": int(self.model.config.sh_degree)}, path)
+
+    def export_ply(self, path, frame: str = "model", color_mode: str = "sh_coeffs") -> Dict[str, int]:
+        """The Gaussians as a 3DGS PLY file (gaussian_ply.py), in the model's frame or the dataset's."""
+        from .gaussian_ply import export_gaussian_ply
+        out = self.datamanager.outputs
+        return export_gaussian_ply(self.model, path, frame=frame, dataparser_transform=out.dataparser_transform,
+                                   dataparser_scale=out.dataparser_scale, color_mode=color_mode)
 
     def resume(self, path) -> None:
-        """The six tensors, the step and the optimiser state of ``save``: the model is rebuilt around the loaded
-        Gaussians (their number may differ from the seeded model's) with this trainer's configuration."""
+        """The six tensors, the step and the optimiser state of ``save`` (its other keys are for the exporter and are not
+        read): the model is rebuilt around the loaded Gaussians (their number may differ from the seeded model's) with
+        this trainer's configuration."""
         ckpt = torch.load(path, map_location=self.model.device, weights_only=False)
         self.model = QEDSplatterModel(self.model.config, **{n: ckpt["params"][n] for n in GROUP_ORDER})
         self._bind_optimizer()
@@ -135,6 +149,10 @@ def main(argv=None) -> Dict:
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--undistort", action="store_true",
                     help="accept OPENCV / OPENCV_FISHEYE distortion: undistort the frames on the GPU while caching them")
+    ap.add_argument("--export-ply", metavar="PATH", default=None,
+                    help="after the last evaluation, write the Gaussians as a 3DGS PLY file (gaussian_ply.py)")
+    ap.add_argument("--export-frame", choices=("model", "dataset"), default="model",
+                    help="'dataset': undo the dataparser's orientation, centring and scale in the exported file")
     ap.add_argument("--cache-device", default=None, help="'cpu' keeps the image cache in pinned host memory")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -170,6 +188,10 @@ def main(argv=None) -> Dict:
     print(f"step {trainer.step}: " + ", ".join(f"{k} {v:.5g}" for k, v in metrics.items()), flush=True)
     if a.save:
         trainer.save(a.save)
+    if a.export_ply:
+        res = trainer.export_ply(a.export_ply, a.export_frame)
+        print(f"exported {res['written']} Gaussians to {a.export_ply} ({a.export_frame} frame; dropped "
+              f"{res['dropped_nonfinite']} non-finite, {res['dropped_low_opacity']} below opacity 1/255)")
     done = trainer.step - first
     result = {"steps": trainer.step, "steps_per_s": done / elapsed if elapsed > 0 and done else 0.0,
               "eval": metrics, "gaussian_count": trainer.model.num_points}
