@@ -66,7 +66,9 @@ extern "C" {
  *   2  round 4: qed_composite_fwd / qed_composite_bwd gained `t_final` in the middle of their argument lists; the row of
  *      the compact data-parallel message grew from 3 N + 16 to 3 N + 20 floats (still reported as 1 by that round's
  *      library).  A caller built against another version must not call further: the pointers would be shifted.
- *   3  round 5: qed_composite_fwd gained `tile_order` behind `tile_cost`. */
+ *   3  round 5: qed_composite_fwd gained `tile_order` behind `tile_cost`.
+ * New entry points change nothing a caller of version 3 relies on and keep the number (the latest: qed_present_range,
+ * qed_present_frame). */
 #define QED_ABI_VERSION 3
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
@@ -841,6 +843,42 @@ int qed_pack_gaussians(int32_t N, int32_t sh_degree, int32_t color_mode, const f
 int qed_unpack_gaussians(int32_t N, int32_t sh_degree, const uint8_t* rows, int64_t row_bytes, const int32_t* h_offsets,
                          const double* h_similarity, const double* h_sh, float* means, float* scales, float* quats,
                          float* opacities, float* features_dc, float* features_rest, void* stream);
+
+/* ---- a rendered frame finished for image files (csrc/present.hip) --------------------------------------------------
+ * get_outputs' float planes of one frame -- rgb [height,width,3], depth [height,width], alpha [height,width] (the
+ * accumulation) -- turned into the integer planes an image writer stores.  A pixel is VALID when alpha > 0 and its depth
+ * is finite and > 0.  clamp(x, 0, 1) = fminf(fmaxf(x, 0), 1), which sends NaN to 0; fmaf is ONE rounding.
+ *
+ * qed_present_range writes (min, max) of the depth over the valid pixels into range_out (device float[2]); (0, 0) if no
+ * pixel is valid.  It zeroes range_out itself (a memset on `stream`) and combines the workgroups of its one launch through
+ * integer atomics on the bit patterns of the positive floats: the result does not depend on the order.
+ *
+ * qed_present_frame writes, in one launch, every plane whose pointer is not NULL:
+ *   out_rgb8 [height,width,3]      floor(fmaf(clamp(x, 0, 1), 255, 0.5)).  NaN gives 0.
+ *   out_alpha8 [height,width]      the same rule on alpha.
+ *   out_depth16 [height,width]     uint16, little-endian.  0 where alpha <= 0 or the depth is not finite or <= 0 (0 is the
+ *                                  dataset's "no measurement", as qed_ingest_ground_truth's readers take it); otherwise
+ *                                  min(65535, floor(fmaf(depth, inv_depth_unit, 0.5))).  inv_depth_unit is a float32 the
+ *                                  host computes in float64 as 1 / (dataparser_scale * depth_unit_scale_factor).
+ *   out_depthmap8 [height,width,3] t = clamp((depth - lo) * inv_span, 0, 1), where (lo, hi) = range_dev[0], range_dev[1]
+ *                                  if range_dev (device float[2], qed_present_range's result, never read back) is not
+ *                                  NULL, else the host's near, far; inv_span = 1 / (hi - lo) in float32, or 0 when
+ *                                  hi <= lo.  k = min(255, (int)(t * 255)) (truncation, as Nerfstudio's
+ *                                  apply_depth_colormap indexes its table).  c = fmaf(alpha_c, lut[k][ch] - 255, 255)
+ *                                  with alpha_c = clamp(alpha, 0, 1): the colour over white by accumulation.  The stored
+ *                                  byte is floor(c + 0.5f).  Pixels that are not valid are white.
+ *   lut                            device uint8[256][3], any alignment.
+ * The fast path (a lane owns four consecutive pixels, every store is a whole dword) needs rgb, depth and alpha 16-byte
+ * aligned and the outputs dword-aligned; any other alignment takes a per-pixel path with the same results.
+ * Refused on the host: an empty or too large frame, NULL alpha, no output at all, an output whose input is NULL
+ * (out_rgb8: rgb; out_depth16: depth; out_depthmap8: depth and lut), an inv_depth_unit that is not positive and finite
+ * when out_depth16 is asked for, NaN near / far when they are read, misaligned element pointers.  No allocation, no sync,
+ * nothing is read back. */
+int qed_present_range(int32_t height, int32_t width, const float* depth, const float* alpha, float* range_out,
+                      void* stream);
+int qed_present_frame(int32_t height, int32_t width, const float* rgb, const float* depth, const float* alpha,
+                      float inv_depth_unit, const float* range_dev, float near, float far, const uint8_t* lut,
+                      uint8_t* out_rgb8, uint16_t* out_depth16, uint8_t* out_depthmap8, uint8_t* out_alpha8, void* stream);
 
 #ifdef __cplusplus
 }

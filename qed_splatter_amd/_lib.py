@@ -106,6 +106,8 @@ SIGNATURES = {
     "qed_pack_workspace_bytes": (_L, [_L]),
     "qed_pack_gaussians": (C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "qed_unpack_gaussians": (C.c_int, [_I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qed_present_range": (C.c_int, [_I, _I, _P, _P, _P, _P]),
+    "qed_present_frame": (C.c_int, [_I, _I, _P, _P, _P, _F, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
 }
 
 class Post(C.Structure):

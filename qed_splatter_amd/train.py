@@ -1,7 +1,7 @@
 """Train on a dataset directory -- what ``ns-train qed-splatter --data PATH`` does in the reference, on one GPU:
 
     python -m qed_splatter_amd.train --data DIR --steps 30000 [--save ckpt.pt] [--resume ckpt.pt]
-                                     [--export-ply splat.ply [--export-frame dataset]]
+                                     [--export-ply splat.ply [--export-frame dataset]] [--render-eval DIR]
 
 The dataset is read by ``dataparser.parse_dataset``, cached by ``datamanager.FullImageDatamanager`` (uint8 images on
 the GPU), and every step takes the next training camera and its frame through the eager fused route: ``fused_loss``
@@ -154,6 +154,9 @@ def main(argv=None) -> Dict:
     ap.add_argument("--export-frame", choices=("model", "dataset"), default="model",
                     help="'dataset': undo the dataparser's orientation, centring and scale in the exported file")
     ap.add_argument("--cache-device", default=None, help="'cpu' keeps the image cache in pinned host memory")
+    ap.add_argument("--render-eval", metavar="DIR", default=None,
+                    help="after the last evaluation, write the evaluation views as PNG files (render.py: colour, 16-bit depth "
+                         "in the dataset's unit, colour-mapped depth, accumulation)")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("qed_splatter_amd.train needs a GPU")
@@ -195,6 +198,11 @@ def main(argv=None) -> Dict:
     done = trainer.step - first
     result = {"steps": trainer.step, "steps_per_s": done / elapsed if elapsed > 0 and done else 0.0,
               "eval": metrics, "gaussian_count": trainer.model.num_points}
+    if a.render_eval:
+        from .render import dataset_path, render_to_directory
+        unit = float(dm.outputs.dataparser_scale) * float(dm.outputs.depth_unit_scale_factor)
+        result["render_eval"] = render_to_directory(trainer.model, dataset_path(dm, "eval"), a.render_eval, depth_unit=unit)
+        print(f"rendered {result['render_eval']['frames']} evaluation views to {a.render_eval}")
     print(json.dumps(result))
     return result
 
