@@ -38,7 +38,7 @@ def build_lib(force: bool = False, verbose: bool = False, variant: str = "", ext
     obj_dir = PKG / "build" / variant if variant else PKG / "build"
     obj_dir.mkdir(exist_ok=True, parents=True)
     lib_path = LIB_DIR / f"libqed_splat_{variant}.so" if variant else LIB_PATH
-    headers = [CSRC / "qed_common.h", PKG.parent / "include" / "qed_splat.h"]
+    headers = [CSRC / "qed_common.h", CSRC / "qed_reduce.h", PKG.parent / "include" / "qed_splat.h"]
     objs = []
     procs = []
     for src in SOURCES:

@@ -352,24 +352,22 @@ bilagrid_tv_fwd_kernel(const float* __restrict__ g, TvArgs a, double* __restrict
             }
         }
     }
-    double s = (double)sx * a.wx + (double)sy * a.wy + (double)sl * a.wl;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    __shared__ double s_w[4];
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+    const double v[1] = {(double)sx * a.wx + (double)sy * a.wy + (double)sl * a.wl};
+    __shared__ double s_w[1][4];
+    __shared__ double s[1];
+    block_sum_d(v, s_w, s);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s[0];
 }
 
 // Fixed-order fold of the block partials (one workgroup).
 __global__ void __launch_bounds__(256)
 bilagrid_tv_fold_kernel(const double* __restrict__ partials, int n, float* __restrict__ out) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) s += partials[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
-    __shared__ double s_w[4];
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = (float)((s_w[0] + s_w[1]) + (s_w[2] + s_w[3]));
+    double v[1] = {0.0};
+    for (int i = threadIdx.x; i < n; i += 256) v[0] += partials[i];
+    __shared__ double s_w[1][4];
+    __shared__ double s[1];
+    block_sum_d(v, s_w, s);
+    if (threadIdx.x == 0) out[0] = (float)s[0];
 }
 
 __global__ void __launch_bounds__(256)

@@ -283,8 +283,7 @@ __global__ void __launch_bounds__(256) pack_scan_kernel(const int* __restrict__ 
         __syncthreads();
     }
     // the two drop counts: per-thread partials -> wave sums -> thread 0
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { bad += __shfl_xor(bad, o, 64); faint += __shfl_xor(faint, o, 64); }
+    bad = wave_sum_i(bad); faint = wave_sum_i(faint);
     if (lane == 0) { drop_tot[0][wid] = bad; drop_tot[1][wid] = faint; }
     __syncthreads();
     if (tid == 0) {

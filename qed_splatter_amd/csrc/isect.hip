@@ -129,8 +129,7 @@ isect_emit_kernel(int N, int C, const float* __restrict__ means2d, const int* __
                 }
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o, 64); all += __shfl_xor(all, o, 64); }
+        before = wave_sum_ll(before); all = wave_sum_ll(all);
         if (lane == 0) { s_scan[0][wid] = before; s_scan[1][wid] = all; }
         __syncthreads();
         before = s_scan[0][0] + s_scan[0][1] + s_scan[0][2] + s_scan[0][3];
@@ -341,8 +340,7 @@ count_sorted_kernel(int n_slots, const int* __restrict__ order, const int* __res
         }
     }
     __shared__ int wsum[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum_i(v);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) block_sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -768,8 +766,7 @@ bucket_partition_kernel(const unsigned* __restrict__ keys, const int* __restrict
         before = tid < b ? t : 0;
         if (tid == b) size = t;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o, 64); size += __shfl_xor(size, o, 64); }
+    before = wave_sum_i(before); size = wave_sum_i(size);
     if (wid < 4 && lane == 0) { s_wsum[wid][0] = before; s_wsum[wid][1] = size; }
     for (int i = tid; i < kPartWaves * 256; i += kPartThreads) (&s_cnt[0][0])[i] = 0;
     __syncthreads();

@@ -220,10 +220,11 @@ lpips_distance_kernel(const float* __restrict__ feat, const float* __restrict__ 
         }
         acc += wave_sum(d);
     }
-    __shared__ double s[4];
-    if (lane == 0) s[wave] = (double)acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    const double v[1] = {(double)acc};                        // already a wave's sum, the same in every lane
+    __shared__ double s_w[1][4];
+    __shared__ double s[1];
+    block_combine_d(v, s_w, s);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s[0];
 }
 
 struct LpipsFold {
@@ -236,18 +237,16 @@ __global__ void __launch_bounds__(256)
 lpips_finalize_kernel(LpipsFold f, const double* __restrict__ partials, float* __restrict__ out) {
     static_assert(kDistMaxGrid == 256, "one partial per thread");
     __shared__ double s_w[kLpipsLayers][4];
+    __shared__ double s[kLpipsLayers];
+    double v[kLpipsLayers];
 #pragma unroll
-    for (int l = 0; l < kLpipsLayers; ++l) {
-        double v = (int)threadIdx.x < f.n_blocks[l] ? partials[l * kDistMaxGrid + threadIdx.x] : 0.0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((threadIdx.x & 63) == 0) s_w[l][threadIdx.x >> 6] = v;
-    }
-    __syncthreads();
+    for (int l = 0; l < kLpipsLayers; ++l)
+        v[l] = (int)threadIdx.x < f.n_blocks[l] ? partials[l * kDistMaxGrid + threadIdx.x] : 0.0;
+    block_sum_d(v, s_w, s);
     if (threadIdx.x != 0) return;
     double total = 0.0;
     for (int l = 0; l < kLpipsLayers; ++l) {
-        const double term = (s_w[l][0] + s_w[l][1] + s_w[l][2] + s_w[l][3]) / (double)f.n_pix[l];
+        const double term = s[l] / (double)f.n_pix[l];
         out[1 + l] = (float)term;
         total += term;
     }

@@ -96,7 +96,7 @@ mcmc_weights_kernel(int N, const float* __restrict__ opac, float thresh, unsigne
         cdf[i] = w;
         counts[i] = 0;
     }
-    for (int o = 32; o > 0; o >>= 1) w += __shfl_xor(w, o, 64);
+    w = (unsigned long long)wave_sum_ll((long long)w);
     const unsigned long long dm = __ballot(dead);
     __shared__ unsigned long long s_w[4];
     __shared__ int s_d[4];
@@ -144,7 +144,7 @@ mcmc_scan_blocks_kernel(int nb, unsigned long long* __restrict__ block, const in
         if (tid == 0) s_base += tot;
         __syncthreads();
     }
-    for (int o = 32; o > 0; o >>= 1) dead += __shfl_xor(dead, o, 64);
+    dead = wave_sum_i(dead);
     if (lane == 0) s_dead[wave] = dead;
     __syncthreads();
     if (tid == 0) {
@@ -368,13 +368,13 @@ mcmc_reg_kernel(int N, const float* __restrict__ scales, const float* __restrict
                 float* __restrict__ g_scales, float* __restrict__ g_opac, double* __restrict__ partials) {
     const float co = g_opac ? a.co * (a.up_o ? a.up_o[0] : 1.f) : 0.f;
     const float cs = g_scales ? a.cs * (a.up_s ? a.up_s[0] : 1.f) : 0.f;
-    double so = 0.0, ss = 0.0;
+    double v[2] = {0.0, 0.0};                                 // sum of opacities, sum of scales
     for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
         const float sig = 1.f / (1.f + expf(-opac[i]));
         const float e0 = expf(scales[(size_t)3 * i]), e1 = expf(scales[(size_t)3 * i + 1]),
                     e2 = expf(scales[(size_t)3 * i + 2]);
-        so += (double)sig;
-        ss += (double)e0 + (double)e1 + (double)e2;
+        v[0] += (double)sig;
+        v[1] += (double)e0 + (double)e1 + (double)e2;
         if (g_opac) g_opac[i] += co * (sig * (1.f - sig));
         if (g_scales) {
             float* g = g_scales + (size_t)3 * i;
@@ -382,28 +382,22 @@ mcmc_reg_kernel(int N, const float* __restrict__ scales, const float* __restrict
         }
     }
     if (!partials) return;
-    for (int o = 32; o > 0; o >>= 1) { so += __shfl_down(so, o); ss += __shfl_down(ss, o); }
-    __shared__ double s_o[4], s_s[4];
-    if ((threadIdx.x & 63) == 0) { s_o[threadIdx.x >> 6] = so; s_s[threadIdx.x >> 6] = ss; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partials[2 * blockIdx.x] = (s_o[0] + s_o[1]) + (s_o[2] + s_o[3]);
-        partials[2 * blockIdx.x + 1] = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
-    }
+    __shared__ double s_w[2][4];
+    __shared__ double s[2];
+    block_sum_d(v, s_w, s);
+    if (threadIdx.x < 2) partials[2 * blockIdx.x + threadIdx.x] = s[threadIdx.x];
 }
 
 // fixed-order fold of the block partials (one workgroup): out = (reg_o, reg_s, reg_o + reg_s)
 __global__ void __launch_bounds__(256)
 mcmc_reg_fold_kernel(const double* __restrict__ partials, int nb, double wo, double ws, float* __restrict__ out) {
-    double so = 0.0, ss = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 256) { so += partials[2 * b]; ss += partials[2 * b + 1]; }
-    for (int o = 32; o > 0; o >>= 1) { so += __shfl_down(so, o); ss += __shfl_down(ss, o); }
-    __shared__ double s_o[4], s_s[4];
-    if ((threadIdx.x & 63) == 0) { s_o[threadIdx.x >> 6] = so; s_s[threadIdx.x >> 6] = ss; }
-    __syncthreads();
+    double v[2] = {0.0, 0.0};
+    for (int b = threadIdx.x; b < nb; b += 256) { v[0] += partials[2 * b]; v[1] += partials[2 * b + 1]; }
+    __shared__ double s_w[2][4];
+    __shared__ double s[2];
+    block_sum_d(v, s_w, s);
     if (threadIdx.x == 0) {
-        const float ro = (float)(wo * ((s_o[0] + s_o[1]) + (s_o[2] + s_o[3])));
-        const float rs = (float)(ws * ((s_s[0] + s_s[1]) + (s_s[2] + s_s[3])));
+        const float ro = (float)(wo * s[0]), rs = (float)(ws * s[1]);
         out[0] = ro; out[1] = rs; out[2] = ro + rs;
     }
 }

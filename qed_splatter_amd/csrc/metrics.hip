@@ -19,13 +19,57 @@ constexpr int kMetricMaxGrid = QED_METRICS_WS_DOUBLES / kMetricCols;
 // columns: 0 sum (dr^2+dg^2+db^2) | 1 n_valid | 2 sum |g-p|/g | 3 sum (g-p)^2/g | 4 sum (g-p)^2
 //          5 sum (log g - log p)^2 over non-NaN | 6 count non-NaN | 7,8,9 counts a1,a2,a3
 // Each workgroup writes its ten partial sums to its own slots (workspace[col][block]) and a second,
-// one-workgroup launch folds them: same-address atomics serialise (~12 ns each; ten per workgroup made
-// this pass 103 us at 1080p instead of ~15).
+// one-workgroup launch folds them (the pattern and its tail: qed_reduce.h).
 
-// per-wave partial of slot `slot` -> s_tmp[slot][wave]
-__device__ __forceinline__ void park_wave_sum(float v, double* s_tmp, int slot) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s_tmp[slot * 4 + (threadIdx.x >> 6)] = (double)v;
+// THE definition of columns 0-9: one pixel's terms, from its two colours (has_rgb) and its two depths (has_depth)
+__device__ __forceinline__ void metric_terms(float* acc, bool has_rgb, const float (&pr)[3], const float (&gr)[3],
+                                             bool has_depth, float p, float g, float tolerance) {
+    if (has_rgb) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float d = pr[k] - gr[k];
+            acc[0] += d * d;
+        }
+    }
+    if (has_depth && isfinite(p) && isfinite(g) && g > tolerance) {
+        const float d = g - p;
+        acc[1] += 1.f;
+        acc[2] += fabsf(d) / g;
+        acc[3] += d * d / g;
+        acc[4] += d * d;
+        const float l = logf(g) - logf(p);          // NaN for p < 0, +-inf for p == 0 (kept, like nanmean)
+        const float l2 = l * l;
+        if (!isnan(l2)) { acc[5] += l2; acc[6] += 1.f; }
+        const float t = fmaxf(g / p, p / g);
+        acc[7] += t < 1.25f ? 1.f : 0.f;
+        acc[8] += t < 1.25f * 1.25f ? 1.f : 0.f;
+        acc[9] += t < 1.25f * 1.25f * 1.25f ? 1.f : 0.f;
+    }
+}
+
+// THE definition of out[0..9], from the sums of columns 0-9
+__device__ void metric_outputs(const double* s, int n_pix, int has_rgb, int has_depth, float* __restrict__ out) {
+    const float nanv = __builtin_nanf("");
+    if (has_rgb) {
+        const double mse = s[0] / (3.0 * (double)n_pix);
+        out[0] = (float)mse;
+        out[1] = (float)(10.0 * log10(1.0 / mse));
+    } else {
+        out[0] = nanv; out[1] = nanv;
+    }
+    const double n = s[1];
+    if (has_depth && n > 0.0) {
+        out[2] = (float)(s[2] / n);
+        out[3] = (float)(s[3] / n);
+        out[4] = (float)sqrt(s[4] / n);
+        out[5] = s[6] > 0.0 ? (float)sqrt(s[5] / s[6]) : nanv;
+        out[6] = (float)(s[7] / n);
+        out[7] = (float)(s[8] / n);
+        out[8] = (float)(s[9] / n);
+    } else {
+        for (int i = 2; i < 9; ++i) out[i] = nanv;
+    }
+    out[9] = (float)n;
 }
 
 __global__ void __launch_bounds__(256)
@@ -55,42 +99,13 @@ metrics_kernel(int n_pix, const float* __restrict__ pred_rgb, const float* __res
             if (pred_depth != nullptr) { pd[u] = pred_depth[i]; gd[u] = gt_depth[i]; }
         }
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            if (!in[u]) continue;
-            if (pred_rgb != nullptr) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float d = pr[u][k] - gr[u][k];
-                    acc[0] += d * d;
-                }
-            }
-            if (pred_depth != nullptr) {
-                const float p = pd[u], g = gd[u];
-                if (isfinite(p) && isfinite(g) && g > tolerance) {
-                    const float d = g - p;
-                    acc[1] += 1.f;
-                    acc[2] += fabsf(d) / g;
-                    acc[3] += d * d / g;
-                    acc[4] += d * d;
-                    const float l = logf(g) - logf(p);          // NaN for p < 0, +-inf for p == 0 (kept, like nanmean)
-                    const float l2 = l * l;
-                    if (!isnan(l2)) { acc[5] += l2; acc[6] += 1.f; }
-                    const float t = fmaxf(g / p, p / g);
-                    acc[7] += t < 1.25f ? 1.f : 0.f;
-                    acc[8] += t < 1.25f * 1.25f ? 1.f : 0.f;
-                    acc[9] += t < 1.25f * 1.25f * 1.25f ? 1.f : 0.f;
-                }
-            }
-        }
+        for (int u = 0; u < kU; ++u)
+            if (in[u]) metric_terms(acc, pred_rgb != nullptr, pr[u], gr[u], pred_depth != nullptr, pd[u], gd[u], tolerance);
     }
-    __shared__ double s_tmp[kMetricCols * 4];
-#pragma unroll
-    for (int i = 0; i < kMetricCols; ++i) park_wave_sum(acc[i], s_tmp, i);
-    __syncthreads();
-    if (threadIdx.x < kMetricCols) {
-        const int i = threadIdx.x;
-        partials[(size_t)i * kMetricMaxGrid + blockIdx.x] = s_tmp[4 * i] + s_tmp[4 * i + 1] + s_tmp[4 * i + 2] + s_tmp[4 * i + 3];
-    }
+    __shared__ double s_w[kMetricCols][4];
+    __shared__ double s[kMetricCols];
+    block_sum_f(acc, s_w, s);
+    if (threadIdx.x < kMetricCols) partials[(size_t)threadIdx.x * kMetricMaxGrid + blockIdx.x] = s[threadIdx.x];
 }
 
 __global__ void __launch_bounds__(256)
@@ -107,73 +122,33 @@ metrics_finalize_kernel(int n_pix, int n_blocks, int has_rgb, int has_depth, con
 #pragma unroll
         for (int c = 0; c < kMetricCols; ++c) v[c] += partials[(size_t)c * kMetricMaxGrid + b];
     }
-#pragma unroll
-    for (int c = 0; c < kMetricCols; ++c) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o, 64);
-        if ((threadIdx.x & 63) == 0) s_w[c][threadIdx.x >> 6] = v[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < kMetricCols) s[threadIdx.x] = s_w[threadIdx.x][0] + s_w[threadIdx.x][1] + s_w[threadIdx.x][2] + s_w[threadIdx.x][3];
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const float nanv = __builtin_nanf("");
-    if (has_rgb) {
-        const double mse = s[0] / (3.0 * (double)n_pix);
-        out[0] = (float)mse;
-        out[1] = (float)(10.0 * log10(1.0 / mse));
-    } else {
-        out[0] = nanv; out[1] = nanv;
-    }
-    const double n = s[1];
-    if (has_depth && n > 0.0) {
-        out[2] = (float)(s[2] / n);
-        out[3] = (float)(s[3] / n);
-        out[4] = (float)sqrt(s[4] / n);
-        out[5] = s[6] > 0.0 ? (float)sqrt(s[5] / s[6]) : nanv;
-        out[6] = (float)(s[7] / n);
-        out[7] = (float)(s[8] / n);
-        out[8] = (float)(s[9] / n);
-    } else {
-        for (int i = 2; i < 9; ++i) out[i] = nanv;
-    }
-    out[9] = (float)n;
+    block_sum_d(v, s_w, s);
+    if (threadIdx.x == 0) metric_outputs(s, n_pix, has_rgb, has_depth, out);
 }
 
 // model.py:192-194 `torch.nanmean(torch.exp(self.scales[..., -1]))`: ~8 eager launches over N values per step in the
 // reference; here one pass + a one-workgroup fold.  partials: [2][kMetricMaxGrid] doubles (sum, count of non-NaN).
 __global__ void __launch_bounds__(256)
 nanmean_exp_kernel(int n, const float* __restrict__ x, int stride, double* __restrict__ partials) {
-    float sum = 0.f, cnt = 0.f;
+    float acc[2] = {0.f, 0.f};                                // sum, count
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < (size_t)n; i += (size_t)gridDim.x * 256) {
         const float e = expf(x[i * (size_t)stride]);
-        if (!isnan(e)) { sum += e; cnt += 1.f; }
+        if (!isnan(e)) { acc[0] += e; acc[1] += 1.f; }
     }
-    __shared__ double s_tmp[2 * 4];
-    park_wave_sum(sum, s_tmp, 0);
-    park_wave_sum(cnt, s_tmp, 1);
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const int i = threadIdx.x;
-        partials[(size_t)i * kMetricMaxGrid + blockIdx.x] = s_tmp[4 * i] + s_tmp[4 * i + 1] + s_tmp[4 * i + 2] + s_tmp[4 * i + 3];
-    }
+    __shared__ double s_w[2][4];
+    __shared__ double s[2];
+    block_sum_f(acc, s_w, s);
+    if (threadIdx.x < 2) partials[(size_t)threadIdx.x * kMetricMaxGrid + blockIdx.x] = s[threadIdx.x];
 }
 
 __global__ void __launch_bounds__(256)
 nanmean_exp_finalize_kernel(int n_blocks, const double* __restrict__ partials, float* __restrict__ out) {
     __shared__ double s_w[2][4];
-    for (int c = 0; c < 2; ++c) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < n_blocks; b += 256) v += partials[(size_t)c * kMetricMaxGrid + b];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if ((threadIdx.x & 63) == 0) s_w[c][threadIdx.x >> 6] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double sum = s_w[0][0] + s_w[0][1] + s_w[0][2] + s_w[0][3], cnt = s_w[1][0] + s_w[1][1] + s_w[1][2] + s_w[1][3];
-        out[0] = cnt > 0.0 ? (float)(sum / cnt) : __builtin_nanf("");      // torch.nanmean of nothing is NaN
-    }
+    __shared__ double s[2];
+    double v[2] = {0.0, 0.0};                                 // sum, count
+    for (int b = threadIdx.x; b < n_blocks; b += 256) { v[0] += partials[b]; v[1] += partials[kMetricMaxGrid + b]; }
+    block_sum_d(v, s_w, s);
+    if (threadIdx.x == 0) out[0] = s[1] > 0.0 ? (float)(s[0] / s[1]) : __builtin_nanf("");      // torch.nanmean of nothing is NaN
 }
 
 // ---- everything get_metrics_dict needs from the images in ONE pass + ONE fold (qed_step_metrics) -------------------
@@ -212,32 +187,13 @@ step_metrics_kernel(int n_pix, const float* __restrict__ pred_rgb, const float* 
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             if (!in[u]) continue;
+            metric_terms(acc, true, pr[u], gr[u], pred_depth != nullptr, pd[u], gd[u], tolerance);
+            if (!want_loss) continue;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float d = pr[u][k] - gr[u][k];
-                acc[0] += d * d;
-                if (want_loss) acc[10] += fabsf(pr[u][k] * mk[u] - gr[u][k] * mk[u]);
-            }
-            if (pred_depth != nullptr) {
-                const float p = pd[u], g = gd[u];
-                if (isfinite(p) && isfinite(g) && g > tolerance) {
-                    const float d = g - p;
-                    acc[1] += 1.f;
-                    acc[2] += fabsf(d) / g;
-                    acc[3] += d * d / g;
-                    acc[4] += d * d;
-                    const float l = logf(g) - logf(p);
-                    const float l2 = l * l;
-                    if (!isnan(l2)) { acc[5] += l2; acc[6] += 1.f; }
-                    const float t = fmaxf(g / p, p / g);
-                    acc[7] += t < 1.25f ? 1.f : 0.f;
-                    acc[8] += t < 1.25f * 1.25f ? 1.f : 0.f;
-                    acc[9] += t < 1.25f * 1.25f * 1.25f ? 1.f : 0.f;
-                }
-                if (want_loss) {                               // model.py:93-105: masked depths, finite, target > 0
-                    const float dp = p * mk[u], dg = g * mk[u];
-                    if (isfinite(dp) && isfinite(dg) && dg > 0.f) { acc[11] += fabsf(dp - dg); acc[12] += 1.f; }
-                }
+            for (int k = 0; k < 3; ++k) acc[10] += fabsf(pr[u][k] * mk[u] - gr[u][k] * mk[u]);
+            if (pred_depth != nullptr) {                       // model.py:93-105: masked depths, finite, target > 0
+                const float dp = pd[u] * mk[u], dg = gd[u] * mk[u];
+                if (isfinite(dp) && isfinite(dg) && dg > 0.f) { acc[11] += fabsf(dp - dg); acc[12] += 1.f; }
             }
         }
     }
@@ -247,16 +203,12 @@ step_metrics_kernel(int n_pix, const float* __restrict__ pred_rgb, const float* 
             if (!isnan(e)) { acc[13] += e; acc[14] += 1.f; }
         }
     }
-    __shared__ double s_tmp[kStepCols * 4];
-#pragma unroll
-    for (int i = 0; i < kStepCols; ++i) park_wave_sum(acc[i], s_tmp, i);
-    __syncthreads();
-    if (threadIdx.x < kStepCols) {
-        const int i = threadIdx.x;
-        // (a workgroup's sum of <= 2 048 pixels' terms: exact enough as a float; the fold adds the 1 024 of them in double)
-        reinterpret_cast<float*>(partials)[(size_t)i * kStepMaxGrid + blockIdx.x] =
-            (float)(s_tmp[4 * i] + s_tmp[4 * i + 1] + s_tmp[4 * i + 2] + s_tmp[4 * i + 3]);
-    }
+    __shared__ double s_w[kStepCols][4];
+    __shared__ double s[kStepCols];
+    block_sum_f(acc, s_w, s);
+    // (a workgroup's sum of <= 2 048 pixels' terms: exact enough as a float; the fold adds the 1 024 of them in double)
+    if (threadIdx.x < kStepCols)
+        reinterpret_cast<float*>(partials)[(size_t)threadIdx.x * kStepMaxGrid + blockIdx.x] = (float)s[threadIdx.x];
 }
 
 __global__ void __launch_bounds__(256)
@@ -295,33 +247,10 @@ step_metrics_finalize_kernel(int n_pix, int n_blocks, int has_depth, const doubl
         for (int j = 0; j < 8; ++j) v[kStepCols] += (int)threadIdx.x + 256 * j < ssim_n ? (double)e[j] : 0.0;
         for (int b0 = threadIdx.x + 2048; b0 < ssim_n; b0 += 256) v[kStepCols] += (double)ssim_sum[b0];
     }
-#pragma unroll
-    for (int c = 0; c <= kStepCols; ++c) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[c] += __shfl_xor(v[c], o, 64);
-        if ((threadIdx.x & 63) == 0) s_w[c][threadIdx.x >> 6] = v[c];
-    }
-    __syncthreads();
-    if (threadIdx.x <= kStepCols) s[threadIdx.x] = s_w[threadIdx.x][0] + s_w[threadIdx.x][1] + s_w[threadIdx.x][2] + s_w[threadIdx.x][3];
-    __syncthreads();
+    block_sum_d(v, s_w, s);
     if (threadIdx.x != 0) return;
     const float nanv = __builtin_nanf("");
-    const double mse = s[0] / (3.0 * (double)n_pix);
-    out[0] = (float)mse;
-    out[1] = (float)(10.0 * log10(1.0 / mse));
-    const double n = s[1];
-    if (has_depth && n > 0.0) {
-        out[2] = (float)(s[2] / n);
-        out[3] = (float)(s[3] / n);
-        out[4] = (float)sqrt(s[4] / n);
-        out[5] = s[6] > 0.0 ? (float)sqrt(s[5] / s[6]) : nanv;
-        out[6] = (float)(s[7] / n);
-        out[7] = (float)(s[8] / n);
-        out[8] = (float)(s[9] / n);
-    } else {
-        for (int i = 2; i < 9; ++i) out[i] = nanv;
-    }
-    out[9] = (float)n;
+    metric_outputs(s, n_pix, 1, has_depth, out);
     out[10] = ssim_sum != nullptr ? (float)(s[kStepCols] * (double)ssim_norm) : nanv;
     out[11] = has_scales && s[14] > 0.0 ? (float)(s[13] / s[14]) : nanv;          // torch.nanmean of nothing is NaN
     if (losses != nullptr) {

@@ -145,45 +145,18 @@ __device__ __forceinline__ unsigned long long nn_key(int cx, int cy, int cz) {
 // ---- (1) per-axis min / max of the finite points ---------------------------------------------------------------------
 __global__ void __launch_bounds__(kNnThreads)
 nn_minmax_kernel(int n, const float* __restrict__ points, float* __restrict__ part, int* __restrict__ part_bad) {
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int bad = 0;
-    for (long long i = (long long)blockIdx.x * kNnThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kNnThreads) {
-        const float f[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
-        if (isfinite(f[0]) && isfinite(f[1]) && isfinite(f[2])) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], f[a]); mx[a] = fmaxf(mx[a], f[a]); }
-        } else {
-            ++bad;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64));
-        }
-        bad += __shfl_xor(bad, o, 64);
-    }
     __shared__ float s_m[kNnThreads / 64][6];
     __shared__ int s_bad[kNnThreads / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) {
+    Bounds3 b;
+    for (long long i = (long long)blockIdx.x * kNnThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kNnThreads) {
+        const float f[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
+        bounds3_add(b, f);
+    }
+    bounds3_block<kNnThreads>(b, s_m, s_bad);
+    if (threadIdx.x == 0) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { s_m[wid][a] = mn[a]; s_m[wid][3 + a] = mx[a]; }
-        s_bad[wid] = bad;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float r = s_m[0][threadIdx.x];
-        for (int w = 1; w < kNnThreads / 64; ++w)
-            r = threadIdx.x < 3 ? fminf(r, s_m[w][threadIdx.x]) : fmaxf(r, s_m[w][threadIdx.x]);
-        part[6 * blockIdx.x + threadIdx.x] = r;
-    }
-    if (threadIdx.x == 6) {
-        int b = 0;
-        for (int w = 0; w < kNnThreads / 64; ++w) b += s_bad[w];
-        part_bad[blockIdx.x] = b;
+        for (int a = 0; a < 3; ++a) { part[6 * blockIdx.x + a] = b.mn[a]; part[6 * blockIdx.x + 3 + a] = b.mx[a]; }
+        part_bad[blockIdx.x] = b.bad;
     }
 }
 
@@ -210,42 +183,20 @@ nn_fold_kernel(int n, int n_parts, const float* __restrict__ part, const int* __
                NnHeader* __restrict__ hdr, int* __restrict__ status) {
     __shared__ float s_m[kNnThreads / 64][6];
     __shared__ int s_bad[kNnThreads / 64];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int bad = 0;
+    Bounds3 b;
     for (int i = threadIdx.x; i < n_parts; i += kNnThreads) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], part[6 * i + a]); mx[a] = fmaxf(mx[a], part[6 * i + 3 + a]); }
-        bad += part_bad[i];
+        for (int a = 0; a < 3; ++a) { b.mn[a] = fminf(b.mn[a], part[6 * i + a]); b.mx[a] = fmaxf(b.mx[a], part[6 * i + 3 + a]); }
+        b.bad += part_bad[i];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64));
-        }
-        bad += __shfl_xor(bad, o, 64);
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_m[wid][a] = mn[a]; s_m[wid][3 + a] = mx[a]; }
-        s_bad[wid] = bad;
-    }
-    __syncthreads();
+    bounds3_block<kNnThreads>(b, s_m, s_bad);
     if (threadIdx.x == 0) {
-        int tb = 0;
-        for (int w = 0; w < kNnThreads / 64; ++w) {
-            tb += s_bad[w];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], s_m[w][a]); mx[a] = fmaxf(mx[a], s_m[w][3 + a]); }
-        }
         float max_ext = 0.f;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            if (tb == n) { mn[a] = 0.f; mx[a] = 0.f; }
-            hdr->mn[a] = mn[a];
-            hdr->ext[a] = mx[a] - mn[a];
+            if (b.bad == n) { b.mn[a] = 0.f; b.mx[a] = 0.f; }
+            hdr->mn[a] = b.mn[a];
+            hdr->ext[a] = b.mx[a] - b.mn[a];
             max_ext = fmaxf(max_ext, hdr->ext[a]);
         }
         hdr->max_ext = max_ext;
@@ -254,7 +205,7 @@ nn_fold_kernel(int n, int n_parts, const float* __restrict__ part, const int* __
         hdr->n_cells = 0;
         hdr->scan_status[0] = 0;
         status[0] = 0;
-        status[1] = tb;
+        status[1] = b.bad;
         status[2] = 0;
         status[3] = 0;
     }
@@ -631,8 +582,7 @@ pd_prepare_kernel(int n, const float* __restrict__ dist, double threshold, unsig
         vals[i] = (int)i;
         under += (double)d < threshold ? 1 : 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) under += __shfl_xor(under, o, 64);
+    under = wave_sum_i(under);
     if ((threadIdx.x & 63) == 0 && under) atomicAdd(count, (unsigned long long)under);      // integers: exact in any order
     if (blockIdx.x == 0 && threadIdx.x == 0) n_dev[0] = n;
 }

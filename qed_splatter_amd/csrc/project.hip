@@ -450,9 +450,7 @@ project_fwd_kernel(int N, int C, const float* __restrict__ means, const float* _
     if (slot < total) tiles_per_gauss[slot] = ntiles;
     // block sum of tile counts (input of the intersection scan)
     __shared__ int wsum[4];
-    int v = ntiles;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int v = wave_sum_i(ntiles);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) block_sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/qed_splat.h"
+#include "qed_reduce.h"
 
 namespace qed {
 
@@ -244,41 +245,6 @@ __device__ __forceinline__ void sh_basis(float x, float y, float z, float* b) {
 }
 
 
-// ---- wave64 cross-lane helpers (DPP; no LDS traffic) --------------------------------------
-// sum over the 16 lanes of each DPP row; result valid in every lane of the row
-__device__ __forceinline__ float row16_sum(float v) {
-    // quad_perm / row_ror rotate within a row of 16 lanes
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));  // row_ror:1
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));  // row_ror:2
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));  // row_ror:4
-    // row_ror:8 as ONE instruction.  Written with the builtin, the compiler sinks this last add into a following
-    // `if (lane % 16 == 0)` and leaves v_mov 0 + v_mov_dpp outside it: three instructions instead of one, per value.
-    // (s_nop 1: a DPP read needs two wait states after the VALU write of its source; the compiler cannot see
-    // that hazard through inline asm.)
-    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(v));
-    return v;
-}
-
-// full wave64 sum, result valid in every lane
-__device__ __forceinline__ float wave_sum(float v) {
-    v = row16_sum(v);
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // ---- shared between loss.hip and ssim.hip: the sums workspace of the loss passes -------------------------------
 // sums (QED_LOSS_SUMS_FLOATS floats): from [8] on four rows of kLossMaxGrid per-workgroup partials: n_valid, max depth
 // (pass 1), sum |rgb - gt|, sum |depth - gt| (pass 2); loss_finalize_kernel folds them into sums[0..3] and the losses.
@@ -397,8 +363,7 @@ __device__ __forceinline__ void tile_order_body(const TileOrderJob& job, int* __
         mine += c;
         atomicAdd(&cnt[bucket_of(c) * R + region_of(i)], 1);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    mine = wave_sum_ll(mine);
     if (lane == 0) atomicAdd((unsigned long long*)total_s, (unsigned long long)mine);
     __syncthreads();
     // threshold of the split (in cost units -> bucket index): buckets [0, first_light) hold cost > thr

@@ -68,8 +68,7 @@ seed_gaussians_kernel(int n, const float* __restrict__ dist, int k, const unsign
     const long long n_rest = (long long)n * (sh_coeffs - 1) * 3;
     for (long long i = (long long)blockIdx.x * kSeedThreads + threadIdx.x; i < n_rest; i += (long long)gridDim.x * kSeedThreads)
         features_rest[i] = 0.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) clamped += __shfl_xor(clamped, o, 64);
+    clamped = wave_sum_i(clamped);
     if ((threadIdx.x & 63) == 0 && clamped) atomicAdd(&status[0], clamped);
 }
 

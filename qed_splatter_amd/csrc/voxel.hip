@@ -87,46 +87,19 @@ __device__ __forceinline__ float voxel_index(float x, float v) { return floorf(x
 // ---- (1) min / max of the voxel indices ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(kVoxThreads)
 voxel_minmax_kernel(int n, const float* __restrict__ points, float v, float* __restrict__ part, int* __restrict__ part_bad) {
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int bad = 0;
+    __shared__ float s_m[kVoxThreads / 64][6];
+    __shared__ int s_bad[kVoxThreads / 64];
+    Bounds3 b;
     for (long long i = (long long)blockIdx.x * kVoxThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kVoxThreads) {
         const float x = points[3 * i], y = points[3 * i + 1], z = points[3 * i + 2];
         const float f[3] = {voxel_index(x, v), voxel_index(y, v), voxel_index(z, v)};
-        if (isfinite(f[0]) && isfinite(f[1]) && isfinite(f[2])) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], f[a]); mx[a] = fmaxf(mx[a], f[a]); }
-        } else {
-            ++bad;
-        }
+        bounds3_add(b, f);
     }
+    bounds3_block<kVoxThreads>(b, s_m, s_bad);
+    if (threadIdx.x == 0) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64));
-        }
-        bad += __shfl_xor(bad, o, 64);
-    }
-    __shared__ float s_m[kVoxThreads / 64][6];
-    __shared__ int s_bad[kVoxThreads / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_m[wid][a] = mn[a]; s_m[wid][3 + a] = mx[a]; }
-        s_bad[wid] = bad;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float r = s_m[0][threadIdx.x];
-        for (int w = 1; w < kVoxThreads / 64; ++w)
-            r = threadIdx.x < 3 ? fminf(r, s_m[w][threadIdx.x]) : fmaxf(r, s_m[w][threadIdx.x]);
-        part[6 * blockIdx.x + threadIdx.x] = r;
-    }
-    if (threadIdx.x == 6) {
-        int b = 0;
-        for (int w = 0; w < kVoxThreads / 64; ++w) b += s_bad[w];
-        part_bad[blockIdx.x] = b;
+        for (int a = 0; a < 3; ++a) { part[6 * blockIdx.x + a] = b.mn[a]; part[6 * blockIdx.x + 3 + a] = b.mx[a]; }
+        part_bad[blockIdx.x] = b.bad;
     }
 }
 
@@ -138,53 +111,31 @@ voxel_fold_kernel(int n, int n_parts, const float* __restrict__ part, const int*
                   VoxelHeader* __restrict__ hdr, int* __restrict__ status) {
     __shared__ float s_m[kVoxThreads / 64][6];
     __shared__ int s_bad[kVoxThreads / 64];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    int bad = 0;
+    Bounds3 b;
     for (int i = threadIdx.x; i < n_parts; i += kVoxThreads) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], part[6 * i + a]); mx[a] = fmaxf(mx[a], part[6 * i + 3 + a]); }
-        bad += part_bad[i];
+        for (int a = 0; a < 3; ++a) { b.mn[a] = fminf(b.mn[a], part[6 * i + a]); b.mx[a] = fmaxf(b.mx[a], part[6 * i + 3 + a]); }
+        b.bad += part_bad[i];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64));
-            mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64));
-        }
-        bad += __shfl_xor(bad, o, 64);
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_m[wid][a] = mn[a]; s_m[wid][3 + a] = mx[a]; }
-        s_bad[wid] = bad;
-    }
-    __syncthreads();
+    bounds3_block<kVoxThreads>(b, s_m, s_bad);
     if (threadIdx.x == 0) {
-        int tb = 0;
-        for (int w = 0; w < kVoxThreads / 64; ++w) {
-            tb += s_bad[w];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], s_m[w][a]); mx[a] = fmaxf(mx[a], s_m[w][3 + a]); }
-        }
-        const int n_valid = n - tb;
+        const int n_valid = n - b.bad;
         double widest = 0.0;
         if (n_valid > 0) {
 #pragma unroll
-            for (int a = 0; a < 3; ++a) widest = fmax(widest, (double)mx[a] - (double)mn[a] + 1.0);
+            for (int a = 0; a < 3; ++a) widest = fmax(widest, (double)b.mx[a] - (double)b.mn[a] + 1.0);
         } else {
 #pragma unroll
-            for (int a = 0; a < 3; ++a) { mn[a] = 0.f; mx[a] = 0.f; }
+            for (int a = 0; a < 3; ++a) { b.mn[a] = 0.f; b.mx[a] = 0.f; }
         }
         const bool refused = widest > (double)(1 << kVoxAxisBits);
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { hdr->mn[a] = mn[a]; hdr->mx[a] = mx[a]; }
+        for (int a = 0; a < 3; ++a) { hdr->mn[a] = b.mn[a]; hdr->mx[a] = b.mx[a]; }
         hdr->n_sort = refused ? 0 : n;
         hdr->n_valid = refused ? 0 : n_valid;
         hdr->scan_status[0] = 0;
         status[0] = refused ? 1 : 0;
-        status[1] = tb;
+        status[1] = b.bad;
         status[2] = (int)fmin(widest, 2147483647.0);
         status[3] = 0;
     }
@@ -314,10 +265,7 @@ voxel_span_kernel(int n_chunks, const VoxelHeader* __restrict__ hdr, const int* 
         for (int a = 0; a < 3; ++a) s[a] += p[a];
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) s[a] += __shfl_xor(s[a], o, 64);
-    }
+    for (int a = 0; a < 3; ++a) s[a] = wave_sum_d(s[a]);
     if (lane == 0) {
         const double cnt = (double)(end - begin);
 #pragma unroll
