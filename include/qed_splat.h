@@ -67,9 +67,11 @@ extern "C" {
  *      the compact data-parallel message grew from 3 N + 16 to 3 N + 20 floats (still reported as 1 by that round's
  *      library).  A caller built against another version must not call further: the pointers would be shifted.
  *   3  round 5: qed_composite_fwd gained `tile_order` behind `tile_cost`.
- * New entry points change nothing a caller of version 3 relies on and keep the number (the latest: qed_present_range,
+ *   4  qed_adam_tick_t carries beta1 / beta2 as doubles (they were floats): the device-resident bias corrections are
+ *      formed at double precision, as the host-state path forms them.
+ * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_present_range,
  * qed_present_frame). */
-#define QED_ABI_VERSION 3
+#define QED_ABI_VERSION 4
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
 
@@ -368,8 +370,8 @@ int qed_ssim_fwd_step(int32_t height, int32_t width, int32_t channels, const flo
  * the previous step's Adam launches and this step's); follow with qed_adam_step_sh(parts | QED_ADAM_PART_TICKED). */
 typedef struct {
     float* dev_state;        /* as qed_adam_step_dev */
-    float beta1, beta2;
-    float* dev_lr_slot;      /* NULL, or &dev_lr[scheduled group]: receives the exponential decay of qed_lr_exp_decay_dev */
+    double beta1, beta2;     /* doubles, as the Adam entry points take them: the bias corrections are formed in double */
+    float* dev_lr_slot;     /* NULL, or &dev_lr[scheduled group]: receives the exponential decay of qed_lr_exp_decay_dev */
     float lr_init, lr_final;
     int32_t max_steps;
     const int32_t* skip_flag; /* NULL, or as qed_adam_step's: non-zero -> the state is not advanced */
@@ -665,7 +667,8 @@ int qed_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
 
 /* Same update with the step state and learning rates in DEVICE memory, so that a captured hipGraph
  * can be replayed: dev_state[3] = {step, 1/(1-beta1^step), 1/sqrt(1-beta2^step)} is advanced by one
- * (zero it before the first step), dev_lr[8] holds the per-group learning rates. */
+ * (zero it before the first step), dev_lr[8] holds the per-group learning rates.  Both factors are formed from the
+ * double betas at double precision and rounded once: they agree with qed_adam_step's to float rounding at every step. */
 int qed_adam_step_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                       int32_t n_groups, const int64_t* h_group_begin, const float* dev_lr, double beta1,
                       double beta2, float eps, float* dev_state, const int32_t* skip_flag, void* stream);

@@ -122,7 +122,7 @@ class PostGrad(C.Structure):
 
 class AdamTick(C.Structure):
     """qed_adam_tick_t (include/qed_splat.h): the optimiser's device step state, advanced by qed_loss_grad_ssim."""
-    _fields_ = [("dev_state", C.c_void_p), ("beta1", C.c_float), ("beta2", C.c_float), ("dev_lr_slot", C.c_void_p),
+    _fields_ = [("dev_state", C.c_void_p), ("beta1", C.c_double), ("beta2", C.c_double), ("dev_lr_slot", C.c_void_p),
                 ("lr_init", C.c_float), ("lr_final", C.c_float), ("max_steps", C.c_int32), ("skip_flag", C.c_void_p)]
 
 
@@ -175,7 +175,7 @@ class QedSplatError(RuntimeError):
     pass
 
 
-ABI_VERSION = 3          # include/qed_splat.h: QED_ABI_VERSION (tests/test_abi.py checks the two against each other)
+ABI_VERSION = 4         # include/qed_splat.h: QED_ABI_VERSION (tests/test_abi.py checks the two against each other)
 
 
 def load():

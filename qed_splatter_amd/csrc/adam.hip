@@ -297,7 +297,7 @@ extern "C" int qed_adam_step_dev(float* params, const float* grads, float* exp_a
                                  double beta2, float eps, float* dev_state, const int32_t* skip_flag, void* stream) {
     QED_REQUIRE(dev_lr && dev_state, "device lr / state required");
     hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                       AdamTick{dev_state, (float)beta1, (float)beta2, nullptr, 0.f, 0.f, 0.f, skip_flag});
+                       AdamTick{dev_state, beta1, beta2, nullptr, 0.f, 0.f, 0.f, skip_flag});
     return adam_launch(params, grads, exp_avg, exp_avg_sq, n_groups, h_group_begin, nullptr, beta1, beta2, eps, 1,
                        dev_state, dev_lr, skip_flag, stream);
 }
@@ -348,7 +348,7 @@ extern "C" int qed_adam_step_sh(float* params, const float* grads, float* exp_av
         if (!(parts & QED_ADAM_PART_TICKED)) {           // (else qed_loss_grad_ssim's fold launch has advanced the state)
             const bool sched = sched_group >= 0;
             hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, st,
-                               AdamTick{dev_state, (float)beta1, (float)beta2,
+                               AdamTick{dev_state, beta1, beta2,
                                         sched ? dev_lr + sched_group : (float*)nullptr,
                                         sched ? logf(sched_lr_init) : 0.f, sched ? logf(sched_lr_final) : 0.f,
                                         sched ? 1.f / (float)sched_max_steps : 0.f, skip_flag});

@@ -255,9 +255,12 @@ __device__ __forceinline__ float* loss_part(float* sums, int row) { return sums 
 // 1 / (1 - beta1^step), 1 / sqrt(1 - beta2^step)}; one thread.  A launch of its own (adam_tick_kernel) or, in the fused
 // training step, a passenger of the loss pass's one-workgroup fold launch (qed_loss_grad_ssim's `tick`): that launch
 // sits between the previous step's Adam launches and this step's, which is all the tick needs.
+// The betas stay DOUBLES down to here: 1 - (float)0.999 is off by 1.3e-5 relative (see AdamCoef, adam.hip), which
+// 1 / sqrt(1 - beta2^step) would carry for the first thousand steps.  Both factors are formed in double and rounded once,
+// exactly as the host-state path forms them (adam_launch).  One thread, once per step.
 struct AdamTick {
     float* state;           // NULL: nothing to do
-    float beta1, beta2;
+    double beta1, beta2;
     float* lr_slot;         // NULL, or the scheduled group's learning-rate slot (lr_exp_decay_kernel's formula)
     float log_init, log_final, inv_max_steps;
     const int* skip;        // NULL, or the word that makes the step a no-op when non-zero (see adam_skipped, adam.hip)
@@ -271,8 +274,8 @@ __device__ __forceinline__ void adam_tick(const AdamTick& t) {
     }
     const float n = t.state[0] + 1.f;
     t.state[0] = n;
-    t.state[1] = 1.f / (1.f - powf(t.beta1, n));
-    t.state[2] = 1.f / sqrtf(1.f - powf(t.beta2, n));
+    t.state[1] = (float)(1.0 / (1.0 - pow(t.beta1, (double)n)));
+    t.state[2] = (float)(1.0 / sqrt(1.0 - pow(t.beta2, (double)n)));
 }
 
 __global__ void loss_finalize_kernel(int n_pix, int n_blocks, int has_depth, float* __restrict__ sums, float rgb_weight,

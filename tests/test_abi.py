@@ -41,7 +41,7 @@ def test_host_only_entry_points(lib):
     from qed_splatter_amd import _lib
     header = open(HEADER).read()
     declared = int(re.search(r"#define\s+QED_ABI_VERSION\s+(\d+)", header).group(1))
-    assert lib.qed_version() == declared == _lib.ABI_VERSION == 3
+    assert lib.qed_version() == declared == _lib.ABI_VERSION == 4
     # workspace sizing is pure host arithmetic: monotone, and enough for 256 counters per block
     a, b = lib.qed_sort_workspace_bytes(1), lib.qed_sort_workspace_bytes(10_000_000)
     assert 0 < a < b and b >= 256 * 4 * (10_000_000 // 2048)

@@ -1013,10 +1013,16 @@ def test_fused_adam_matches_torch(cuda):
         opt.step()
         for o in ref_opts:
             o.step()
-        for k in PARAM_NAMES:
+        for i, k in enumerate(PARAM_NAMES):
             # the reference optimiser sees the same gradients only on the first step (parameters drift
             # by fp32 rounding afterwards), so compare after re-synchronising
             assert_close(m.gauss_params[k], ref_params[k], 1e-5, f"adam {k}")
+            # both moments, three steps of float32 rounding on either side (1 - (float)0.999 alone would be 1.3e-5; the
+            # element-wise comparison against float64 is tests/test_adam_parity.py's)
+            st = ref_opts[i].state[ref_params[k]]
+            b0, b1 = m.group_begin[i], m.group_begin[i + 1]
+            assert_close(opt.exp_avg[b0:b1], st["exp_avg"].reshape(-1), 2e-6, f"adam exp_avg {k}")
+            assert_close(opt.exp_avg_sq[b0:b1], st["exp_avg_sq"].reshape(-1), 2e-6, f"adam exp_avg_sq {k}")
             ref_params[k].data.copy_(m.gauss_params[k].data)
 
 
