@@ -140,12 +140,15 @@ class _ImageLosses(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rgb, depth, gt_rgb, gt_depth, mask, ssim_lambda, depth_lambda, ssim_shared=None, loss_shared=None,
-                vsplat=None, grad_out=None):
+                handover=None):
         lib = L.load()
         ctx.set_materialize_grads(False)
-        # (holder, rows, static buffer | None): the compositing backward's accumulator, zeroed by this node's backward launch
-        ctx.vsplat = vsplat
-        ctx.grad_out = grad_out   # (v_rgb, v_depth) static buffers of a captured get_outputs segment, or None
+        # handover.Handover of the step these images belong to, or None.  The first loss taken on them zeroes the compositing
+        # backward's accumulator in its backward launch, and behind a captured get_outputs segment writes v_rgb / v_depth
+        # into the segment's static buffers
+        ctx.handover = handover
+        ctx.zeroes = handover is not None and handover.claim_accumulator()
+        ctx.writes = handover is not None and handover.claim_grad_buffers()
         if not rgb.is_cuda:
             raise L.QedSplatError("get_loss_dict needs GPU tensors: there is no CPU path in the product")
         H, W, _ = rgb.shape
@@ -194,7 +197,8 @@ class _ImageLosses(torch.autograd.Function):
         def scalar(g):
             return None if g is None else g.to(torch.float32).reshape(1).contiguous()
         g_main, g_depth = scalar(g_main), scalar(g_depth)
-        sv_rgb, sv_depth = ctx.grad_out if ctx.grad_out is not None else (None, None)
+        handover = ctx.handover
+        sv_rgb, sv_depth = (handover.v_rgb, handover.v_depth) if ctx.writes else (None, None)
 
         def out_like(t, static):
             return static if (static is not None and static.shape == t.shape) else torch.empty_like(t)
@@ -204,24 +208,19 @@ class _ImageLosses(torch.autograd.Function):
         if v_rgb is not None and ssim_lambda > 0.0:
             # ONE launch: the L1 term joins the SSIM term inside the SSIM backward pass, the depth term rides along
             n_out = _ssim_n_out(H, W)
-            zero = None
-            if ctx.vsplat is not None:
-                holder, rows, static = ctx.vsplat
-                zero = static if static is not None else \
-                    torch.empty(rows, L.VSPLAT_FLOATS, dtype=torch.float32, device=rgb.device)
+            zero = handover.accumulator(rgb.device) if ctx.zeroes else None
             L.check(lib.qed_image_losses_ssim_bwd(H, W, L.ptr(rgb), L.ptr(depth), L.ptr(gt_rgb), L.ptr(gt_depth),
                                                   L.ptr(mask), L.ptr(maps), L.ptr(sums), 1.0 - ssim_lambda, depth_lambda,
                                                   -ssim_lambda / n_out, L.ptr(g_main), L.ptr(g_depth), L.ptr(v_rgb),
                                                   L.ptr(v_depth), L.ptr(zero), zero.numel() if zero is not None else 0, st),
                     "qed_image_losses_ssim_bwd")
             if zero is not None:
-                del holder[:]
-                holder.append(zero)
+                handover.offer(vsplat=zero)
         else:
             L.check(lib.qed_image_losses_bwd(H * W, L.ptr(rgb), L.ptr(depth), L.ptr(gt_rgb), L.ptr(gt_depth), L.ptr(mask),
                                              L.ptr(sums), 1.0 - ssim_lambda, depth_lambda, L.ptr(g_main), L.ptr(g_depth), 0,
                                              L.ptr(v_rgb), L.ptr(v_depth), st), "qed_image_losses_bwd")
-        return v_rgb, v_depth, None, None, None, None, None, None, None, None, None
+        return (v_rgb, v_depth) + (None,) * 8
 
 
 class _FusedImageLoss(torch.autograd.Function):
@@ -229,8 +228,8 @@ class _FusedImageLoss(torch.autograd.Function):
     (model.py:295-297, 304-306, 87-116 and the parent's main loss behind :83-85)."""
 
     @staticmethod
-    def forward(ctx, render, alpha, background, gt_rgb, gt_depth, mask, ssim_lambda, depth_lambda, vsplat_holder=None,
-                vsplat_rows=0, tick=None, tile_cost=None, order_buf=None):
+    def forward(ctx, render, alpha, background, gt_rgb, gt_depth, mask, ssim_lambda, depth_lambda, handover=None, tick=None,
+                tile_cost=None):
         import ctypes
         lib = L.load()
         ctx.set_materialize_grads(False)
@@ -248,17 +247,16 @@ class _FusedImageLoss(torch.autograd.Function):
             # main = (1 - l) L1 + l (1 - SSIM): ONE launch forms the SSIM gradient w.r.t. the clamped colour and pushes
             # it, with the L1 part and the depth term, through the clamp / background composite (qed_loss_grad_ssim)
             # the same launch zeroes the accumulator the compositing backward will add into (no fill launch there)
-            vsplat = None
-            if vsplat_holder is not None and vsplat_rows > 0:
-                vsplat = torch.empty(vsplat_rows, L.VSPLAT_FLOATS, dtype=torch.float32, device=dev)
+            vsplat = handover.accumulator(dev) if (handover is not None and handover.claim_accumulator()) else None
             maps, ssum, n_out = ssim_buffers(H, W, dev)
             # The SSIM forward launch carries two passengers that would otherwise be launches of their own on the step's
             # critical chain: pass 1 of the image loss (qed_loss_reduce: ~9 us) and -- the forward pass's per-tile costs
             # are known by now -- the compositing backward's launch order (~10 us in front of that kernel).
             order_ws = None
-            if vsplat_holder is not None and tile_cost is not None:
+            if handover is not None and tile_cost is not None:
                 # (the camera's persistent launch-order buffer when the caller keeps one: model.fused_loss, frame_key)
-                order_ws = order_buf if (order_buf is not None and order_buf.numel() == tile_cost.shape[0] + 1) else \
+                kept = handover.frame_order
+                order_ws = kept.buffer if (kept is not None and kept.fits(tile_cost.shape[0])) else \
                     torch.empty(tile_cost.shape[0] + 1, dtype=torch.int32, device=dev)
             if os.environ.get("QED_STEP_PASSENGERS", "1") == "0":          # measurement hook: every job a launch of its own
                 L.check(lib.qed_loss_reduce(*args, L.ptr(sums), st), "qed_loss_reduce")
@@ -277,8 +275,7 @@ class _FusedImageLoss(torch.autograd.Function):
                                            vsplat.numel() if vsplat is not None else 0,
                                            ctypes.addressof(tick) if tick is not None else None, st), "qed_loss_grad_ssim")
             if vsplat is not None or order_ws is not None:
-                del vsplat_holder[:]
-                vsplat_holder.append({"vsplat": vsplat, "order_ws": order_ws})
+                handover.offer(vsplat, order_ws)
         else:
             L.check(lib.qed_loss_reduce(*args, L.ptr(sums), st), "qed_loss_reduce")
             L.check(lib.qed_loss_grad(*args, L.ptr(sums), 1.0, depth_lambda, L.ptr(v_render), L.ptr(v_alpha),
@@ -292,13 +289,13 @@ class _FusedImageLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, v_total, _v_parts):
         if v_total is None:
-            return (None,) * 13
+            return (None,) * 11
         v_render, v_alpha = ctx.saved_tensors
         # the kernel wrote d(total)/d(render, alpha).  The usual upstream gradient is the cached unit tensor of
         # backward_fused() and needs no scaling pass; anything else (a weighted loss, a GradScaler) is applied
         if v_total.data_ptr() != _unit_grad(v_total.device).data_ptr():
             v_render, v_alpha = v_render * v_total, v_alpha * v_total
-        return v_render, v_alpha, None, None, None, None, None, None, None, None, None, None, None
+        return (v_render, v_alpha) + (None,) * 9
 
 
 def _mcmc_reg_values(opacities: Tensor, scales: Tensor, lo: float, ls: float) -> Tensor:

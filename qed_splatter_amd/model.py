@@ -37,6 +37,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib as L
+from .handover import FrameOrder, Handover
 from .losses import _FusedImageLoss, _ImageLosses, _McmcReg, _f32_image, _mcmc_reg_grad_adder, _mcmc_reg_values
 from .losses import _ssim_key, _unit_grad
 from .losses import _PostProcess, _SSIM, _UNIT_GRADS, ssim  # noqa: F401  (also importable from here)
@@ -210,25 +211,22 @@ class StepContext:
         tensor's identity, version and the downscale factor -- get_metrics_dict and get_loss_dict prepare the same image;
       * ``ssim``: get_metrics_dict's SSIM forward on (rgb, ground truth) with the maps and sums the loss needs -- taken ONCE
         (``take_ssim``) and checked against the tensors the loss is actually handed before it is used;
-      * ``take_accumulator()``: (holder, rows) through which the loss's backward launch hands the compositing backward a
-        zero-filled gradient accumulator -- once; a second loss on the same outputs makes the backward pass fill its own."""
+      * ``handover``: the step's ``handover.Handover``: the loss's backward launch hands the compositing backward a zero-filled
+        gradient accumulator through it -- claimed once; a second loss on the same outputs makes the backward fill its own."""
 
-    __slots__ = ("rgb", "_holder", "_rows", "_gt", "ssim", "static")
+    __slots__ = ("rgb", "handover", "_gt", "ssim")
 
     def __init__(self):
         self.rgb = None
-        self._holder, self._rows = None, 0
+        self.handover = None
         self._gt = None
         self.ssim = None
-        # a captured segment's static buffers (segments.OutputsSegment): (v_rgb [H,W,3], v_depth [H,W,1] | None, the
-        # compositing backward's accumulator) -- the loss's backward launch writes / zeroes THESE instead of fresh ones
-        self.static = None
 
     def owns(self, outputs) -> bool:
         return self.rgb is not None and outputs.get("rgb") is self.rgb
 
-    def bind(self, rgb: Tensor, holder: list, rows: int) -> None:
-        self.rgb, self._holder, self._rows = rgb, holder, rows
+    def bind(self, rgb: Tensor, handover: Handover) -> None:
+        self.rgb, self.handover = rgb, handover
 
     def gt_image(self, image: Tensor, d: int, convert) -> Tensor:
         memo = self._gt
@@ -242,19 +240,6 @@ class StepContext:
     def take_ssim(self):
         shared, self.ssim = self.ssim, None
         return shared
-
-    def take_accumulator(self):
-        if self._holder is None:
-            return None
-        pair, self._holder = (self._holder, self._rows, self.static[2] if self.static is not None else None), None
-        return pair
-
-    def take_grad_buffers(self):
-        """(v_rgb, v_depth) static buffers of a captured segment for the loss's backward launch, once; else None."""
-        if self.static is None or self.static[0] is None:
-            return None
-        bufs, self.static = self.static[:2], (None, None, self.static[2])
-        return bufs
 
 
 def write_sh_grads(means: Tensor, viewmat: Tensor, sh_degree: int, v_color: Tensor, v_rest: Tensor) -> None:
@@ -861,16 +846,15 @@ class QEDSplatterModel(nn.Module):
             flags |= L.F_SH_GRAD_COMPACT
 
         background = self._get_background_color()
-        holder: list = []         # (get_loss_dict's backward launch leaves the compositing backward's zeroed accumulator here)
 
-        # the camera's launch-order slot (fused_loss: frame_key): the reference's trainer hands the camera index in
+        # the camera's launch order (fused_loss: frame_key): the reference's trainer hands the camera index in
         # camera.metadata["cam_idx"]; only on the eager route -- a captured segment is replayed for every camera
-        frame_slot = None
+        frame_order = None
         meta = getattr(camera, "metadata", None)
         if self.training and torch.is_grad_enabled() and meta is not None and "cam_idx" in meta and crop_ids is None:
-            frame_slot = self._frame_order_slot(meta["cam_idx"], H, W)
+            frame_order = self._frame_order_slot(meta["cam_idx"], H, W)
 
-        def render_fn(c2w, intr, bg, hold, capture_slot=None, viewmats=None, Ks=None, manual=None):
+        def render_fn(c2w, intr, bg, handover, capture_slot=None, viewmats=None, Ks=None, manual=None):
             """The rasterization(...) call of model.py:267-288 (+ the statements that follow it, inside the compositing
             kernels): here on this call's tensors, and -- once the shape has been seen a few times -- captured on static
             ones (segments.OutputsSegment)."""
@@ -883,12 +867,11 @@ class QEDSplatterModel(nn.Module):
                 quats=quats_crop,                       # normalised inside the projection kernel (model.py:269)
                 viewmats=viewmats, Ks=Ks, width=W, height=H, render_mode=render_mode, sh_degree=sh_degree_to_use,
                 _flags=flags, _sh_rest=sh_rest, _sync=not (self.config.async_intersection_count and self.training),
-                _c2w=(c2w, intr) if c2w is not None else None, _post_background=bg, _vsplat_holder=hold,
+                _c2w=(c2w, intr) if c2w is not None else None, _post_background=bg, _handover=handover,
                 _means2d_leaf=True,     # xys is only retained and read (below; densify.py): its gradient arrives as a view
                 _capture_slot=capture_slot, _manual=manual,
                 # (a captured backward pass always writes the compact form; _SegmentFn.backward asks per replay)
-                _lazy_sh=self._lazy_sh_begin if (lazy and manual is None) else None,
-                _tile_order=frame_slot if (manual is None and capture_slot is None) else None)
+                _lazy_sh=self._lazy_sh_begin if (lazy and manual is None) else None)
 
         seg = None
         if (self.training and self.config.graph_segments and cam_c2w is not None and crop_ids is None
@@ -896,12 +879,13 @@ class QEDSplatterModel(nn.Module):
             seg = self._outputs_segment(W, H, render_mode, sh_degree_to_use, flags, render_fn, cam_c2w, background)
         if seg is not None:
             rgb, alpha, depth_im = seg.run(cam_c2w[0], cam_c2w[1], background)
-            info, holder, render = seg.info, seg.holder, None
-            ctx.static = (seg.v_rgb[0], seg.v_depth[0] if seg.v_depth is not None else None, seg.vsplat)
+            info, handover, render = seg.info, seg.handover, None       # (the segment's own: it knows the static buffers)
             background = seg.bg
         else:
+            # (get_loss_dict's backward launch offers the compositing backward its zeroed accumulator through this)
+            handover = Handover(viewmat.shape[0] * means_crop.shape[0], frame_order)
             render, alpha, info = render_fn(cam_c2w[0] if cam_c2w else None, cam_c2w[1] if cam_c2w else None, background,
-                                            holder, viewmats=viewmat, Ks=K)
+                                            handover, viewmats=viewmat, Ks=K)
             # model.py:296-297 (composite + clamp) and :304-308 (depth fix-up) ran inside the compositing kernel, and
             # their backward runs inside the compositing backward (rasterization(_post_background=...)): no pass of its
             # own over the image in either direction (losses._PostProcess is the stand-alone form of the same statements)
@@ -938,7 +922,7 @@ class QEDSplatterModel(nn.Module):
         # The step's shortcuts (shared SSIM, the loss writing the compositing backward's gradient buffers) assume the loss
         # gradient goes straight to the compositing backward: they are bound to the image BEFORE a bilateral grid, so a
         # corrected image takes the general path of get_loss_dict / get_metrics_dict
-        ctx.bind(rgb if pre_grid is None else pre_grid, holder, info["radii"].numel())
+        ctx.bind(rgb if pre_grid is None else pre_grid, handover)
         return {
             "rgb": rgb,
             "depth": depth_im,
@@ -1011,11 +995,10 @@ class QEDSplatterModel(nn.Module):
                 loss_shared = shared["loss"]
         # the accumulator of the compositing backward behind THESE outputs is zeroed by this loss's backward launch (the
         # first loss taken on them: a second one leaves the fill to the backward pass)
-        pair = ctx.take_accumulator() if (mine and torch.is_grad_enabled()) else None
-        grad_out = ctx.take_grad_buffers() if (mine and torch.is_grad_enabled()) else None
+        handover = ctx.handover if (mine and torch.is_grad_enabled()) else None
         main, depth = _ImageLosses.apply(pred_img, depth_out, gt_img, depth_batch, mask, float(cfg.ssim_lambda),
-                                         float(cfg.depth_lambda), shared["maps_sum"] if shared else None, loss_shared, pair,
-                                         grad_out)
+                                         float(cfg.depth_lambda), shared["maps_sum"] if shared else None, loss_shared,
+                                         handover)
         out = {"main_loss": main, "scale_reg": self._scale_reg()}
         lo, ls = self._mcmc_reg_weights()
         if lo > 0.0 or ls > 0.0:
@@ -1122,17 +1105,16 @@ class QEDSplatterModel(nn.Module):
         losses["loss"].backward(gradient=_unit_grad(losses["loss"].device))
 
     # ---- fused training step: model.py:199-321 + 73-118 in as few passes as possible ----
-    def _frame_order_slot(self, frame_key, H: int, W: int) -> list:
-        """[order buffer [tiles + 1] int32, holds-an-order flag] of camera ``frame_key`` at this resolution: the launch order
-        a frame's compositing backward is given (from that frame's per-tile work counts), which the NEXT frame of the same
-        camera hands its compositing forward.  Persistent, so that a captured step replays against it."""
+    def _frame_order_slot(self, frame_key, H: int, W: int) -> FrameOrder:
+        """The FrameOrder (order buffer [tiles + 1] int32, holds-an-order flag) of camera ``frame_key`` at this resolution:
+        the launch order a frame's compositing backward is given (from that frame's per-tile work counts), which the NEXT
+        frame of the same camera hands its compositing forward.  Persistent, so that a captured step replays against it."""
         tiles = ((W + 15) // 16) * ((H + 15) // 16)
         orders = self.__dict__.setdefault("_frame_orders", {})
-        slot = orders.get((frame_key, H, W))
-        if slot is None or slot[0].device != self.device:
-            slot = [torch.empty(tiles + 1, dtype=torch.int32, device=self.device), False]
-            orders[(frame_key, H, W)] = slot
-        return slot
+        order = orders.get((frame_key, H, W))
+        if order is None or order.buffer.device != self.device:
+            order = orders[(frame_key, H, W)] = FrameOrder(torch.empty(tiles + 1, dtype=torch.int32, device=self.device))
+        return order
 
     def fused_loss(self, camera, batch, background: Optional[Tensor] = None, sync: bool = True,
                    compact_sh_grad: bool = False, optimizer: Optional["FlatAdam"] = None,
@@ -1170,7 +1152,6 @@ class QEDSplatterModel(nn.Module):
         attrs["sh_views"] = None              # set by parallel.exchange_grads_compact(rebuild=False)
         bg = (background if background is not None else self._get_background_color()).to(self.device, torch.float32)
         gt_rgb, gt_depth, mask = self._ground_truth(batch, bg, H, W)           # exactly as get_loss_dict prepares it
-        holder: list = []         # (the fused loss launch leaves the compositing backward's zeroed accumulator here)
         # strategy="mcmc": the two regularisers of get_loss_dict, folded into ``loss``; their gradient is added to the flat
         # gradient by the projection backward, right after it has written it (for an upstream gradient of 1, as above)
         lo, ls = self._mcmc_reg_weights()
@@ -1181,10 +1162,9 @@ class QEDSplatterModel(nn.Module):
                 post_bwd = _mcmc_reg_grad_adder(self.opacities, self.scales, lo, ls)
         # the launch-order buffer of this camera (see ``frame_key``): [C T + 1] int32, written by every training frame's
         # loss launch, read by the next frame's compositing forward -- persistent, so that a captured step replays against it
-        frame_slot, frame_order, frame_order_valid = None, None, False
-        if frame_key is not None:
-            frame_slot = self._frame_order_slot(frame_key, H, W)
-            frame_order, frame_order_valid = frame_slot[0], frame_slot[1]
+        frame_order = self._frame_order_slot(frame_key, H, W) if frame_key is not None else None
+        # (the fused loss launch offers the compositing backward its zeroed accumulator and launch order through this)
+        handover = Handover(self.num_points, frame_order)
         # ``optimizer`` (a FlatAdam stepped with device_state=True, fused_sh=True right after this step's backward): the
         # loss pass's fold launch advances its device step state, so that the optimiser needs no launch of its own for it
         tick = None
@@ -1194,19 +1174,20 @@ class QEDSplatterModel(nn.Module):
             render, alpha, info = self._rasterize(
                 means=self.means, quats=self.quats, scales=self.scales, opacities=self.opacities, colors=colors,
                 viewmats=viewmat, Ks=K, width=W, height=H, render_mode="RGB+D", sh_degree=deg, _flags=flags,
-                _sh_rest=sh_rest, _sync=sync, _vsplat_holder=holder, _c2w=cam_c2w,
-                _tile_order=frame_order if frame_order_valid else None, _post_bwd=post_bwd)
+                _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd)
             attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
             attrs["last_viewmat"], attrs["last_sh_degree"] = viewmat, deg
             # (the compositing node keeps the forward pass's per-tile costs: the loss launch sorts them for its backward)
             tile_cost = getattr(render.grad_fn, "tile_cost", None) if torch.is_grad_enabled() else None
             total, parts = _FusedImageLoss.apply(render, alpha, bg.contiguous(), gt_rgb, gt_depth, mask,
                                                  float(cfg.ssim_lambda), cfg.depth_lambda,
-                                                 holder if torch.is_grad_enabled() else None, self.num_points, tick,
-                                                 tile_cost, frame_order)
-            if frame_slot is not None and tile_cost is not None and float(cfg.ssim_lambda) > 0.0 \
+                                                 handover if torch.is_grad_enabled() else None, tick, tile_cost)
+            if frame_order is not None and tile_cost is not None and float(cfg.ssim_lambda) > 0.0 \
                     and os.environ.get("QED_STEP_PASSENGERS", "1") != "0":
-                frame_slot[1] = True              # (the buffer holds an order from here on, in stream order)
+                frame_order.valid = True          # (the buffer holds an order from here on, in stream order)
+            # on this route the camera's buffer is written by the loss launch only: a compositing backward that finds no
+            # order offered (ssim_lambda = 0, a second pass through a retained graph) sorts into a buffer of its own
+            handover.frame_order = None
         except BaseException:
             # the launch that would have advanced the optimiser's device step state did not happen: the optimiser
             # must tick for itself on the next step (otherwise its counter would be off by one from here on)

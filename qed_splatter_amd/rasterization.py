@@ -312,19 +312,16 @@ def _packed_vsplat(C, N, v_means2d, v_depths, v_conics, v_opac, v_rgb, dev) -> T
 class _Composite(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, conics, rgb, opac, depths, splats, flatten_ids, offsets, backgrounds, width, height,
-                tile_w, tile_h, channels, absgrad, vsplat_holder=None, post_background=None, grad_leaf=None,
-                tile_order=None):
+                tile_w, tile_h, channels, absgrad, handover=None, post_background=None, grad_leaf=None):
         lib = L.load()
         ctx.set_materialize_grads(False)
-        ctx.vsplat_holder = vsplat_holder
+        ctx.handover = handover                                  # (handover.Handover: what the loss launch does for the backward)
         ctx.grad_leaf = grad_leaf[0] if grad_leaf else None      # (in a list: not an autograd input)
-        # tile_order: a launch order for THIS kernel from an earlier frame of the same camera -- a tensor, or a camera's
-        # SLOT [tensor, valid] (model.py: _frame_orders): read while valid, and the backward pass below writes its own
-        # order into it for the next frame
-        ctx.order_slot = tile_order if isinstance(tile_order, list) else None
-        if ctx.order_slot is not None:
-            tile_order = ctx.order_slot[0] if ctx.order_slot[1] else None
         C, N = opac.shape
+        # the camera's launch order (handover.FrameOrder) from an earlier frame, for THIS kernel: read while valid; the
+        # backward pass below, or the loss launch, writes this frame's order into it for the next frame
+        order = handover.frame_order if handover is not None else None
+        tile_order = order.buffer if (order is not None and order.valid and order.fits(C * tile_w * tile_h)) else None
         dev = opac.device
         render = torch.empty(C, height, width, channels, dtype=torch.float32, device=dev)
         alpha = torch.empty(C, height, width, 1, dtype=torch.float32, device=dev)
@@ -351,8 +348,7 @@ class _Composite(torch.autograd.Function):
         L.check(lib.qed_composite_fwd(C, N, L.ptr(splats), L.ptr(flatten_ids), L.ptr(offsets), width, height, tile_w,
                                       tile_h, channels, L.ptr(bg), L.ptr(render), L.ptr(alpha), L.ptr(t_final),
                                       L.ptr(last_ids), L.ptr(tile_cost),
-                                      L.ptr(tile_order) if (tile_order is not None and tile_order.numel() == C * tile_w * tile_h + 1)
-                                      else None, C_byref(post), L.composite_launch_flags(), _stream()),
+                                      L.ptr(tile_order), C_byref(post), L.composite_launch_flags(), _stream()),
                 "qed_composite_fwd")
         ctx.tile_cost = tile_cost
         ctx.save_for_backward(splats, flatten_ids, offsets, alpha, last_ids, bg, render if post is not None else None, pbg,
@@ -396,26 +392,25 @@ class _Composite(torch.autograd.Function):
             v_alpha = _f32c(v_alpha, "v_alpha") if v_alpha is not None else torch.zeros(
                 C, height, width, 1, dtype=torch.float32, device=dev)
         R = L.VSPLAT_FLOATS
-        # the fused loss launch may already have zeroed an accumulator for this backward pass (model.fused_loss hands it
-        # over through the holder; taken once -- a second backward through a retained graph makes its own)
-        holder = ctx.vsplat_holder
-        handed = holder.pop() if holder else None
-        # (the fused loss launch hands over the zeroed accumulator and, when its SSIM pass carried the ordering job, the
-        # launch order of THIS forward pass's tile costs: a dict; older callers hand over the accumulator alone)
-        vsplat, order_ws = (handed.get("vsplat"), handed.get("order_ws")) if isinstance(handed, dict) else (handed, None)
-        if vsplat is None or vsplat.shape != (C * N, R) or vsplat.device != dev or vsplat.dtype != torch.float32:
+        # the loss launch may already have zeroed an accumulator for this backward pass and, when its SSIM pass carried the
+        # ordering job, sorted THIS forward pass's tile costs into the launch order (taken once -- a second backward
+        # through a retained graph makes its own)
+        n_tiles = C * tile_w * tile_h
+        handover = ctx.handover
+        vsplat, order_ws = handover.take(C, N, n_tiles, dev) if handover is not None else (None, None)
+        if vsplat is None:
             vsplat = torch.zeros(C * N, R, dtype=torch.float32, device=dev)
         tile_cost = ctx.tile_cost
         flags = L.composite_launch_flags()
-        if order_ws is not None and tile_cost is not None and order_ws.numel() == C * tile_w * tile_h + 1 and (flags & 3) == 0:
+        if order_ws is not None and tile_cost is not None and (flags & 3) == 0:
             flags |= L.CL_ORDER_READY
         elif tile_cost is not None:
-            slot = ctx.order_slot
-            if slot is not None and slot[0].numel() == C * tile_w * tile_h + 1 and (flags & 3) == 0:
-                order_ws = slot[0]              # the camera's persistent buffer: the next frame's forward pass reads it
-                slot[1] = True
+            slot = handover.frame_order if handover is not None else None
+            if slot is not None and slot.fits(n_tiles) and (flags & 3) == 0:
+                order_ws = slot.buffer          # the camera's persistent buffer: the next frame's forward pass reads it
+                slot.valid = True
             else:
-                order_ws = torch.empty(C * tile_w * tile_h + 1, dtype=torch.int32, device=dev)
+                order_ws = torch.empty(n_tiles + 1, dtype=torch.int32, device=dev)
         else:
             order_ws = None
         L.check(lib.qed_composite_bwd(C, N, L.ptr(splats), L.ptr(flatten_ids), L.ptr(offsets), width, height, tile_w,
@@ -439,7 +434,7 @@ class _Composite(torch.autograd.Function):
         if absgrad:
             # gsplat convention (absgrad=True at model.py:284): the densifier reads means2d.absgrad
             (leaf if leaf is not None else ctx.means2d_ref).absgrad = v3[..., 2:4]
-        return (v_means2d, v_conics, v_rgb_g, v_opac, v_depths) + (None,) * 14
+        return (v_means2d, v_conics, v_rgb_g, v_opac, v_depths) + (None,) * 13
 
 
 def C_byref(struct):
@@ -457,9 +452,9 @@ def rasterization(
     far_plane: float = 1e10, render_mode: str = "RGB", sh_degree: Optional[int] = None, sparse_grad: bool = False,
     absgrad: bool = False, rasterize_mode: str = "classic", radius_clip: float = 0.0, eps2d: float = 0.3,
     backgrounds: Optional[Tensor] = None, _flags: int = 0, _sh_rest: Optional[Tensor] = None,
-    _sync: bool = True, _vsplat_holder: Optional[list] = None, _c2w: Optional[Tuple[Tensor, Tensor]] = None,
+    _sync: bool = True, _handover=None, _c2w: Optional[Tuple[Tensor, Tensor]] = None,
     _post_background: Optional[Tensor] = None, _means2d_leaf: bool = False, _capture_slot=None,
-    _manual: Optional[list] = None, _lazy_sh=None, _tile_order: Optional[Tensor] = None, _post_bwd=None,
+    _manual: Optional[list] = None, _lazy_sh=None, _post_bwd=None,
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Same call surface as the reference's call (model.py:267-288).
 
@@ -541,10 +536,10 @@ def rasterization(
     if _means2d_leaf and wants_grad:
         means2d_out = means2d.detach().requires_grad_(True)
         grad_leaf = [means2d_out]
-    outs = _run_node(_Composite, _manual, (wants_grad,) * 5 + (False,) * 14,
+    outs = _run_node(_Composite, _manual, (wants_grad,) * 5 + (False,) * 13,
                      means2d, conics, rgb, opac, depths if channels == 4 else None, splats, flatten_ids, offsets,
-                     backgrounds, int(width), int(height), tile_w, tile_h, channels, bool(absgrad), _vsplat_holder,
-                     _post_background, grad_leaf, _tile_order)
+                     backgrounds, int(width), int(height), tile_w, tile_h, channels, bool(absgrad), _handover,
+                     _post_background, grad_leaf)
     render, alpha, last_ids = outs[:3]
     info = {
         "camera_ids": None, "gaussian_ids": None,

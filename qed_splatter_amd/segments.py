@@ -35,6 +35,7 @@ from torch import Tensor
 
 from . import _lib as L
 from .binning import _workspace, pinned_slot
+from .handover import Handover
 from .rasterization import manual_backward
 
 
@@ -87,9 +88,8 @@ class _SegmentFn(torch.autograd.Function):
                     m_._materialise_sh_grads()      # (a compact SH gradient waiting there is completed before it is copied)
                 _RAW_GRAD.__set__(p, old.clone())
         # the accumulator K7 adds into: zeroed by the loss's own backward launch when that was _ImageLosses (StepContext)
-        if not (seg.holder and seg.holder[0] is seg.vsplat):
+        if not seg.handover.take_static_zeroed():
             seg.vsplat.zero_()
-        del seg.holder[:]
         graph.replay()
         owner = getattr(seg, "lazy_owner", None)
         if owner is not None:
@@ -115,7 +115,7 @@ class _SegmentFn(torch.autograd.Function):
 
 class OutputsSegment:
     """The captured form of one shape of ``get_outputs`` (see the module docstring).  ``render_fn(c2w, intr, background,
-    holder, capture_slot) -> (render, alpha, info)`` makes the eager ``rasterization(...)`` call of get_outputs on the
+    handover, capture_slot) -> (render, alpha, info)`` makes the eager ``rasterization(...)`` call of get_outputs on the
     tensors it is given."""
 
     def __init__(self, device, params: List[Tensor], render_fn: Callable, shape_key: Tuple,
@@ -126,7 +126,7 @@ class OutputsSegment:
         self.render_fn = render_fn
         self.shape_key = shape_key                # the workspace's calibration key of this shape: ((W, H), N, C)
         self.generation = 0
-        self.holder: list = []
+        self.handover = Handover()                # (what the loss launch does for the backward replay; filled in by capture)
         self._bwd: Dict[bool, Tuple] = {}
         words, address, self._keep = pinned_slot()    # what every replay's binning stores {M, overflow, watchdog} into
         self.slot = (words, address)
@@ -141,7 +141,7 @@ class OutputsSegment:
         # thread_local: HIP calls of other threads (a viewer's eval render, RCCL's watchdog) must not break the capture
         self.manual: list = []                    # the two nodes' contexts: the call runs without the autograd engine
         with torch.cuda.graph(self.g_fwd, capture_error_mode="thread_local"):
-            render, alpha, info = self.render_fn(self.c2w, self.intr, self.bg, self.holder, self.slot, manual=self.manual)
+            render, alpha, info = self.render_fn(self.c2w, self.intr, self.bg, self.handover, self.slot, manual=self.manual)
         self.render, self.alpha, self.info = render, alpha, info
         self.rgb = info.pop("post_rgb")
         self.depth = info.pop("post_depth")
@@ -150,6 +150,10 @@ class OutputsSegment:
         self.v_depth = torch.zeros_like(self.depth) if self.depth is not None else None
         self.v_alpha = None
         self.vsplat = torch.zeros(info["radii"].numel(), L.VSPLAT_FLOATS, dtype=torch.float32, device=dev)
+        # the loss's backward launch writes / zeroes THESE instead of fresh buffers (v_rgb [H,W,3], v_depth [H,W,1] | None)
+        h = self.handover
+        h.rows, h.vsplat = self.vsplat.shape[0], self.vsplat
+        h.v_rgb, h.v_depth = self.v_rgb[0], self.v_depth[0] if self.v_depth is not None else None
         self.backward_graph(False)                # the usual backward (nothing downstream used `accumulation`)
 
     def backward_graph(self, with_alpha: bool):
@@ -163,10 +167,9 @@ class OutputsSegment:
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self.g_fwd.pool(), capture_error_mode="thread_local"):
-            self.holder[:] = [self.vsplat]        # _Composite.backward takes its accumulator from the holder
+            self.handover.offer(vsplat=self.vsplat)   # _Composite.backward takes its accumulator from the hand-over
             v_means, v_quats, v_scales, v_opac, v_dc, v_rest, _ = manual_backward(
                 self.manual, None, self.v_alpha if with_alpha else None, self.v_rgb, self.v_depth)
-        del self.holder[:]
         by_name = dict(means=v_means, scales=v_scales, quats=v_quats, opacities=v_opac, features_dc=v_dc, features_rest=v_rest)
         grads = tuple((by_name[n].view(p.shape) if (by_name[n] is not None and p.requires_grad) else None)
                       for n, p in zip(self.param_names, self.params))
@@ -177,7 +180,7 @@ class OutputsSegment:
 
     # ---- replay ----------------------------------------------------------------------------------------------
     def run(self, c2w: Tensor, intr: Tensor, background: Tensor):
-        """One training-step forward: (rgb [1,H,W,3], alpha [1,H,W,1], depth [1,H,W,1] | None, info, holder, grad buffers)."""
+        """One training-step forward: (rgb [1,H,W,3], alpha [1,H,W,1], depth [1,H,W,1] | None)."""
         ws = _workspace(self.device)
         # the step's camera / background into the static buffers the graph reads: ONE multi-tensor copy launch, and none
         # for a source that is the very tensor (same object, same version) copied last time
@@ -192,7 +195,7 @@ class OutputsSegment:
         if dst:
             torch._foreach_copy_(dst, src)
         self.slot[0][0] = -1                      # (the previous replay's word was read by poll_pending before this call)
-        del self.holder[:]
+        self.handover.reset()
         outs = _SegmentFn.apply(self, *self.params)
         ws.arm_pending(self.slot[0], self.shape_key)
         rgb, alpha = outs[0], outs[1]

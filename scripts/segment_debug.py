@@ -28,10 +28,11 @@ print("eager steps done", flush=True)
 mode = os.environ.get("QED_SEG_MODE", "thread_local")
 from qed_splatter_amd.rasterization import rasterization  # noqa: E402
 from qed_splatter_amd import _lib as L  # noqa: E402
+from qed_splatter_amd.handover import Handover  # noqa: E402
 c2w = cam.camera_to_worlds.clone()
 intr = cam.intrinsics_fxfycxcy().clone()
 bg = torch.zeros(3, device=dev)
-holder = []
+handover = Handover()
 host = torch.zeros(4, dtype=torch.int32).pin_memory()
 slot = (host.numpy(), host.data_ptr())
 g1 = torch.cuda.CUDAGraph()
@@ -44,7 +45,7 @@ with torch.cuda.graph(g1, capture_error_mode=mode):
             means=m.means, quats=m.quats, scales=m.scales, opacities=m.opacities, colors=m.features_dc, viewmats=vm, Ks=Ks,
             width=w, height=h, render_mode="RGB+D", sh_degree=3, absgrad=True,
             _flags=L.F_LOG_SCALES | L.F_LOGIT_OPAC | L.F_TIGHT_TILES, _sh_rest=m.features_rest, _sync=False, _c2w=(c2w, intr),
-            _post_background=bg, _vsplat_holder=holder, _means2d_leaf=True, _capture_slot=slot)
+            _post_background=bg, _handover=handover, _means2d_leaf=True, _capture_slot=slot)
 print("forward captured", flush=True)
 rgb, depth = info["post_rgb"], info["post_depth"]
 v_rgb, v_depth = torch.ones_like(rgb), torch.ones_like(depth)
@@ -54,7 +55,7 @@ g2 = torch.cuda.CUDAGraph()
 torch.cuda.synchronize()
 print("capturing backward", flush=True)
 with torch.cuda.graph(g2, pool=g1.pool(), capture_error_mode=mode):
-    holder[:] = [vsplat]
+    handover.offer(vsplat=vsplat)
     grads = torch.autograd.grad([rgb, depth], params, [v_rgb, v_depth], retain_graph=os.environ.get("QED_SEG_RETAIN", "1") == "1",
                                 allow_unused=True)
 print("backward captured", flush=True)

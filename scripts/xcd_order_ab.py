@@ -28,7 +28,7 @@ lib = L.load()
 out = model.fused_loss(cam, batch, frame_key=0)
 node = out["loss"].grad_fn.next_functions[0][0]
 slot = model._frame_orders[(0, h, w)]
-plain = slot[0].clone()
+plain = slot.buffer.clone()
 T = plain.numel() - 1
 n_split = int(plain[T])
 cost = node.tile_cost.sum(1).cpu()
@@ -79,9 +79,9 @@ def timed(which, reps=30):
         for _ in range(reps):
             for p in model.parameters():
                 p.grad = None
-            slot[0].copy_(which)                          # the forward pass reads it ...
+            slot.buffer.copy_(which)                          # the forward pass reads it ...
             o = model.fused_loss(cam, batch, frame_key=0)
-            slot[0].copy_(which)                          # ... and the backward pass (the loss launch rewrote it)
+            slot.buffer.copy_(which)                          # ... and the backward pass (the loss launch rewrote it)
             model.backward_fused(o)
     finally:
         for k, fn in saved.items():

@@ -1361,7 +1361,43 @@ def test_camera_index_keeps_a_launch_order_per_camera_and_changes_no_result(cuda
     for rep in range(3):
         rgb1, l1, g1 = step(cam)
         slot = m._frame_orders[(3, 208, 320)]
-        assert slot[1] and sorted(slot[0][:T].cpu().tolist()) == list(range(T))       # written by the backward pass
+        assert slot.valid and sorted(slot.buffer[:T].cpu().tolist()) == list(range(T))   # written by the backward pass
         assert torch.equal(rgb1, rgb0) and l1 == l0                                   # (rep >= 1: the forward pass used it)
         for k in PARAM_NAMES:
             assert_close(g1[k], g0[k], 2e-5, f"rep {rep}: grad {k}")
+
+
+@pytest.mark.parametrize("route", ["fused_loss", "get_loss_dict"])
+def test_second_backward_through_a_retained_graph_fills_its_own_accumulator_and_order(cuda, route):
+    """What the loss launch hands the compositing backward (a zeroed accumulator; on the fused route the launch order as
+    well) is taken ONCE: a second backward pass through the same graph finds no order offered and makes its own, and the
+    gradients that wait in the fields become twice those of a fresh model's single pass."""
+    names = ("means", "scales", "quats", "opacities", "features_dc")
+    sc = scene(3000, 160, 112, seed=12)
+
+    def forward(m, cam, batch):
+        """(loss, compositing node) of one step on this route."""
+        if route == "fused_loss":
+            loss = m.fused_loss(cam, batch)["loss"]
+            return loss, loss.grad_fn.next_functions[0][0]
+        out = m.get_outputs(cam)
+        return sum(m.get_loss_dict(out, batch).values()), out["rgb"].grad_fn.next_functions[0][0]
+
+    m, cam, batch = _model(sc, cuda, graph_segments=False)
+    m.train()
+    forward(m, cam, batch)[0].backward()
+    once = {k: m.gauss_params[k].grad.detach().clone() for k in names}
+
+    m, cam, batch = _model(sc, cuda, graph_segments=False)
+    m.train()
+    loss, node = forward(m, cam, batch)
+    handed = node.handover.offered_order
+    assert (handed is not None) == (route == "fused_loss")
+    loss.backward(retain_graph=True)
+    first = node.order_ws
+    assert first is not None and (handed is None or first is handed)
+    assert node.handover.offered_vsplat is None and node.handover.offered_order is None    # taken: nothing left
+    loss.backward(retain_graph=True)
+    assert node.order_ws is not None and node.order_ws is not first
+    for k in names:
+        assert_close(m.gauss_params[k].grad, 2.0 * once[k].double().cpu(), 2e-5, f"{route}: grad {k} after two passes")

@@ -1668,9 +1668,8 @@ def test_fused_step_hands_the_backward_its_tile_order(cuda):
     model.step = 3
     out = model.fused_loss(cam, batch)
     node = out["loss"].grad_fn.next_functions[0][0]
-    holder = node.vsplat_holder
-    assert holder and isinstance(holder[0], dict) and holder[0]["order_ws"] is not None
-    handed = holder[0]["order_ws"]
+    handed = node.handover.offered_order
+    assert handed is not None
     model.backward_fused(out)
     assert node.order_ws is handed                                     # taken over, not recomputed
     T = node.tile_cost.shape[0]
@@ -1688,12 +1687,12 @@ def test_fused_step_hands_the_backward_its_tile_order(cuda):
         o2 = model.fused_loss(cam, batch, frame_key="cam 7")
         slot = model._frame_orders[("cam 7", h, w)]
         node2 = o2["loss"].grad_fn.next_functions[0][0]
-        assert node2.vsplat_holder[0]["order_ws"] is slot[0] and slot[1]
+        assert node2.handover.offered_order is slot.buffer and slot.valid
         model.backward_fused(o2)
         assert float(o2["loss"]) == loss_ref
         for k, r in ref.items():
             assert_close(model.gauss_params[k].grad, r, 2e-5, f"frame_key rep {rep}: grad {k}")
-    assert sorted(slot[0][:T].cpu().tolist()) == list(range(T))
+    assert sorted(slot.buffer[:T].cpu().tolist()) == list(range(T))
 
 
 @pytest.mark.parametrize("tight", [True, False])

@@ -61,12 +61,13 @@ def test_step_context_hands_everything_out_once_and_only_to_its_own_outputs():
     `owns` is an identity test on outputs["rgb"]."""
     import torch
 
+    from qed_splatter_amd.handover import Handover
     from qed_splatter_amd.model import StepContext
     ctx = StepContext()
     rgb = torch.zeros(4, 5, 3)
     assert not ctx.owns({"rgb": rgb})                              # nothing bound yet
-    holder: list = []
-    ctx.bind(rgb, holder, 7)
+    handover = Handover(7)
+    ctx.bind(rgb, handover)
     assert ctx.owns({"rgb": rgb}) and not ctx.owns({"rgb": rgb.clone()}) and not ctx.owns({})
     # conversions
     calls = []
@@ -88,17 +89,63 @@ def test_step_context_hands_everything_out_once_and_only_to_its_own_outputs():
     # one-shot hand-overs
     ctx.ssim = {"key": 1}
     assert ctx.take_ssim() == {"key": 1} and ctx.take_ssim() is None
-    assert ctx.take_grad_buffers() is None                         # no captured segment behind these outputs
-    acc = ctx.take_accumulator()
-    assert acc[0] is holder and acc[1] == 7 and acc[2] is None and ctx.take_accumulator() is None
+    acc = ctx.handover
+    assert acc is handover and not acc.claim_grad_buffers()        # no captured segment behind these outputs
+    assert acc.claim_accumulator() and acc.rows == 7 and acc.vsplat is None and not acc.claim_accumulator()
+    assert acc.accumulator("cpu").shape == (7, 16)                 # (a fresh one for the claimant to zero)
     # with a segment's static buffers
-    ctx2 = StepContext()
-    ctx2.bind(rgb, holder, 7)
     v_rgb, v_depth, vsplat = torch.zeros(4, 5, 3), torch.zeros(4, 5, 1), torch.zeros(7, 16)
-    ctx2.static = (v_rgb, v_depth, vsplat)
-    got = ctx2.take_grad_buffers()
-    assert got[0] is v_rgb and got[1] is v_depth and ctx2.take_grad_buffers() is None
-    assert ctx2.take_accumulator()[2] is vsplat                    # the accumulator survives the gradient buffers' hand-over
+    ctx2 = StepContext()
+    ctx2.bind(rgb, Handover(7, None, vsplat, v_rgb, v_depth))
+    got = ctx2.handover
+    assert got.claim_grad_buffers() and got.v_rgb is v_rgb and got.v_depth is v_depth and not got.claim_grad_buffers()
+    assert got.claim_accumulator() and got.accumulator("cpu") is vsplat    # it survives the gradient buffers' hand-over
+
+
+def test_handover_is_taken_once_and_only_when_it_fits_the_launch():
+    """handover.Handover (CPU: plain tensors): what the loss launch offers is returned by the compositing backward's take as
+    the very objects, once; a buffer of the wrong shape, dtype or length is not returned (the backward then makes its own);
+    each claim is granted once; a segment's reset re-arms offer and claims; a camera's FrameOrder starts invalid."""
+    import torch
+
+    from qed_splatter_amd.handover import FrameOrder, Handover
+    C, N, tiles, cpu = 1, 7, 12, torch.device("cpu")
+    vsplat, order = torch.zeros(C * N, 16), torch.zeros(tiles + 1, dtype=torch.int32)
+    h = Handover(C * N)
+    assert h.take(C, N, tiles, cpu) == (None, None)                # nothing offered yet
+    h.offer(vsplat, order)
+    assert h.offered_vsplat is vsplat and h.offered_order is order
+    got = h.take(C, N, tiles, cpu)
+    assert got[0] is vsplat and got[1] is order
+    assert h.offered_vsplat is None and h.offered_order is None and h.take(C, N, tiles, cpu) == (None, None)
+    h.offer(vsplat=vsplat)                                         # (get_loss_dict's launch: no order)
+    got = h.take(C, N, tiles, cpu)
+    assert got[0] is vsplat and got[1] is None
+    # unfit buffers: one row short, float64, another row width, on another device; an order one element short
+    for bad in (torch.zeros(C * N - 1, 16), torch.zeros(C * N, 16, dtype=torch.float64), torch.zeros(C * N, 12),
+                torch.zeros(C * N, 16, device="meta")):
+        h.offer(bad, order)
+        got = h.take(C, N, tiles, cpu)
+        assert got[0] is None and got[1] is order and h.offered_vsplat is None
+    h.offer(vsplat, torch.zeros(tiles, dtype=torch.int32))
+    got = h.take(C, N, tiles, cpu)
+    assert got[0] is vsplat and got[1] is None
+    # claims, and a segment's replay
+    assert h.claim_accumulator() and not h.claim_accumulator() and not h.claim_grad_buffers()
+    assert not Handover().claim_accumulator()                      # no rows: nothing to zero
+    static, v_rgb = torch.zeros(C * N, 16), torch.zeros(4, 5, 3)
+    s = Handover(C * N, None, static, v_rgb, None)
+    assert s.claim_accumulator() and s.claim_grad_buffers() and not s.claim_accumulator() and not s.claim_grad_buffers()
+    s.offer(vsplat=s.accumulator(cpu))
+    assert s.take_static_zeroed() and not s.take_static_zeroed()   # the static accumulator was the one zeroed; asked once
+    s.offer(vsplat=vsplat)
+    assert not s.take_static_zeroed() and s.offered_vsplat is None # another buffer: the segment zeroes its own
+    s.offer(vsplat=static)
+    s.reset()
+    assert s.offered_vsplat is None and s.claim_accumulator() and s.claim_grad_buffers()
+    # the camera's buffer
+    fo = FrameOrder(order)
+    assert fo.buffer is order and not fo.valid and fo.fits(tiles) and not fo.fits(tiles + 1)
 
 
 def test_lazy_sh_gradient_parameters_complete_the_gradients_for_every_python_reader(monkeypatch):
