@@ -883,6 +883,39 @@ int qed_present_frame(int32_t height, int32_t width, const float* rgb, const flo
                       float inv_depth_unit, const float* range_dev, float near, float far, const uint8_t* lut,
                       uint8_t* out_rgb8, uint16_t* out_depth16, uint8_t* out_depthmap8, uint8_t* out_alpha8, void* stream);
 
+/* ---- camera pose optimiser: Nerfstudio's CameraOptimizer, mode SO3xR3 (csrc/pose.hip) -------------------------------
+ * pose_adjustment[n_rows, 6], one row per training camera: columns 0:3 the translation d, 3:6 the rotation vector w.
+ *   a = sqrt(max(|w|^2, 1e-4));  R = I + (sin a / a) K + ((1 - cos a) / a^2) K^2,  K = skew(w)
+ *   c2w_opt[3,4] = c2w[3,4] [[R, d], [0, 0, 0, 1]]            (R_opt = R0 R, t_opt = R0 d + t0)
+ * Below the clamp (|w| < 0.01) the angle is held at 0.01 and passes no gradient, as upstream.  sinf / cosf are the precise
+ * ones.  Camera c of a call uses row rows[c] (device int32) or, with rows == NULL, row0 + c (a batch of all rows: C =
+ * n_rows, row0 = 0); a rows[c] outside [0, n_rows) gives NaN outputs.  The regulariser is
+ *   trans_l2_penalty * mean_rows |d| + rot_l2_penalty * mean_rows |w|     (gradient 0 at a zero row).
+ *
+ * qed_pose_apply: c2w_out[C,3,4] from c2w_in[C,3,4], one launch; reg_out (device float, may be NULL) receives the
+ *   regulariser's value over ALL rows.
+ * qed_pose_apply_bwd: v_rows[C,6] = the gradient of each camera's row for the gradient v_c2w[C,3,4] of c2w_out.
+ * qed_pose_step: everything a training step does for the poses after qed_project_bwd, in one one-workgroup launch.
+ *   v_viewmats[1,4,4] is the buffer qed_project_bwd accumulated for the view matrix rendered from qed_pose_apply's result
+ *   for row `row` of c2w_in[1,3,4]; it is read and ZEROED for the next step.  The gradient goes back through get_viewmat
+ *   (flip of the y / z columns, rigid inverse: the chain rule of those statements) and through the composition to the row;
+ *   the regulariser's gradient is added to every row; torch.optim.Adam's update (no weight decay, no amsgrad; `step`
+ *   1-based, betas doubles as for qed_adam_step) runs over all n_rows x 6 elements with rate lr.  raw_grad[n_rows,6]
+ *   (may be NULL) receives the gradient the update used, reg_out (may be NULL) the regulariser's value BEFORE the update.
+ *   row = -1: no camera this step (c2w_in may be NULL).  skip_flag as qed_adam_step's: non-zero -> the buffer is zeroed,
+ *   nothing else is written but reg_out.
+ * Refused on the host: null buffers, n_rows outside [1, 2^24), rows outside pose_adjustment, step < 1.  No allocation, no
+ * sync. */
+int qed_pose_apply(int32_t C, int32_t n_rows, const float* pose_adjustment, const int32_t* rows, int32_t row0,
+                   const float* c2w_in, float* c2w_out, float trans_l2_penalty, float rot_l2_penalty, float* reg_out,
+                   void* stream);
+int qed_pose_apply_bwd(int32_t C, int32_t n_rows, const float* pose_adjustment, const int32_t* rows, int32_t row0,
+                       const float* c2w_in, const float* v_c2w, float* v_rows, void* stream);
+int qed_pose_step(int32_t n_rows, int32_t row, float* pose_adjustment, float* exp_avg, float* exp_avg_sq,
+                  const float* c2w_in, float* v_viewmats, float trans_l2_penalty, float rot_l2_penalty, float lr,
+                  double beta1, double beta2, float eps, int32_t step, float* raw_grad, float* reg_out,
+                  const int32_t* skip_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

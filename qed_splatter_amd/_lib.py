@@ -108,6 +108,9 @@ SIGNATURES = {
     "qed_unpack_gaussians": (C.c_int, [_I, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qed_present_range": (C.c_int, [_I, _I, _P, _P, _P, _P]),
     "qed_present_frame": (C.c_int, [_I, _I, _P, _P, _P, _F, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "qed_pose_apply": (C.c_int, [_I, _I, _P, _P, _I, _P, _P, _F, _F, _P, _P]),
+    "qed_pose_apply_bwd": (C.c_int, [_I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "qed_pose_step": (C.c_int, [_I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _D, _D, _F, _I, _P, _P, _P, _P]),
 }
 
 class Post(C.Structure):

@@ -79,6 +79,10 @@ class DataparserOutputs:
     src_intrinsics: Optional[np.ndarray] = None
     distortion_params: Optional[np.ndarray] = None
     camera_models: Optional[List[Optional[str]]] = None
+    # camera_to_worlds [n,3,4] and dataparser_transform [3,4] before their rounding to float32: what maps poses back to the
+    # dataset's own frame (train.py --save-poses) without the float32 rounding of the translations
+    camera_to_worlds_f64: Optional[np.ndarray] = None
+    dataparser_transform_f64: Optional[np.ndarray] = None
 
     def __len__(self) -> int:
         return len(self.image_filenames)
@@ -219,4 +223,5 @@ def parse_dataset(data_dir, config: Optional[DataparserConfig] = None, verbose: 
         n_skipped=n_skipped, ply_file_path=ply, config=cfg,
         src_intrinsics=np.asarray(src_intr, dtype=np.float64) if cfg.undistort else None,
         distortion_params=np.asarray(dists, dtype=np.float64) if cfg.undistort else None,
-        camera_models=models if cfg.undistort else None)
+        camera_models=models if cfg.undistort else None,
+        camera_to_worlds_f64=np.array(c2w, dtype=np.float64), dataparser_transform_f64=np.array(transform, dtype=np.float64))

@@ -1006,6 +1006,9 @@ class QEDSplatterModel(nn.Module):
         if self.training and cfg.use_bilateral_grid and self.bil_grids is not None:      # the parent's tv_loss
             from .bilagrid import total_variation_loss
             out["tv_loss"] = 10 * total_variation_loss(self.bil_grids.grids)
+        pose_losses = getattr(self.camera_optimizer, "get_loss_dict", None)
+        if self.training and pose_losses is not None:                        # the parent's camera_opt_regularizer
+            pose_losses(out)
         out["depth_loss"] = depth
         return out
 
@@ -1118,7 +1121,7 @@ class QEDSplatterModel(nn.Module):
 
     def fused_loss(self, camera, batch, background: Optional[Tensor] = None, sync: bool = True,
                    compact_sh_grad: bool = False, optimizer: Optional["FlatAdam"] = None,
-                   frame_key=None) -> Dict[str, Tensor]:
+                   frame_key=None, camera_optimizer=None, cam_idx=None) -> Dict[str, Tensor]:
         """Forward + K8 fused loss.  Returns {"loss", "main_loss", "depth_loss"}: ``loss`` = main + depth is
         the differentiable total (call ``.backward()`` on it as is: the kernel already wrote its gradient
         for an upstream gradient of 1); the two parts are detached views for logging.  Numerically the
@@ -1129,7 +1132,14 @@ class QEDSplatterModel(nn.Module):
         compositing backward (from this frame's per-tile work counts) is what the NEXT frame under the same key hands
         its compositing FORWARD kernel, which cannot know its costs in advance (heaviest tiles first: 114-117 us against
         122-126 at config B).  A scheduling hint only: images and gradients do not depend on it.  Leave it None when
-        consecutive frames come from unrelated cameras and no index is at hand."""
+        consecutive frames come from unrelated cameras and no index is at hand.
+
+        ``camera_optimizer`` (a camera_optimizer.CameraOptimizer; None or mode "off": nothing changes): in training the
+        frame is rendered from the camera's ADJUSTED pose -- one launch, then the projection kernel's camera-to-world path
+        as for any other pose -- and the projection backward leaves the view matrix's gradient in the optimiser's buffer:
+        follow ``backward_fused`` with ``camera_optimizer.step_fused(step)``.  The camera's row is ``cam_idx`` (the
+        datamanager's ``batch["image_idx"]``), else ``camera.metadata["cam_idx"]``.  The regulariser's value is returned
+        as ``camera_opt_regularizer`` and is part of ``loss`` (its gradient is qed_pose_step's business)."""
         assert camera.shape[0] == 1, "Only one camera at a time"
         if self.training and self.config.use_bilateral_grid and self.bil_grids is not None:
             raise NotImplementedError(
@@ -1140,7 +1150,21 @@ class QEDSplatterModel(nn.Module):
         cfg = self.config
         self.__dict__["_step"] = StepContext()   # (conversions of the batch are shared within a step, never across steps)
         attrs = self.__dict__            # (plain attributes, as in get_outputs)
-        viewmat, K, cam_c2w, W, H = self._camera_inputs(camera, camera.camera_to_worlds)
+        pose_opt = camera_optimizer if (camera_optimizer is not None and camera_optimizer.active and self.training) else None
+        attrs["pose_optimizer"] = pose_opt       # (parallel.py refuses a data-parallel step behind it)
+        c2w, pose_reg = camera.camera_to_worlds, None
+        if pose_opt is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise NotImplementedError("a camera optimiser inside a captured step (graph.py, segments.py): the camera's "
+                                          "row and the learning rate are host arguments of its launches")
+            idx = pose_opt.camera_index(camera, cam_idx)
+            if idx is None:
+                raise ValueError("fused_loss(camera_optimizer=...) needs the camera's training index: cam_idx=... or "
+                                 "camera.metadata['cam_idx']")
+            c2w, pose_reg = pose_opt.begin_fused(c2w, idx)           # qed_pose_apply: the one extra forward launch
+        viewmat, K, cam_c2w, W, H = self._camera_inputs(camera, c2w)
+        if pose_opt is not None and cam_c2w is None:
+            raise L.QedSplatError("fused_loss(camera_optimizer=...) needs a camera with intrinsics_fxfycxcy (PinholeCameras)")
         deg, colors, sh_rest, color_flags = self._color_inputs(self.features_dc, self.features_rest)
         flags = self._base_flags(W, H) | color_flags
         if compact_sh_grad and cfg.sh_degree > 0:
@@ -1174,7 +1198,8 @@ class QEDSplatterModel(nn.Module):
             render, alpha, info = self._rasterize(
                 means=self.means, quats=self.quats, scales=self.scales, opacities=self.opacities, colors=colors,
                 viewmats=viewmat, Ks=K, width=W, height=H, render_mode="RGB+D", sh_degree=deg, _flags=flags,
-                _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd)
+                _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd,
+                _pose_grad=pose_opt.pose_grad if (pose_opt is not None and torch.is_grad_enabled()) else None)
             attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
             attrs["last_viewmat"], attrs["last_sh_degree"] = viewmat, deg
             # (the compositing node keeps the forward pass's per-tile costs: the loss launch sorts them for its backward)
@@ -1195,8 +1220,12 @@ class QEDSplatterModel(nn.Module):
                 optimizer.drop_tick()
             raise
         if mcmc_vals is None:
-            return {"loss": total, "main_loss": parts[0], "depth_loss": parts[1]}
-        out = {"loss": total + mcmc_vals[2], "main_loss": parts[0]}
-        self._put_mcmc_regs(out, lo, ls, mcmc_vals)
-        out["depth_loss"] = parts[1]
+            out = {"loss": total, "main_loss": parts[0], "depth_loss": parts[1]}
+        else:
+            out = {"loss": total + mcmc_vals[2], "main_loss": parts[0]}
+            self._put_mcmc_regs(out, lo, ls, mcmc_vals)
+            out["depth_loss"] = parts[1]
+        if pose_reg is not None:
+            out["loss"] = out["loss"] + pose_reg
+            out["camera_opt_regularizer"] = pose_reg
         return out

@@ -25,6 +25,7 @@ def allreduce_flat_grad(model, world_size: int, group=None) -> torch.Tensor:
     The gradients already alias one contiguous allocation (``model.flat_grad()``), so nothing is
     packed or copied.  Loss is normalised by the global camera count, i.e. gradients are averaged.
     """
+    _refuse_camera_optimizer(model, "allreduce_flat_grad")
     g = model.flat_grad()
     if g is None:
         raise RuntimeError("no gradients to reduce: call backward() first")
@@ -39,6 +40,14 @@ def allreduce_flat_grad(model, world_size: int, group=None) -> torch.Tensor:
         dist.all_reduce(g, op=dist.ReduceOp.SUM, group=group)
         g.mul_(1.0 / max(world_size, 1))
     return g
+
+
+def _refuse_camera_optimizer(model, who: str) -> None:
+    """A data-parallel step behind fused_loss(camera_optimizer=...): every rank renders another camera and would step
+    another row of pose_adjustment from its own gradient; the rows and their Adam state are not exchanged."""
+    if model.__dict__.get("pose_optimizer") is not None:
+        raise NotImplementedError(f"{who}: the last fused_loss ran with a camera optimiser; pose optimisation under data "
+                                  "parallelism is not supported")
 
 
 def _refuse_compact(model, who: str) -> None:
@@ -66,6 +75,7 @@ def exchange_grads_compact(model, world_size: int, group=None, views=None, rebui
     ``FlatAdam.step(fused_sh=True)``, which evaluates the coefficient gradients inside the optimiser pass
     (the message buffers are persistent, so a captured Adam graph keeps reading the right memory)."""
     from . import _lib as L
+    _refuse_camera_optimizer(model, "exchange_grads_compact")
     g = model.flat_grad()
     if g is None:
         raise RuntimeError("no gradients to exchange: call backward() first")
@@ -344,6 +354,7 @@ def exchange_grads_compact_begin(model, world_size: int, group=None, prepared: b
     Gaussians this rank's camera saw (index + colour gradient, at most ``sparse_cap`` of them); ``wait_views()`` scatters
     the gathered lists into the dense rows the optimiser reads.  Same ``model.sh_views``, same update as the dense message
     (a Gaussian a rank did not see has a zero colour gradient there either way)."""
+    _refuse_camera_optimizer(model, "exchange_grads_compact_begin")
     if sparse_cap is not None:
         return _exchange_sparse_begin(model, world_size, group, int(sparse_cap), visible, fold)
     g = model.flat_grad()
@@ -491,6 +502,7 @@ def allreduce_and_step(model, optimizer, world_size: int, n_chunks: int = 4, gro
     hiding the ~0.13 ms Adam pass of config B is worth it only if four 30 MB all-reduces cost less than
     0.13 ms more than one 118 MB all-reduce.  bench.py keeps the single collective (not measurable on the
     one-GPU development box); ``scripts/dp_rehearsal.py`` checks the equivalence on two ranks."""
+    _refuse_camera_optimizer(model, "allreduce_and_step")
     g = model.flat_grad()
     if g is None:
         raise RuntimeError("no gradients to reduce: call backward() first")

@@ -136,10 +136,11 @@ class _ProjectSH(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, sh0, shN, viewmats, Ks, width, height, tile_w, tile_h,
                 sh_degree, flags, eps2d, near_plane, far_plane, radius_clip, c2w=None, intr=None, lazy_sh=None,
-                post_bwd=None):
+                post_bwd=None, pose_grad=None):
         lib = L.load()
         ctx.lazy_sh = lazy_sh
         ctx.post_bwd = post_bwd
+        ctx.pose_grad = pose_grad
         # undefined output gradients arrive as None instead of freshly zero-filled tensors (autograd would
         # otherwise fill one per output per step, the 24 MB splat record included)
         ctx.set_materialize_grads(False)
@@ -159,6 +160,10 @@ class _ProjectSH(torch.autograd.Function):
             assert intr.dtype == torch.float32 and intr.is_contiguous() and tuple(intr.shape) == (C, 4)
             assert not viewmats.requires_grad, "no gradient reaches camera-to-world matrices through this path"
             cam_in, flags = (c2w, intr), flags | L.F_CAMERA_C2W
+        if pose_grad is not None:
+            # rasterization(_pose_grad=...): the backward pass ADDS the view matrices' gradient to the caller's buffer
+            assert pose_grad.dtype == torch.float32 and pose_grad.is_contiguous() and tuple(pose_grad.shape) == (C, 4, 4) \
+                and pose_grad.device == dev
         sh0_stride = sh0.stride(0) if sh0.dim() > 1 else 3
         # a [N,K,3] colours tensor is passed as (colors, 3K, colors + 3, 3K) -- no copy
         if sh0.dim() == 3:
@@ -244,6 +249,9 @@ class _ProjectSH(torch.autograd.Function):
             shN_ptr = L.ptr(shN)
         del flat                                # only the views stay referenced -> autograd can adopt them
         v_viewmats = None
+        # (_pose_grad: a persistent, zeroed buffer of the caller's takes the view matrices' gradient -- the camera optimiser
+        # of the fused route, whose pose reaches the kernel as a camera-to-world matrix that does not require grad)
+        pose_grad = getattr(ctx, "pose_grad", None)
         if ctx.needs_input_grad[6]:
             v_viewmats = torch.zeros_like(viewmats)
         # QED_F_SH_GRAD_COMPACT asked for by a caller that keeps the Gaussians' SH gradients in compact form until somebody
@@ -260,12 +268,13 @@ class _ProjectSH(torch.autograd.Function):
             N, C, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(opacities), L.ptr(sh0), sh0_stride, shN_ptr,
             shN_stride, sh_degree, L.ptr(viewmats), L.ptr(Ks), width, height, eps2d, flags, L.ptr(radii),
             L.ptr(vsplat), L.ptr(v_means), L.ptr(v_quats), L.ptr(v_scales), L.ptr(v_opacities), v_sh0_ptr,
-            v_sh0_stride, v_shN_ptr, v_shN_stride, L.ptr(v_viewmats), L.ptr(sh_jac), _stream()), "qed_project_bwd")
+            v_sh0_stride, v_shN_ptr, v_shN_stride, L.ptr(v_viewmats if v_viewmats is not None else pose_grad), L.ptr(sh_jac),
+            _stream()), "qed_project_bwd")
         post = getattr(ctx, "post_bwd", None)
         if post is not None:
             post(v_scales, v_opacities)         # terms of the loss that read the parameters directly (model: MCMC)
         v_opacities = v_opacities.view(ctx.opac_shape)
-        return (v_means, v_quats, v_scales, v_opacities, v_sh0, v_shN, v_viewmats, None) + (None,) * 14
+        return (v_means, v_quats, v_scales, v_opacities, v_sh0, v_shN, v_viewmats, None) + (None,) * 15
 
 
 _VSPLAT_REGISTRY: "weakref.WeakValueDictionary[int, Tensor]" = weakref.WeakValueDictionary()
@@ -454,7 +463,7 @@ def rasterization(
     backgrounds: Optional[Tensor] = None, _flags: int = 0, _sh_rest: Optional[Tensor] = None,
     _sync: bool = True, _handover=None, _c2w: Optional[Tuple[Tensor, Tensor]] = None,
     _post_background: Optional[Tensor] = None, _means2d_leaf: bool = False, _capture_slot=None,
-    _manual: Optional[list] = None, _lazy_sh=None, _post_bwd=None,
+    _manual: Optional[list] = None, _lazy_sh=None, _post_bwd=None, _pose_grad: Optional[Tensor] = None,
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Same call surface as the reference's call (model.py:267-288).
 
@@ -466,7 +475,9 @@ def rasterization(
     (RGB+D) are their results, differentiable like ``render`` / ``alpha``.  ``_means2d_leaf``: ``info["means2d"]`` is a
     leaf that receives ``.grad`` / ``.absgrad`` as views (see below) instead of gsplat's non-leaf.  ``_post_bwd(v_scales,
     v_opacities)``: called by the projection backward right after it has written the parameter gradients, to add terms of
-    its own to them in place (the views alias the flat gradient).
+    its own to them in place (the views alias the flat gradient).  ``_pose_grad`` [C,4,4]: a persistent, zeroed buffer the
+    projection backward adds the view matrices' gradient to (qed_project_bwd's v_viewmats) although ``viewmats`` does not
+    require grad: the camera optimiser of the fused route (camera_optimizer.py), whose qed_pose_step reads and zeroes it.
     """
     if packed or sparse_grad:
         raise NotImplementedError("packed=True / sparse_grad=True are not used by the reference (model.py:278,283)")
@@ -515,7 +526,7 @@ def rasterization(
         _ProjectSH, _manual, None,
         means, quats, scales, opacities, sh0, shN, viewmats, Ks, int(width), int(height), tile_w, tile_h, deg, flags,
         float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
-        *(_c2w if _c2w is not None else (None, None)), _lazy_sh, _post_bwd)
+        *(_c2w if _c2w is not None else (None, None)), _lazy_sh, _post_bwd, _pose_grad)
 
     # the packed tile rectangles of the records save the emit pass a recomputation; with F_TIGHT_TILES they
     # are the only place the (smaller) rectangles exist

@@ -2,12 +2,16 @@
 
     python -m qed_splatter_amd.train --data DIR --steps 30000 [--save ckpt.pt] [--resume ckpt.pt]
                                      [--export-ply splat.ply [--export-frame dataset]] [--render-eval DIR]
+                                     [--camera-optimizer SO3xR3 [--camera-opt-lr 1e-4] [--save-poses poses.json]]
 
 The dataset is read by ``dataparser.parse_dataset``, cached by ``datamanager.FullImageDatamanager`` (uint8 images on
 the GPU), and every step takes the next training camera and its frame through the eager fused route: ``fused_loss``
 (which makes the step's ground truth in one launch, csrc/ingest.hip) -> ``backward_fused`` -> ``FlatAdam.step`` ->
 ``Densifier``.  ``--undistort`` accepts datasets whose cameras carry OPENCV or OPENCV_FISHEYE distortion: their frames are
 resampled to a pinhole on the GPU while the cache is filled (dataparser.py, csrc/undistort.hip).  The captured hipGraph step (graph.py) is not used: it replays ONE camera and ONE ground truth.
+
+``--camera-optimizer SO3xR3`` refines the training cameras' poses along with the Gaussians (camera_optimizer.py: Nerfstudio's
+CameraOptimizer, two extra launches per step); ``--save-poses`` writes the refined poses in the dataset's own frame.
 
 The Gaussians are seeded from the dataset's ``ply_file_path`` (``--init-from-ply`` overrides it) in the frame of the
 cameras, or from random points when there is none.  Every ``--eval-every`` steps and at the end the evaluation split
@@ -17,12 +21,15 @@ from __future__ import annotations
 
 import argparse
 import json
+import os
 import time
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from . import _lib as L
+from .camera_optimizer import CameraOptimizer, CameraOptimizerConfig
 from .datamanager import FullImageDatamanager
 from .dataparser import DataparserConfig
 from .densify import DensifyConfig, Densifier
@@ -30,13 +37,17 @@ from .model import GROUP_ORDER, FlatAdam, QEDSplatterModel, QEDSplatterModelConf
 
 
 class Trainer:
-    """One model, its optimiser and densifier, driven by a datamanager."""
+    """One model, its optimiser and densifier -- and, with ``camera_opt_config`` in a mode other than "off", a camera pose
+    optimiser over the training cameras --, driven by a datamanager."""
 
     def __init__(self, model: QEDSplatterModel, datamanager: FullImageDatamanager, seed: int = 0,
-                 densify_config: Optional[DensifyConfig] = None):
+                 densify_config: Optional[DensifyConfig] = None, camera_opt_config: Optional[CameraOptimizerConfig] = None):
         self.model, self.datamanager, self.seed = model, datamanager, int(seed)
         self.densify_config = densify_config
         self.step = 0
+        self.camera_optimizer: Optional[CameraOptimizer] = None
+        if camera_opt_config is not None and camera_opt_config.mode != "off":
+            self.camera_optimizer = CameraOptimizer(camera_opt_config, datamanager.num_train, model.device)
         self._bind_optimizer()
 
     def _bind_optimizer(self) -> None:
@@ -54,8 +65,11 @@ class Trainer:
             p.grad = None
         idx = batch["image_idx"]
         # frame_key: the camera's index -- its compositing forward reuses the launch order of this camera's last frame
-        losses = model.fused_loss(camera, batch, compact_sh_grad=True, frame_key=idx)
+        pose_opt = self.camera_optimizer
+        losses = model.fused_loss(camera, batch, compact_sh_grad=True, frame_key=idx, camera_optimizer=pose_opt, cam_idx=idx)
         model.backward_fused(losses)
+        if pose_opt is not None:
+            pose_opt.step_fused(step)           # the camera's row gradient, the regulariser's, Adam over all rows: one launch
         self.optimizer.step(fused_sh=True)
         self.densifier.after_train(step)
         if step % self.densifier.config.refine_every == 0:
@@ -91,10 +105,38 @@ class Trainer:
         """The six tensors, the step, the optimiser state -- and the dataparser's transform and scale and the SH degree,
         so that ``python -m qed_splatter_amd.gaussian_ply export --frame dataset`` works from the file alone."""
         out = self.datamanager.outputs
-        torch.save({"params": {n: self.model.gauss_params[n].detach().clone() for n in GROUP_ORDER}, "step": self.step,
-                    "optimizer": self.optimizer.state_dict(),
-                    "dataparser_transform": out.dataparser_transform.detach().cpu().clone(),
-                    "dataparser_scale": float(out.dataparser_scale), "sh_degree": int(self.model.config.sh_degree)}, path)
+        ckpt = {"params": {n: self.model.gauss_params[n].detach().clone() for n in GROUP_ORDER}, "step": self.step,
+                "optimizer": self.optimizer.state_dict(),
+                "dataparser_transform": out.dataparser_transform.detach().cpu().clone(),
+                "dataparser_scale": float(out.dataparser_scale), "sh_degree": int(self.model.config.sh_degree)}
+        if self.camera_optimizer is not None:           # pose_adjustment, its Adam moments and step count
+            ckpt["camera_opt"] = {k: (v.detach().clone() if torch.is_tensor(v) else v)
+                                  for k, v in self.camera_optimizer.state_dict().items()}
+        torch.save(ckpt, path)
+
+    def camera_opt_metrics(self) -> Dict[str, float]:
+        """camera_optimizer.get_metrics_dict as floats ({} without a camera optimiser)."""
+        out: Dict = {}
+        if self.camera_optimizer is not None:
+            self.camera_optimizer.get_metrics_dict(out)
+        return {k: float(v) for k, v in out.items()}
+
+    def save_poses(self, path, data_dir=None) -> int:
+        """The training cameras' (refined) poses as a ``transforms.json``-shaped file: ``frames`` = [{"file_path",
+        "transform_matrix" 4x4}], in the dataset's own frame -- ``dataparser_scale`` and ``dataparser_transform`` undone in
+        float64 on the host.  ``file_path`` is relative to ``data_dir`` when that is given.  Returns the number of frames."""
+        out = self.datamanager.outputs
+        adj = self.camera_optimizer.pose_adjustment.detach().cpu().numpy() if self.camera_optimizer is not None else None
+        poses = poses_in_dataset_frame(out, self.datamanager.i_train, adj)
+        frames = []
+        for k, m in zip(self.datamanager.i_train, poses):
+            name = out.image_filenames[k]
+            name = os.path.relpath(name, data_dir) if data_dir is not None else str(name)
+            frames.append({"file_path": name.replace(os.sep, "/"), "transform_matrix": m.tolist()})
+        mode = self.camera_optimizer.config.mode if self.camera_optimizer is not None else "off"
+        with open(path, "w") as f:
+            json.dump({"camera_optimizer": mode, "frames": frames}, f, indent=1)
+        return len(frames)
 
     def export_ply(self, path, frame: str = "model", color_mode: str = "sh_coeffs") -> Dict[str, int]:
         """The Gaussians as a 3DGS PLY file (gaussian_ply.py), in the model's frame or the dataset's."""
@@ -112,6 +154,41 @@ class Trainer:
         self._bind_optimizer()
         self.optimizer.load_state_dict(ckpt["optimizer"])
         self.step = int(ckpt["step"])
+        # (a checkpoint written without a camera optimiser: the poses start from zero adjustments)
+        if self.camera_optimizer is not None and "camera_opt" in ckpt:
+            self.camera_optimizer.load_state_dict(ckpt["camera_opt"])
+
+
+def exp_map_SO3xR3_f64(pose_adjustment: np.ndarray) -> np.ndarray:
+    """[n,6] -> [n,4,4] float64 on the host: the adjustment matrices [[R, d], [0, 0, 0, 1]] of camera_optimizer.py."""
+    t = np.asarray(pose_adjustment, dtype=np.float64)
+    out = np.tile(np.eye(4), (t.shape[0], 1, 1))
+    for i, (d, w) in enumerate(zip(t[:, :3], t[:, 3:])):
+        a = np.sqrt(max(float(w @ w), 1e-4))
+        K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+        out[i, :3, :3] = np.eye(3) + (np.sin(a) / a) * K + ((1.0 - np.cos(a)) / (a * a)) * (K @ K)
+        out[i, :3, 3] = d
+    return out
+
+
+def poses_in_dataset_frame(outputs, indices, pose_adjustment=None) -> np.ndarray:
+    """[len(indices),4,4] float64: the cameras ``indices`` of the dataparser's outputs, adjusted by the rows of
+    ``pose_adjustment`` (row j belongs to indices[j]; None: as parsed), mapped back to the frame of the dataset's own
+    ``transform_matrix`` entries: translation / dataparser_scale, then the inverse of dataparser_transform."""
+    idx = np.asarray(list(indices), dtype=np.int64)
+    c2w = outputs.camera_to_worlds_f64
+    c2w = np.asarray(c2w if c2w is not None else outputs.camera_to_worlds.double().numpy(), dtype=np.float64)[idx]
+    T = outputs.dataparser_transform_f64
+    T = np.asarray(T if T is not None else outputs.dataparser_transform.double().numpy(), dtype=np.float64)
+    full = np.tile(np.eye(4), (len(idx), 1, 1))
+    full[:, :3] = c2w[:, :3]
+    if pose_adjustment is not None:
+        full = full @ exp_map_SO3xR3_f64(pose_adjustment)
+    full[:, :3, 3] /= float(outputs.dataparser_scale)
+    inv = np.eye(4)
+    inv[:3, :3] = T[:, :3].T
+    inv[:3, 3] = -T[:, :3].T @ T[:, 3]
+    return inv @ full
 
 
 def build_model(config: QEDSplatterModelConfig, datamanager: FullImageDatamanager, init_from_ply=None, seed: int = 0,
@@ -157,6 +234,13 @@ def main(argv=None) -> Dict:
     ap.add_argument("--render-eval", metavar="DIR", default=None,
                     help="after the last evaluation, write the evaluation views as PNG files (render.py: colour, 16-bit depth "
                          "in the dataset's unit, colour-mapped depth, accumulation)")
+    ap.add_argument("--camera-optimizer", choices=("off", "SO3xR3"), default="off",
+                    help="refine the training cameras' poses (Nerfstudio's CameraOptimizer; camera_optimizer.py)")
+    ap.add_argument("--camera-opt-lr", type=float, default=1e-4,
+                    help="the pose optimiser's learning rate (decays to 5e-7 over 30000 steps after a 1000-step warm-up)")
+    ap.add_argument("--save-poses", metavar="PATH", default=None,
+                    help="after training, write the training cameras' (refined) poses in the dataset's own frame, as a "
+                         "transforms.json-shaped file")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("qed_splatter_amd.train needs a GPU")
@@ -172,7 +256,8 @@ def main(argv=None) -> Dict:
                                     background_color=a.background_color, sh_degree=a.sh_degree)
     model = build_model(config, dm, a.init_from_ply, a.seed)
     print(f"seeded {model.num_points} Gaussians")
-    trainer = Trainer(model, dm, seed=a.seed)
+    trainer = Trainer(model, dm, seed=a.seed,
+                      camera_opt_config=CameraOptimizerConfig(mode=a.camera_optimizer, lr=a.camera_opt_lr))
     if a.resume:
         trainer.resume(a.resume)
         print(f"resumed {a.resume} at step {trainer.step} with {trainer.model.num_points} Gaussians")
@@ -198,6 +283,11 @@ def main(argv=None) -> Dict:
     done = trainer.step - first
     result = {"steps": trainer.step, "steps_per_s": done / elapsed if elapsed > 0 and done else 0.0,
               "eval": metrics, "gaussian_count": trainer.model.num_points}
+    if trainer.camera_optimizer is not None:
+        result["camera_opt"] = trainer.camera_opt_metrics()
+    if a.save_poses:
+        result["save_poses"] = trainer.save_poses(a.save_poses, a.data)
+        print(f"wrote {result['save_poses']} training poses to {a.save_poses}")
     if a.render_eval:
         from .render import dataset_path, render_to_directory
         unit = float(dm.outputs.dataparser_scale) * float(dm.outputs.depth_unit_scale_factor)
