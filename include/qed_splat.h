@@ -730,6 +730,22 @@ int qed_bilagrid_tv_fwd(int32_t n_grids, const float* grids, int32_t gx, int32_t
 int qed_bilagrid_tv_bwd(int32_t n_grids, const float* grids, int32_t gx, int32_t gy, int32_t gl, const float* v_tv,
                         float* v_grids, void* stream);
 
+/* The fused training route's grid group (bilagrid.BilateralGridOptimizer).
+ * qed_bilagrid_slice_bwd_acc: qed_bilagrid_slice_bwd's kernel alone -- v_rgb[H,W,3] written, the slab's gradient ADDED
+ *   into slab_ws[Y][X][L][12] (channel-last, the caller's persistent buffer; neither cleared nor re-laid-out here).
+ * qed_bilagrid_step: ONE launch over grids[N,12,L,Y,X]: g = tv_weight * d tv / d grids (qed_bilagrid_tv_bwd's
+ *   definition and weights, from the values the grids hold before the launch) + for grid `row` (-1: none) slab_ws,
+ *   then torch.optim.Adam's update in place on grids / exp_avg / exp_avg_sq (the arithmetic of qed_adam_step; `step`
+ *   is 1-based).  slab_ws is zeroed after it is read.  skip_flag (may be NULL): a device word; non-zero leaves grids and
+ *   moments untouched (slab_ws is zeroed all the same; grad_out is then not written).  grad_out[N,12,L,Y,X] (may be
+ *   NULL): the gradient used.  One workgroup per (grid, channel) volume, staged in LDS: L * Y * X <= 16384. */
+#define QED_BILAGRID_STEP_MAX_VOLUME 16384
+int qed_bilagrid_slice_bwd_acc(int32_t height, int32_t width, const float* rgb, const float* grid, int32_t gx, int32_t gy,
+                               int32_t gl, const float* v_out, float* v_rgb, float* slab_ws, void* stream);
+int qed_bilagrid_step(int32_t n_grids, float* grids, float* exp_avg, float* exp_avg_sq, int32_t gx, int32_t gy,
+                      int32_t gl, float tv_weight, int32_t row, float* slab_ws, float lr, double beta1, double beta2,
+                      float eps, int32_t step, float* grad_out, const int32_t* skip_flag, void* stream);
+
 /* ---- MCMC densification (splatfacto strategy="mcmc"; gsplat MCMCStrategy) -------------------------------------------
  * Flat buffers as qed_densify_emit's: six groups means, scales (log), quats, opacities (logit), features_dc,
  * features_rest, each [N, width], h_*begin[7] their element offsets (+ end), starting at 0.  sigma = sigmoid(logit).

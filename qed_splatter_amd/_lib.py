@@ -95,6 +95,8 @@ SIGNATURES = {
     "qed_bilagrid_slice_bwd": (C.c_int, [_I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "qed_bilagrid_tv_fwd": (C.c_int, [_I, _P, _I, _I, _I, _P, _P, _P]),
     "qed_bilagrid_tv_bwd": (C.c_int, [_I, _P, _I, _I, _I, _P, _P, _P]),
+    "qed_bilagrid_slice_bwd_acc": (C.c_int, [_I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "qed_bilagrid_step": (C.c_int, [_I, _P, _P, _P, _I, _I, _I, _F, _I, _P, _F, _D, _D, _F, _I, _P, _P, _P]),
     "qed_mcmc_workspace_bytes": (_L, [_I, _L]),
     "qed_mcmc_sample": (C.c_int, [_I, _P, _F, _L, _Q, _Q, _P, _P, _L, _P]),
     "qed_mcmc_relocate": (C.c_int, [_I, _P, _P, _P, _P, _F, _P, _Q, _Q, _P, _P, _L, _P]),
@@ -134,6 +136,7 @@ LOSS_SUMS_FLOATS = 8 + 4 * 1024          # QED_LOSS_SUMS_FLOATS
 METRICS_WS_DOUBLES = 10 * 1024           # QED_METRICS_WS_DOUBLES
 STEP_METRICS_WS_DOUBLES = 16 * 1024      # QED_STEP_METRICS_WS_DOUBLES
 BILAGRID_TV_WS_DOUBLES = 1024            # QED_BILAGRID_TV_WS_DOUBLES
+BILAGRID_STEP_MAX_VOLUME = 16384         # QED_BILAGRID_STEP_MAX_VOLUME
 MCMC_REG_WS_DOUBLES = 2048               # QED_MCMC_REG_WS_DOUBLES
 LPIPS_WS_DOUBLES = 5 * 256               # QED_LPIPS_WS_DOUBLES
 LPIPS_TILE_K, LPIPS_TILE_N = 16, 64      # QED_LPIPS_TILE_K, QED_LPIPS_TILE_N

@@ -397,6 +397,104 @@ bilagrid_tv_bwd_kernel(const float* __restrict__ g, TvArgs a, const float* __res
     }
 }
 
+// The fused route's grid step: TV gradient + one slab's data gradient + Adam, all grids in ONE launch.
+//
+// A workgroup owns one (grid, channel) volume [L][Y][X] -- TV differences never leave it.  It stages the volume in LDS,
+// synchronises, forms every element's gradient from the staged (old) values and updates p, m, v in global memory in
+// place: each is read once and written once, and no other workgroup reads what this one writes.  The slab workspace
+// (the slice backward's channel-last [Y][X][L][12]) is read and zeroed by the 12 workgroups of grid `row`, one channel
+// each; with row = -1 the workgroups of grid 0 only zero it.  The arithmetic of the TV gradient is
+// bilagrid_tv_bwd_kernel's with v_tv = tv_weight, Adam's is adam.hip's adam_update.
+constexpr int kBgStepMaxVolume = QED_BILAGRID_STEP_MAX_VOLUME;   // floats of one staged volume: 64 KiB of LDS
+
+struct BgAdam {
+    float beta1, beta2, omb1, omb2, eps, inv_bc1, inv_bc2_sqrt, lr;
+};
+
+__device__ __forceinline__ float bg_adam_update(const BgAdam& a, float pp, float gg, float& mm, float& vv) {
+    mm = a.beta1 * mm + a.omb1 * gg;
+    vv = a.beta2 * vv + a.omb2 * gg * gg;
+    const float denom = sqrtf(vv) * a.inv_bc2_sqrt + a.eps;
+    return pp - a.lr * a.inv_bc1 * mm / denom;
+}
+
+// VEC: X % 4 == 0 and 16-byte aligned buffers -- a thread owns four consecutive x of one row and moves p, m, v as float4.
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+bilagrid_step_kernel(float* __restrict__ grids, float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, TvArgs a,
+                     float tv_scale, int row, float* __restrict__ slab_ws, BgAdam co, float* __restrict__ grad_out,
+                     const int* __restrict__ skip) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    extern __shared__ float4 s_dyn[];
+    float* s_vol = reinterpret_cast<float*>(s_dyn);
+    constexpr int W = VEC ? 4 : 1;
+    const int XY = a.X * a.Y, V = XY * a.L;
+    const int grid = blockIdx.x / 12, c = blockIdx.x - 12 * grid;
+    const size_t base = (size_t)blockIdx.x * V;
+    const bool skipped = skip != nullptr && skip[0] != 0;              // (uniform over the launch)
+    if (skipped || row < 0) {
+        // no slab gradient is consumed: the workspace is handed back zeroed all the same
+        if (grid == (row >= 0 ? row : 0))
+            for (int i = threadIdx.x; i < V; i += 256) slab_ws[(size_t)i * 12 + c] = 0.f;
+        if (skipped) return;
+    }
+    const bool slab = grid == row;
+    if (VEC) {
+        const float4* src = reinterpret_cast<const float4*>(grids + base);
+        for (int i = threadIdx.x; i < V / 4; i += 256) reinterpret_cast<float4*>(s_vol)[i] = src[i];
+    } else {
+        for (int i = threadIdx.x; i < V; i += 256) s_vol[i] = grids[base + i];
+    }
+    __syncthreads();
+    for (int i0 = threadIdx.x * W; i0 < V; i0 += 256 * W) {
+        float pp[4], mm[4], vv[4], gg[4];
+        float* const pm = exp_avg + base + i0;
+        float* const pv = exp_avg_sq + base + i0;
+        if (VEC) {
+            // the moments are touched once per step and by nobody else: non-temporal, as in adam.hip, so that 2 x the
+            // grids' size does not displace the Gaussians' parameters from the last-level cache
+            const v4f m4 = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(pm));
+            const v4f v4 = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(pv));
+            mm[0] = m4.x; mm[1] = m4.y; mm[2] = m4.z; mm[3] = m4.w;
+            vv[0] = v4.x; vv[1] = v4.y; vv[2] = v4.z; vv[3] = v4.w;
+        } else {
+            mm[0] = pm[0]; vv[0] = pv[0];
+        }
+        const int l = i0 / XY, r = i0 - l * XY;
+        const int y = r / a.X, x0 = r - y * a.X;
+        const int oym = y > 0 ? -a.X : 0, oyp = y + 1 < a.Y ? a.X : 0;
+        const int olm = l > 0 ? -XY : 0, olp = l + 1 < a.L ? XY : 0;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const int x = x0 + k;
+            const int oxm = x > 0 ? -1 : 0, oxp = x + 1 < a.X ? 1 : 0;
+            const float* sp = s_vol + i0 + k;
+            const float v = sp[0];
+            const float dx = (v - sp[oxm]) - (sp[oxp] - v);
+            const float dy = (v - sp[oym]) - (sp[oyp] - v);
+            const float dl = (v - sp[olm]) - (sp[olp] - v);
+            float g = tv_scale * (a.wx * dx + a.wy * dy + a.wl * dl);
+            if (slab) {
+                float* w = slab_ws + ((size_t)(y * a.X + x) * a.L + l) * 12 + c;
+                g += w[0];
+                w[0] = 0.f;
+            }
+            gg[k] = g;
+            pp[k] = bg_adam_update(co, v, g, mm[k], vv[k]);
+        }
+        if (VEC) {
+            *reinterpret_cast<float4*>(grids + base + i0) = make_float4(pp[0], pp[1], pp[2], pp[3]);
+            __builtin_nontemporal_store((v4f){mm[0], mm[1], mm[2], mm[3]}, reinterpret_cast<v4f*>(pm));
+            __builtin_nontemporal_store((v4f){vv[0], vv[1], vv[2], vv[3]}, reinterpret_cast<v4f*>(pv));
+            if (grad_out != nullptr)
+                *reinterpret_cast<float4*>(grad_out + base + i0) = make_float4(gg[0], gg[1], gg[2], gg[3]);
+        } else {
+            grids[base + i0] = pp[0]; pm[0] = mm[0]; pv[0] = vv[0];
+            if (grad_out != nullptr) grad_out[base + i0] = gg[0];
+        }
+    }
+}
+
 // Host side ---------------------------------------------------------------------------------------------------------
 
 static int bg_args(int32_t H, int32_t W, int32_t X, int32_t Y, int32_t L, BgArgs& a, bool& staged) {
@@ -437,19 +535,18 @@ extern "C" int qed_bilagrid_slice_fwd(int32_t height, int32_t width, const float
     return check_launch("qed_bilagrid_slice_fwd");
 }
 
-extern "C" int qed_bilagrid_slice_bwd(int32_t height, int32_t width, const float* rgb, const float* grid, int32_t gx,
-                                      int32_t gy, int32_t gl, const float* v_out, float* v_rgb, float* v_grid,
-                                      float* workspace, void* stream) {
+// The slice backward launch: v_rgb written, the slab's gradient ADDED into the channel-last workspace [Y][X][L][12].
+static int bg_slice_bwd_launch(int32_t height, int32_t width, const float* rgb, const float* grid, int32_t gx, int32_t gy,
+                               int32_t gl, const float* v_out, float* v_rgb, float* workspace, bool clear, hipStream_t st,
+                               const char* who) {
     BgArgs a;
     bool staged;
     const int rc = bg_args(height, width, gx, gy, gl, a, staged);
     if (rc != QED_OK) return rc;
-    QED_REQUIRE(rgb && grid && v_out && v_rgb && v_grid && workspace, "null buffers");
+    QED_REQUIRE(rgb && grid && v_out && v_rgb && workspace, "null buffers");
     const unsigned blocks = (unsigned)(a.tiles_x * ((height + kBgTH - 1) / kBgTH));
-    const int n_grid = 12 * gl * gy * gx;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, (size_t)n_grid * sizeof(float), st) != hipSuccess) {
-        set_error("qed_bilagrid_slice_bwd: memset failed");
+    if (clear && hipMemsetAsync(workspace, 0, (size_t)12 * gl * gy * gx * sizeof(float), st) != hipSuccess) {
+        set_error("%s: memset failed", who);
         return QED_E_LAUNCH;
     }
     if (staged)
@@ -458,9 +555,29 @@ extern "C" int qed_bilagrid_slice_bwd(int32_t height, int32_t width, const float
     else
         hipLaunchKernelGGL(bilagrid_slice_bwd_kernel<false>, dim3(blocks), dim3(kBgThreads), 0, st, rgb, grid, v_out, a,
                            v_rgb, workspace);
+    return QED_OK;
+}
+
+extern "C" int qed_bilagrid_slice_bwd(int32_t height, int32_t width, const float* rgb, const float* grid, int32_t gx,
+                                      int32_t gy, int32_t gl, const float* v_out, float* v_rgb, float* v_grid,
+                                      float* workspace, void* stream) {
+    QED_REQUIRE(v_grid, "null buffers");
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = bg_slice_bwd_launch(height, width, rgb, grid, gx, gy, gl, v_out, v_rgb, workspace, true, st,
+                                       "qed_bilagrid_slice_bwd");
+    if (rc != QED_OK) return rc;
+    const int n_grid = 12 * gl * gy * gx;
     hipLaunchKernelGGL(bilagrid_grad_layout_kernel, dim3((unsigned)std::min(1024, (n_grid + 255) / 256)), dim3(256), 0,
                        st, (const float*)workspace, gx, gy, gl, v_grid);
     return check_launch("qed_bilagrid_slice_bwd");
+}
+
+extern "C" int qed_bilagrid_slice_bwd_acc(int32_t height, int32_t width, const float* rgb, const float* grid, int32_t gx,
+                                          int32_t gy, int32_t gl, const float* v_out, float* v_rgb, float* slab_ws,
+                                          void* stream) {
+    const int rc = bg_slice_bwd_launch(height, width, rgb, grid, gx, gy, gl, v_out, v_rgb, slab_ws, false,
+                                       (hipStream_t)stream, "qed_bilagrid_slice_bwd_acc");
+    return rc != QED_OK ? rc : check_launch("qed_bilagrid_slice_bwd_acc");
 }
 
 static int tv_args(int32_t n_grids, int32_t gx, int32_t gy, int32_t gl, TvArgs& a) {
@@ -498,4 +615,34 @@ extern "C" int qed_bilagrid_tv_bwd(int32_t n_grids, const float* grids, int32_t 
     const unsigned nb = (unsigned)std::min(8 * kBgTvBlocks, a.planes / kTvPlanes);
     hipLaunchKernelGGL(bilagrid_tv_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, grids, a, v_tv, v_grids);
     return check_launch("qed_bilagrid_tv_bwd");
+}
+
+extern "C" int qed_bilagrid_step(int32_t n_grids, float* grids, float* exp_avg, float* exp_avg_sq, int32_t gx, int32_t gy,
+                                 int32_t gl, float tv_weight, int32_t row, float* slab_ws, float lr, double beta1,
+                                 double beta2, float eps, int32_t step, float* grad_out, const int32_t* skip_flag,
+                                 void* stream) {
+    TvArgs a;
+    const int rc = tv_args(n_grids, gx, gy, gl, a);
+    if (rc != QED_OK) return rc;
+    QED_REQUIRE((long long)gl * gy * gx <= kBgStepMaxVolume,
+                "qed_bilagrid_step: a grid channel (L * Y * X) may hold at most 16384 floats (64 KiB of LDS)");
+    QED_REQUIRE(n_grids < (1 << 24), "n_grids < 2^24 required");
+    QED_REQUIRE(grids && exp_avg && exp_avg_sq && slab_ws, "null buffers");
+    QED_REQUIRE(row >= -1 && row < n_grids, "row must be -1 (no slab gradient this step) or a grid's index");
+    QED_REQUIRE(step >= 1, "step is 1-based");
+    const BgAdam co{(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps,
+                    (float)(1.0 / (1.0 - pow(beta1, (double)step))), (float)(1.0 / sqrt(1.0 - pow(beta2, (double)step))), lr};
+    const int V = gl * gy * gx;
+    const uintptr_t bits = (uintptr_t)grids | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)grad_out;
+    const bool vec = gx % 4 == 0 && bits % 16 == 0;
+    const float tv_scale = 2.f * tv_weight;                       // bilagrid_tv_bwd_kernel's 2 v_tv
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 blocks((unsigned)n_grids * 12u);
+    if (vec)
+        hipLaunchKernelGGL(bilagrid_step_kernel<true>, blocks, dim3(256), (size_t)V * 4, st, grids, exp_avg, exp_avg_sq, a,
+                           tv_scale, row, slab_ws, co, grad_out, skip_flag);
+    else
+        hipLaunchKernelGGL(bilagrid_step_kernel<false>, blocks, dim3(256), (size_t)V * 4, st, grids, exp_avg, exp_avg_sq, a,
+                           tv_scale, row, slab_ws, co, grad_out, skip_flag);
+    return check_launch("qed_bilagrid_step");
 }

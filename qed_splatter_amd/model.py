@@ -1121,7 +1121,7 @@ class QEDSplatterModel(nn.Module):
 
     def fused_loss(self, camera, batch, background: Optional[Tensor] = None, sync: bool = True,
                    compact_sh_grad: bool = False, optimizer: Optional["FlatAdam"] = None,
-                   frame_key=None, camera_optimizer=None, cam_idx=None) -> Dict[str, Tensor]:
+                   frame_key=None, camera_optimizer=None, cam_idx=None, grid_optimizer=None) -> Dict[str, Tensor]:
         """Forward + K8 fused loss.  Returns {"loss", "main_loss", "depth_loss"}: ``loss`` = main + depth is
         the differentiable total (call ``.backward()`` on it as is: the kernel already wrote its gradient
         for an upstream gradient of 1); the two parts are detached views for logging.  Numerically the
@@ -1139,12 +1139,26 @@ class QEDSplatterModel(nn.Module):
         as for any other pose -- and the projection backward leaves the view matrix's gradient in the optimiser's buffer:
         follow ``backward_fused`` with ``camera_optimizer.step_fused(step)``.  The camera's row is ``cam_idx`` (the
         datamanager's ``batch["image_idx"]``), else ``camera.metadata["cam_idx"]``.  The regulariser's value is returned
-        as ``camera_opt_regularizer`` and is part of ``loss`` (its gradient is qed_pose_step's business)."""
+        as ``camera_opt_regularizer`` and is part of ``loss`` (its gradient is qed_pose_step's business).
+
+        ``grid_optimizer`` (a bilagrid.BilateralGridOptimizer over this model's grids; used in training on a model that
+        holds grids, else ignored): the frame's clamped colour is corrected by grid ``cam_idx`` (else
+        ``camera.metadata["cam_idx"]``) before the L1 and SSIM terms, exactly as get_outputs / get_loss_dict do;
+        ``tv_loss`` = tv_weight * TV of the grids is returned and is part of ``loss``.  The grids' gradient never becomes a
+        tensor: follow ``backward_fused`` with ``grid_optimizer.step_fused(step)`` (_fused_loss_with_grid)."""
         assert camera.shape[0] == 1, "Only one camera at a time"
+        grid_opt = None
         if self.training and self.config.use_bilateral_grid and self.bil_grids is not None:
-            raise NotImplementedError(
-                "fused_loss does not apply the bilateral grid (nor its tv_loss): train a model with bilateral grids "
-                "through get_outputs -> get_loss_dict -> backward")
+            if grid_optimizer is None:
+                raise NotImplementedError(
+                    "fused_loss does not apply the bilateral grid (nor its tv_loss): train a model with bilateral grids "
+                    "through get_outputs -> get_loss_dict -> backward, or pass grid_optimizer=BilateralGridOptimizer(...)")
+            if grid_optimizer.grids is not self.bil_grids.grids:
+                raise ValueError("fused_loss(grid_optimizer=...): the optimiser was built for other grids than this model's")
+            if torch.cuda.is_current_stream_capturing():
+                raise NotImplementedError("a bilateral-grid optimiser inside a captured step (graph.py, segments.py): the "
+                                          "grid's index and the learning rate are host arguments of its launches")
+            grid_opt = grid_optimizer
         if self.__dict__.get("_lazy_sh") is not None and torch.is_grad_enabled():
             self._materialise_sh_grads()          # (compact gradients of a get_outputs step nobody consumed: see there)
         cfg = self.config
@@ -1152,6 +1166,17 @@ class QEDSplatterModel(nn.Module):
         attrs = self.__dict__            # (plain attributes, as in get_outputs)
         pose_opt = camera_optimizer if (camera_optimizer is not None and camera_optimizer.active and self.training) else None
         attrs["pose_optimizer"] = pose_opt       # (parallel.py refuses a data-parallel step behind it)
+        attrs["grid_optimizer"] = grid_opt       # (likewise)
+        grid_idx = None
+        if grid_opt is not None:
+            grid_idx = cam_idx
+            if grid_idx is None:
+                meta = getattr(camera, "metadata", None)
+                grid_idx = meta["cam_idx"] if (meta is not None and "cam_idx" in meta) else None
+            if grid_idx is None:
+                raise ValueError("fused_loss(grid_optimizer=...) needs the camera's training index: cam_idx=... or "
+                                 "camera.metadata['cam_idx']")
+            grid_idx = grid_opt._check_index(int(grid_idx))
         c2w, pose_reg = camera.camera_to_worlds, None
         if pose_opt is not None:
             if torch.cuda.is_current_stream_capturing():
@@ -1189,6 +1214,10 @@ class QEDSplatterModel(nn.Module):
         frame_order = self._frame_order_slot(frame_key, H, W) if frame_key is not None else None
         # (the fused loss launch offers the compositing backward its zeroed accumulator and launch order through this)
         handover = Handover(self.num_points, frame_order)
+        if grid_opt is not None:
+            return self._fused_loss_with_grid(grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags,
+                                              sync, handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask,
+                                              lo, ls, mcmc_vals)
         # ``optimizer`` (a FlatAdam stepped with device_state=True, fused_sh=True right after this step's backward): the
         # loss pass's fold launch advances its device step state, so that the optimiser needs no launch of its own for it
         tick = None
@@ -1228,4 +1257,40 @@ class QEDSplatterModel(nn.Module):
         if pose_reg is not None:
             out["loss"] = out["loss"] + pose_reg
             out["camera_opt_regularizer"] = pose_reg
+        return out
+
+    def _fused_loss_with_grid(self, grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags, sync,
+                              handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask, lo, ls, mcmc_vals):
+        """fused_loss behind ``grid_optimizer``: the loss is taken on the CORRECTED colour, so the gridless route's one
+        launch from ``render`` to its gradient does not apply.  The launches are those of get_outputs -> get_loss_dict:
+        the compositing forward with its post-processing epilogue (clamped colour, fixed-up depth), the slice, the SSIM
+        and loss forwards on the corrected image; backwards the loss launch (which also zeroes the compositing backward's
+        accumulator), the slice backward -- adding the grid's gradient to the optimiser's workspace instead of making a
+        tensor of it --, and the compositing backward with the post-processing gradient in its prologue.  No element-wise
+        torch statement touches an image or the grids.  (The step-state tick of ``optimizer=`` rides on the gridless
+        route's loss launch only: here the optimiser ticks for itself.)"""
+        cfg, attrs = self.config, self.__dict__
+        grad = torch.is_grad_enabled()
+        render, alpha, info = self._rasterize(
+            means=self.means, quats=self.quats, scales=self.scales, opacities=self.opacities, colors=colors,
+            viewmats=viewmat, Ks=K, width=W, height=H, render_mode="RGB+D", sh_degree=deg, _flags=flags,
+            _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd, _post_background=bg,
+            _pose_grad=pose_opt.pose_grad if (pose_opt is not None and grad) else None)
+        attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
+        attrs["last_viewmat"], attrs["last_sh_degree"] = viewmat, deg
+        rgb, tv = grid_opt.begin_fused(info.pop("post_rgb"), grid_idx, H, W)
+        depth = info.pop("post_depth")
+        main, depth_loss = _ImageLosses.apply(rgb.squeeze(0), depth.squeeze(0), gt_rgb, gt_depth, mask,
+                                              float(cfg.ssim_lambda), float(cfg.depth_lambda), None, None,
+                                              handover if grad else None)
+        total = main + depth_loss + tv
+        out = {"loss": total, "main_loss": main.detach()}
+        if mcmc_vals is not None:
+            out["loss"] = total + mcmc_vals[2]
+            self._put_mcmc_regs(out, lo, ls, mcmc_vals)
+        out["depth_loss"] = depth_loss.detach()
+        if pose_reg is not None:
+            out["loss"] = out["loss"] + pose_reg
+            out["camera_opt_regularizer"] = pose_reg
+        out["tv_loss"] = tv
         return out

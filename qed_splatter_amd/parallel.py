@@ -48,6 +48,9 @@ def _refuse_camera_optimizer(model, who: str) -> None:
     if model.__dict__.get("pose_optimizer") is not None:
         raise NotImplementedError(f"{who}: the last fused_loss ran with a camera optimiser; pose optimisation under data "
                                   "parallelism is not supported")
+    if model.__dict__.get("grid_optimizer") is not None:
+        raise NotImplementedError(f"{who}: the last fused_loss ran with a bilateral-grid optimiser; every rank would step "
+                                  "the grids from its own frame, and neither they nor their Adam state are exchanged")
 
 
 def _refuse_compact(model, who: str) -> None:

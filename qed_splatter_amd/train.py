@@ -3,6 +3,7 @@
     python -m qed_splatter_amd.train --data DIR --steps 30000 [--save ckpt.pt] [--resume ckpt.pt]
                                      [--export-ply splat.ply [--export-frame dataset]] [--render-eval DIR]
                                      [--camera-optimizer SO3xR3 [--camera-opt-lr 1e-4] [--save-poses poses.json]]
+                                     [--use-bilateral-grid [--grid-shape 16 16 8]]
 
 The dataset is read by ``dataparser.parse_dataset``, cached by ``datamanager.FullImageDatamanager`` (uint8 images on
 the GPU), and every step takes the next training camera and its frame through the eager fused route: ``fused_loss``
@@ -12,6 +13,10 @@ resampled to a pinhole on the GPU while the cache is filled (dataparser.py, csrc
 
 ``--camera-optimizer SO3xR3`` refines the training cameras' poses along with the Gaussians (camera_optimizer.py: Nerfstudio's
 CameraOptimizer, two extra launches per step); ``--save-poses`` writes the refined poses in the dataset's own frame.
+
+``--use-bilateral-grid`` gives every training image a grid of affine colour transforms (bilagrid.py: splatfacto's
+use_bilateral_grid) that absorbs its exposure and white balance; the grids train on the same route (one slice launch each way
+and one launch, qed_bilagrid_step, for their TV gradient and Adam step).  Evaluation renders stay uncorrected, as upstream.
 
 The Gaussians are seeded from the dataset's ``ply_file_path`` (``--init-from-ply`` overrides it) in the frame of the
 cameras, or from random points when there is none.  Every ``--eval-every`` steps and at the end the evaluation split
@@ -29,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .bilagrid import BilateralGridOptimizer, BilateralGridOptimizerConfig, check_step_shape
 from .camera_optimizer import CameraOptimizer, CameraOptimizerConfig
 from .datamanager import FullImageDatamanager
 from .dataparser import DataparserConfig
@@ -38,12 +44,15 @@ from .model import GROUP_ORDER, FlatAdam, QEDSplatterModel, QEDSplatterModelConf
 
 class Trainer:
     """One model, its optimiser and densifier -- and, with ``camera_opt_config`` in a mode other than "off", a camera pose
-    optimiser over the training cameras --, driven by a datamanager."""
+    optimiser over the training cameras; for a model that holds bilateral grids, their optimiser --, driven by a
+    datamanager."""
 
     def __init__(self, model: QEDSplatterModel, datamanager: FullImageDatamanager, seed: int = 0,
-                 densify_config: Optional[DensifyConfig] = None, camera_opt_config: Optional[CameraOptimizerConfig] = None):
+                 densify_config: Optional[DensifyConfig] = None, camera_opt_config: Optional[CameraOptimizerConfig] = None,
+                 grid_opt_config: Optional[BilateralGridOptimizerConfig] = None):
         self.model, self.datamanager, self.seed = model, datamanager, int(seed)
         self.densify_config = densify_config
+        self.grid_opt_config = grid_opt_config
         self.step = 0
         self.camera_optimizer: Optional[CameraOptimizer] = None
         if camera_opt_config is not None and camera_opt_config.mode != "off":
@@ -52,6 +61,9 @@ class Trainer:
 
     def _bind_optimizer(self) -> None:
         self.optimizer = FlatAdam(self.model, means_schedule=FlatAdam.MEANS_SCHEDULE)
+        self.grid_optimizer: Optional[BilateralGridOptimizer] = None
+        if self.model.bil_grids is not None:
+            self.grid_optimizer = BilateralGridOptimizer(self.model.bil_grids, self.grid_opt_config)
         self.densifier = Densifier(self.model, self.optimizer, self.densify_config or DensifyConfig(),
                                    num_train_data=self.datamanager.num_train, seed=self.seed)
 
@@ -66,11 +78,15 @@ class Trainer:
         idx = batch["image_idx"]
         # frame_key: the camera's index -- its compositing forward reuses the launch order of this camera's last frame
         pose_opt = self.camera_optimizer
-        losses = model.fused_loss(camera, batch, compact_sh_grad=True, frame_key=idx, camera_optimizer=pose_opt, cam_idx=idx)
+        grid_opt = self.grid_optimizer
+        losses = model.fused_loss(camera, batch, compact_sh_grad=True, frame_key=idx, camera_optimizer=pose_opt, cam_idx=idx,
+                                  grid_optimizer=grid_opt)
         model.backward_fused(losses)
         if pose_opt is not None:
             pose_opt.step_fused(step)           # the camera's row gradient, the regulariser's, Adam over all rows: one launch
         self.optimizer.step(fused_sh=True)
+        if grid_opt is not None:
+            grid_opt.step_fused(step)           # every grid's TV gradient, this camera's slab gradient, Adam: one launch
         self.densifier.after_train(step)
         if step % self.densifier.config.refine_every == 0:
             self.densifier.refinement_after(step)
@@ -112,6 +128,10 @@ class Trainer:
         if self.camera_optimizer is not None:           # pose_adjustment, its Adam moments and step count
             ckpt["camera_opt"] = {k: (v.detach().clone() if torch.is_tensor(v) else v)
                                   for k, v in self.camera_optimizer.state_dict().items()}
+        if self.grid_optimizer is not None:             # the grids, their Adam moments and step count
+            ckpt["bilateral_grid"] = {"grids": self.model.bil_grids.grids.detach().clone(),
+                                      "optimizer": {k: (v.detach().clone() if torch.is_tensor(v) else v)
+                                                    for k, v in self.grid_optimizer.state_dict().items()}}
         torch.save(ckpt, path)
 
     def camera_opt_metrics(self) -> Dict[str, float]:
@@ -150,8 +170,15 @@ class Trainer:
         read): the model is rebuilt around the loaded Gaussians (their number may differ from the seeded model's) with
         this trainer's configuration."""
         ckpt = torch.load(path, map_location=self.model.device, weights_only=False)
-        self.model = QEDSplatterModel(self.model.config, **{n: ckpt["params"][n] for n in GROUP_ORDER})
+        n_grids = self.model.bil_grids.grids.shape[0] if self.model.bil_grids is not None else None
+        self.model = QEDSplatterModel(self.model.config, num_train_data=n_grids, **{n: ckpt["params"][n] for n in GROUP_ORDER})
+        # (a checkpoint written without grids: they start from the identity)
+        if self.model.bil_grids is not None and "bilateral_grid" in ckpt:
+            with torch.no_grad():
+                self.model.bil_grids.grids.copy_(ckpt["bilateral_grid"]["grids"])
         self._bind_optimizer()
+        if self.grid_optimizer is not None and "bilateral_grid" in ckpt:
+            self.grid_optimizer.load_state_dict(ckpt["bilateral_grid"]["optimizer"])
         self.optimizer.load_state_dict(ckpt["optimizer"])
         self.step = int(ckpt["step"])
         # (a checkpoint written without a camera optimiser: the poses start from zero adjustments)
@@ -194,18 +221,20 @@ def poses_in_dataset_frame(outputs, indices, pose_adjustment=None) -> np.ndarray
 def build_model(config: QEDSplatterModelConfig, datamanager: FullImageDatamanager, init_from_ply=None, seed: int = 0,
                 device=None) -> QEDSplatterModel:
     """Seeded from ``init_from_ply`` or the dataset's ``ply_file_path`` (through the dataparser's transform and scale,
-    so that points and cameras share a frame); random points when there is neither."""
+    so that points and cameras share a frame); random points when there is neither.  With ``config.use_bilateral_grid`` the
+    model holds one bilateral grid per training image."""
     out = datamanager.outputs
     device = device if device is not None else datamanager.compute_device
     ply = init_from_ply if init_from_ply is not None else out.ply_file_path
     if ply is not None:
         # the cloud is in the frame of the json's poses (see DataparserOutputs.ply_file_path): it moves as the cameras do
         return QEDSplatterModel.from_ply(config, ply, out.dataparser_transform, out.dataparser_scale, seed=seed,
-                                         device=device)
-    return QEDSplatterModel.from_seed_points(config, None, None, random_init=True, seed=seed, device=device)
+                                         device=device, num_train_data=datamanager.num_train)
+    return QEDSplatterModel.from_seed_points(config, None, None, random_init=True, seed=seed, device=device,
+                                             num_train_data=datamanager.num_train)
 
 
-def main(argv=None) -> Dict:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m qed_splatter_amd.train", description=__doc__.split("\n\n")[0])
     ap.add_argument("--data", required=True, help="dataset directory (transforms.json, images, depth maps)")
     ap.add_argument("--steps", type=int, default=30000)
@@ -241,7 +270,17 @@ def main(argv=None) -> Dict:
     ap.add_argument("--save-poses", metavar="PATH", default=None,
                     help="after training, write the training cameras' (refined) poses in the dataset's own frame, as a "
                          "transforms.json-shaped file")
-    a = ap.parse_args(argv)
+    ap.add_argument("--use-bilateral-grid", action="store_true",
+                    help="one grid of affine colour transforms per training image (splatfacto's use_bilateral_grid; bilagrid.py)")
+    ap.add_argument("--grid-shape", type=int, nargs=3, metavar=("X", "Y", "L"), default=[16, 16, 8],
+                    help="the extents of each bilateral grid (every one >= 2, X * Y * L <= 16384)")
+    return ap
+
+
+def main(argv=None) -> Dict:
+    a = build_parser().parse_args(argv)
+    if a.use_bilateral_grid:
+        check_step_shape(*a.grid_shape)
     if not torch.cuda.is_available():
         raise SystemExit("qed_splatter_amd.train needs a GPU")
     L.load()
@@ -253,7 +292,8 @@ def main(argv=None) -> Dict:
                               undistort=a.undistort)
     dm = FullImageDatamanager(a.data, dp_cfg, device=a.cache_device, seed=a.seed)
     config = QEDSplatterModelConfig(num_downscales=a.num_downscales, resolution_schedule=a.resolution_schedule,
-                                    background_color=a.background_color, sh_degree=a.sh_degree)
+                                    background_color=a.background_color, sh_degree=a.sh_degree,
+                                    use_bilateral_grid=a.use_bilateral_grid, grid_shape=tuple(a.grid_shape))
     model = build_model(config, dm, a.init_from_ply, a.seed)
     print(f"seeded {model.num_points} Gaussians")
     trainer = Trainer(model, dm, seed=a.seed,
@@ -265,8 +305,9 @@ def main(argv=None) -> Dict:
     first = trainer.step
     torch.cuda.synchronize()
     t0 = time.time()
+    losses = None
     while trainer.step < a.steps:
-        trainer.train_step()
+        losses = trainer.train_step()
         if a.eval_every and trainer.step % a.eval_every == 0 and trainer.step < a.steps:
             metrics = trainer.evaluate()
             print(f"step {trainer.step}: " + ", ".join(f"{k} {v:.5g}" for k, v in metrics.items()), flush=True)
@@ -285,6 +326,8 @@ def main(argv=None) -> Dict:
               "eval": metrics, "gaussian_count": trainer.model.num_points}
     if trainer.camera_optimizer is not None:
         result["camera_opt"] = trainer.camera_opt_metrics()
+    if trainer.grid_optimizer is not None:
+        result["tv_loss"] = float(losses["tv_loss"]) if losses is not None else None
     if a.save_poses:
         result["save_poses"] = trainer.save_poses(a.save_poses, a.data)
         print(f"wrote {result['save_poses']} training poses to {a.save_poses}")
