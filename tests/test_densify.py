@@ -3,7 +3,9 @@ cases; GPU tests compare csrc/densify.hip (through the C ABI and the Densifier h
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 
+import numpy as np
 import pytest
 import torch
 
@@ -36,6 +38,158 @@ def _scenario(n, seed, rest=15):
     st.xys_grad_norm = avg / 960.0 * st.vis_counts
     st.max_2Dsize = choice([0.01, 0.08, 0.2], (n,)) * jitter((n,))
     return p, m, v, st
+
+
+def _scenario_vectorised(n, seed, rest=0):
+    """_scenario for large n: the same distributions, the axis permutation drawn at once (argsort of uniforms instead of
+    one randperm per Gaussian).  Not the same numbers as _scenario, whose cases keep their data."""
+    g = torch.Generator().manual_seed(seed)
+
+    def choice(vals, size):
+        v = torch.tensor(vals, dtype=torch.float32)
+        return v[torch.randint(0, len(vals), size, generator=g)]
+
+    jitter = lambda size: 1.0 + 0.01 * (2 * torch.rand(size, generator=g) - 1)                      # noqa: E731
+    smax = choice([0.002, 0.008, 0.012, 0.05, 0.6], (n,)) * jitter((n,))
+    scales = torch.log(smax[:, None] * torch.tensor([1.0, 0.7, 0.4])[None, :]).float()
+    scales = torch.gather(scales, 1, torch.argsort(torch.rand(n, 3, generator=g), dim=1))
+    sig = choice([0.001, 0.004, 0.2, 0.9], (n, 1)) * jitter((n, 1))
+    p = {"means": torch.randn(n, 3, generator=g), "scales": scales, "quats": torch.randn(n, 4, generator=g),
+         "opacities": torch.log(sig / (1 - sig)), "features_dc": torch.rand(n, 3, generator=g),
+         "features_rest": torch.randn(n, rest, 3, generator=g) * 0.1}
+    m = {k: torch.randn(t.shape, generator=g) * 0.01 for k, t in p.items()}
+    v = {k: torch.rand(t.shape, generator=g) * 0.01 for k, t in p.items()}
+    st = D.DensifyState()
+    st.vis_counts = torch.randint(1, 40, (n,), generator=g).float()
+    avg = choice([0.0001, 0.002], (n,)) * jitter((n,))                  # x 0.5 max(H,W) = 960 -> vs 0.0005
+    st.xys_grad_norm = avg / 960.0 * st.vis_counts
+    st.max_2Dsize = choice([0.01, 0.08, 0.2], (n,)) * jitter((n,))
+    return p, m, v, st
+
+
+# ---- the block scan at scale: one round of densify_scan_blocks_kernel covers 1024 workgroups of 256 rows ----
+SCAN_ROUND_ROWS = 1024 * 256
+#               N                       step   rest
+SCALE_CASES = [(SCAN_ROUND_ROWS,        700,   0),       # exactly 1024 workgroups: one round, full
+               (SCAN_ROUND_ROWS + 1,    700,   0),       # the second round holds one workgroup with one row
+               (SCAN_ROUND_ROWS + 257,  700,   0),       # densify with the screen tests on
+               (SCAN_ROUND_ROWS + 257,  15100, 0),       # cull only
+               (3 * SCAN_ROUND_ROWS + 1, 700,  0),       # four rounds
+               (SCAN_ROUND_ROWS + 1,    700,   15)]      # the 59-float row at scale
+SCALE_SEED = 1
+
+
+def _outcome_of_rows(p, m, v, st, lo, hi, step):
+    """The oracle on rows [lo, hi) alone (every decision is per row): (splits, duplicates, old rows kept, old rows
+    culled without being split, rows afterwards).  A kept old row keeps its moments, every new row has zero moments."""
+    sl = slice(lo, hi)
+    sub = D.DensifyState()
+    sub.__dict__.update({k: t[sl].clone() for k, t in st.__dict__.items()})
+    with torch.random.fork_rng():
+        out_p, out_m, _, info = D.refinement_after({k: t[sl] for k, t in p.items()}, {k: t[sl] for k, t in m.items()},
+                                                   {k: t[sl] for k, t in v.items()}, sub, step, D.DensifyConfig(),
+                                                   (1080, 1920), 10)
+    k_old = int((out_m["means"] != 0).any(dim=1).sum())
+    return info["n_split"], info["n_dup"], k_old, (hi - lo) - info["n_split"] - k_old, out_p["means"].shape[0]
+
+
+def _scale_inputs(n, step, rest):
+    """The scenario of one scale case, with the condition on it asserted on the oracle alone: the rows of the first scan
+    round and the rows behind it each hold at least one split, one duplicate, one kept old row and one culled row (kept
+    and culled only, where the step does not densify), so that a wrong base of a later round moves rows of every kind.
+    A tail of a single row cannot hold one of each: that row has to be written somewhere."""
+    p, m, v, st = _scenario_vectorised(n, SCALE_SEED, rest)
+    densifies = step < D.DensifyConfig().stop_split_at
+    for lo, hi in ((0, min(n, SCAN_ROUND_ROWS)), (SCAN_ROUND_ROWS, n)):
+        if hi - lo == 0:
+            continue
+        n_split, n_dup, k_old, n_gone, n_after = _outcome_of_rows(p, m, v, st, lo, hi, step)
+        if hi - lo == 1:
+            assert n_after > 0, (lo, hi)
+        elif densifies:
+            assert min(n_split, n_dup, k_old, n_gone) > 0, (lo, hi, n_split, n_dup, k_old, n_gone)
+        else:
+            assert min(k_old, n_gone) > 0, (lo, hi, k_old, n_gone)
+    return p, m, v, st
+
+
+@pytest.mark.parametrize("n,step,rest", SCALE_CASES)
+def test_scale_scenarios_put_every_kind_of_row_on_both_sides_of_the_first_scan_round(n, step, rest):
+    _scale_inputs(n, step, rest)
+
+
+# ---- hand-built rows: (largest log-scale, opacity logit, xys_grad_norm, vis_counts, max_2Dsize) ----
+def _table_inputs(rows, seed, rest=0):
+    """Parameters, moments and statistics whose decision inputs are exactly the given float32 values.  The largest
+    log-scale sits on a different axis from row to row (the others 1 and 2 below it); features_dc[:, 0] is the row
+    index, which every copy of a row carries verbatim.
+
+    The tables put the size threshold at exp(0) = 1, so a split row's children sit exp(scale) |sample| >= 1 from their
+    parent, an order of magnitude further than in _scenario, and the float32 oracle's own rounding of a rotated offset
+    then passes allclose(2e-6, 2e-6) where the offset nearly cancels the mean (measured against the oracle run in float64
+    with scales of exp(3): 1.3e-5, 5 elements over the bound).  The quaternions here are therefore axis-aligned, of
+    length 1, 2 or 4: their rotation matrices are exact diagonal sign matrices on both sides, and what is left is the rounding
+    of one exp, one product and one sum, at scales of at most 2.  Rotations by arbitrary quaternions are compared in the
+    _scenario cases."""
+    n = len(rows)
+    g = torch.Generator().manual_seed(seed)
+    col = lambda c: torch.tensor([float(r[c]) for r in rows], dtype=torch.float32)                   # noqa: E731
+    smax = col(0)
+    scales = torch.stack([smax, smax - 1.0, smax - 2.0], dim=1)
+    scales = torch.gather(scales, 1, (torch.arange(3)[None, :] + torch.arange(n)[:, None]) % 3)
+    quats = torch.eye(4)[torch.randint(0, 4, (n,), generator=g)]                  # unnormalised: length 1, 2 or 4, either sign
+    quats = quats * torch.tensor([1.0, -1.0, 2.0, -4.0])[torch.randint(0, 4, (n, 1), generator=g)]
+    p = {"means": torch.randn(n, 3, generator=g), "scales": scales, "quats": quats,
+         "opacities": col(1)[:, None].clone(), "features_dc": torch.rand(n, 3, generator=g),
+         "features_rest": torch.randn(n, rest, 3, generator=g) * 0.1}
+    p["features_dc"][:, 0] = torch.arange(n, dtype=torch.float32)
+    m = {k: torch.randn(t.shape, generator=g) * 0.01 for k, t in p.items()}
+    v = {k: torch.rand(t.shape, generator=g) * 0.01 + 1e-6 for k, t in p.items()}
+    st = D.DensifyState()
+    st.xys_grad_norm, st.vis_counts, st.max_2Dsize = col(2), col(3), col(4)
+    return p, m, v, st
+
+
+def _around(x):
+    """The float32 below x, x itself and the float32 above it."""
+    x = np.float32(x)
+    return [np.nextafter(x, np.float32(-np.inf)), x, np.nextafter(x, np.float32(np.inf))]
+
+
+# every threshold of the table as an exact float32 (the oracle and the kernel both compare in float32)
+T_GRAD, T_SPLIT_SCREEN, T_CULL_SCREEN = np.float32(0.0005), np.float32(0.05), np.float32(0.15)
+THRESHOLD_CFG = dict(densify_grad_thresh=float(T_GRAD), densify_size_thresh=1.0, cull_scale_thresh=1.0,
+                     cull_alpha_thresh=0.5, split_screen_size=float(T_SPLIT_SCREEN), cull_screen_size=float(T_CULL_SCREEN))
+# values far from every threshold
+SMALL, BIG, OPAQUE, CLEAR, HIGH, QUIET = -5.0, math.log(2.0), 4.0, -4.0, 1.0, 0.0       # (BIG / 1.6 is still above 1)
+
+
+def _threshold_rows():
+    """With last_size (2, 2) and vis_counts 1 the averaged gradient is xys_grad_norm itself; exp(0) = 1 is the size and the
+    cull-scale threshold; sigmoid(0) = 0.5 the opacity threshold.  Per comparison: the row on the threshold and its two
+    float32 neighbours, every other input of the row far from its own threshold.  Around a log-scale or a logit of 0 the
+    neighbours are denormal and still give exp = 1 and sigmoid = 0.5 exactly on both sides, so rows at +-2^-20 (8 and 16
+    float32 steps off exp = 1) and +-2^-16 (sigmoid 64 steps or more off 0.5) stand on either side as well: further than
+    the rounding of any expf."""
+    rows = []
+    for g in _around(T_GRAD):                                   # 1. > on the gradient
+        rows += [(SMALL, OPAQUE, g, 1.0, 0.0), (BIG, OPAQUE, g, 1.0, 0.0)]
+    near_zero = _around(0.0) + [-2.0 ** -20, 2.0 ** -20]
+    for s in near_zero:                                         # 2. > on the size, 3. <= for duplicates, 7. > on the cull scale
+        rows += [(s, OPAQUE, HIGH, 1.0, 0.0), (s, OPAQUE, QUIET, 1.0, 0.0)]
+    for x in _around(T_SPLIT_SCREEN):                           # 4. > on the split screen size
+        rows += [(SMALL, OPAQUE, HIGH, 1.0, x), (SMALL, OPAQUE, QUIET, 1.0, x)]
+    for x in _around(T_CULL_SCREEN):                            # 5. > on the cull screen size
+        rows += [(SMALL, OPAQUE, QUIET, 1.0, x), (SMALL, OPAQUE, HIGH, 1.0, x)]
+    for lg in _around(0.0) + [-2.0 ** -16, 2.0 ** -16]:         # 6. < on the opacity
+        rows += [(SMALL, lg, QUIET, 1.0, 0.0), (SMALL, lg, HIGH, 1.0, 0.0), (BIG, lg, HIGH, 1.0, 0.0)]
+    rows += [(math.log(1.3), OPAQUE, HIGH, 1.0, 0.0),           # split and, after the shrink (1.3 / 1.6 < 1), duplicated
+             (BIG, CLEAR, HIGH, 1.0, 0.0),                      # split with transparent children
+             (SMALL, OPAQUE, 2.0 * T_GRAD, 4.0, 0.0),           # high sum, seen 4 times: the average is half the threshold
+             (SMALL, OPAQUE, 2.0 * T_GRAD, 1.0, 0.0),
+             (BIG, OPAQUE, QUIET, 1.0, 0.0), (SMALL, CLEAR, QUIET, 1.0, 0.0), (SMALL, OPAQUE, QUIET, 1.0, 0.5),
+             (BIG, OPAQUE, HIGH, 1.0, 0.5)]
+    return rows * 6                                             # 6 x 51 rows: more than one workgroup
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -105,7 +259,7 @@ def test_oracle_schedule():
 # ---------------------------------------------------------------------------------------------------
 # GPU: kernels vs oracle
 # ---------------------------------------------------------------------------------------------------
-def _gpu_model(p, m, v, dev):
+def _gpu_model(p, m, v, dev, last_size=(1080, 1920)):
     from qed_splatter_amd.model import FlatAdam, QEDSplatterModel, QEDSplatterModelConfig
     model = QEDSplatterModel(QEDSplatterModelConfig.synthetic(), **{k: p[k].to(dev) for k in PARAM_NAMES})
     opt = FlatAdam(model)
@@ -115,7 +269,7 @@ def _gpu_model(p, m, v, dev):
         opt.exp_avg[off:off + n] = m[name].reshape(-1).to(dev)
         opt.exp_avg_sq[off:off + n] = v[name].reshape(-1).to(dev)
         off += n
-    model.last_size = (1080, 1920)
+    model.last_size = last_size
     return model, opt
 
 
@@ -128,27 +282,38 @@ def _moments(model, opt):
     return out_m, out_v
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("step,n,rest", [(700, 5000, 15), (5000, 3000, 15), (15100, 4000, 15), (3100, 1000, 15),
-                                         (700, 777, 0), (400, 100, 15)])
-def test_refinement_matches_oracle(cuda, step, n, rest):
+def _clone_state(st):
+    out = D.DensifyState()
+    out.__dict__.update({k: (t.clone() if t is not None else None) for k, t in st.__dict__.items()})
+    return out
+
+
+def _refinement_matches_oracle(dev, p, m, v, st, step, cfg_kw=None, last_size=(1080, 1920), num_train_data=10):
+    """One refinement of (p, m, v, st) on the GPU against the oracle under the same configuration: counts exact,
+    parameters within allclose(2e-6, 2e-6), moments bit for bit.  Returns the GPU side's info, model, optimiser and
+    Densifier, the oracle's parameters and the addresses of the buffers before the refinement."""
     from qed_splatter_amd.densify import DensifyConfig, Densifier
-    p, m, v, st = _scenario(n, seed=step + n, rest=rest)
-    cfg_o = D.DensifyConfig()
+    cfg_kw = cfg_kw or {}
+    n = p["means"].shape[0]
+    cfg_o = D.DensifyConfig(**cfg_kw)
     splits_guess = 4 * n
     samples_all = torch.randn(splits_guess, 3, generator=torch.Generator().manual_seed(9))
+    st2 = _clone_state(st)                                  # (the oracle drops the statistics it is handed)
     # the oracle tells how many samples are needed; both sides then use the same ones
-    probe = D.DensifyState(); probe.__dict__.update({k: (t.clone() if t is not None else None) for k, t in st.__dict__.items()})
-    _, _, _, info0 = D.refinement_after(p, m, v, probe, step, cfg_o, (1080, 1920), 10, samples_all[:0] if False else None)
+    _, _, _, info0 = D.refinement_after(p, m, v, _clone_state(st), step, cfg_o, last_size, num_train_data, None)
     ns = cfg_o.n_split_samples * info0["n_split"]
+    assert ns <= splits_guess
     samples = samples_all[:ns]
-    ref_p, ref_m, ref_v, info = D.refinement_after(p, m, v, st, step, cfg_o, (1080, 1920), 10, samples if info0["did_densify"] else None)
+    ref_p, ref_m, ref_v, info = D.refinement_after(p, m, v, st, step, cfg_o, last_size, num_train_data,
+                                                   samples if info0["did_densify"] else None)
 
-    model, opt = _gpu_model(p, m, v, cuda)
-    dz = Densifier(model, opt, DensifyConfig(), num_train_data=10)
-    p2, m2, v2, st2 = _scenario(n, seed=step + n, rest=rest)
-    dz.xys_grad_norm, dz.vis_counts, dz.max_2Dsize = (t.to(cuda) for t in (st2.xys_grad_norm, st2.vis_counts, st2.max_2Dsize))
-    got = dz.refinement_after(step, samples.to(cuda) if ns else None)
+    model, opt = _gpu_model(p, m, v, dev, last_size)
+    dz = Densifier(model, opt, DensifyConfig(**cfg_kw), num_train_data=num_train_data)
+    dz.xys_grad_norm, dz.vis_counts, dz.max_2Dsize = (t.to(dev) for t in (st2.xys_grad_norm, st2.vis_counts, st2.max_2Dsize))
+    old_ptrs = (model.flat_params.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr())
+    got = dz.refinement_after(step, samples.to(dev) if ns else None)
+    print(f"refinement N={n} step={step}: n_split={got['n_split']} n_dup={got['n_dup']} n_culled={got['n_culled']} "
+          f"n_after={got['n_after']}")
     assert got["did_densify"] == info["did_densify"] and got["opacity_reset"] == info["opacity_reset"]
     assert (got["n_split"], got["n_dup"], got["n_culled"]) == (info["n_split"], info["n_dup"], info["n_culled"])
     assert model.num_points == ref_p["means"].shape[0] == got["n_after"]
@@ -163,6 +328,182 @@ def test_refinement_matches_oracle(cuda, step, n, rest):
     # the model still trains after the swap: parameters are leaf views of one flat buffer in group order
     assert model.flat_params.numel() == sum(model.gauss_params[k].numel() for k in PARAM_NAMES)
     assert model.gauss_params["means"].data_ptr() == model.flat_params.data_ptr()
+    return SimpleNamespace(info=got, model=model, opt=opt, dz=dz, ref_p=ref_p, old_ptrs=old_ptrs)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("step,n,rest", [(700, 5000, 15), (5000, 3000, 15), (15100, 4000, 15), (3100, 1000, 15),
+                                         (700, 777, 0), (400, 100, 15)])
+def test_refinement_matches_oracle(cuda, step, n, rest):
+    p, m, v, st = _scenario(n, seed=step + n, rest=rest)
+    _refinement_matches_oracle(cuda, p, m, v, st, step)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,step,rest", SCALE_CASES)
+def test_refinement_matches_oracle_past_one_scan_round(cuda, n, step, rest):
+    """densify_scan_blocks_kernel walks the per-workgroup counts 1024 at a time and carries the base from round to round:
+    a second round exists only above 262 144 Gaussians.  A wrong base overlaps rows and leaves others unwritten."""
+    p, m, v, st = _scale_inputs(n, step, rest)
+    _refinement_matches_oracle(cuda, p, m, v, st, step)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("step", [700, 3500, 5000])
+def test_decisions_on_their_thresholds(cuda, step):
+    """Each comparison of classify_one with its input exactly on the threshold and one float32 to either side.  Step 700:
+    screen tests on, big-scale culling off; step 3500: both on (the only range where the cull screen size is read);
+    step 5000: screen tests off, big-scale culling on."""
+    p, m, v, st = _table_inputs(_threshold_rows(), seed=step)
+    r = _refinement_matches_oracle(cuda, p, m, v, st, step, THRESHOLD_CFG, last_size=(2, 2))
+    assert r.info["did_densify"] and r.info["n_split"] > 0 and r.info["n_dup"] > 0 and r.info["n_culled"] > r.info["n_split"]
+
+
+@pytest.mark.gpu
+def test_every_high_gradient_row_is_split_or_duplicated_around_the_size_threshold(cuda):
+    """Log-scales within 8 float32 steps of log(densify_size_thresh), high-gradient and quiet: whatever expf rounds to,
+    `>` for the split and `<=` for the duplicate leave no high-gradient row untouched (a split row is shrunk by 1.6 and so
+    duplicated as well) and touch no quiet one.  Rows are told apart by features_dc[:, 0], which every copy carries."""
+    from qed_splatter_amd.densify import DensifyConfig, Densifier
+    cfg = DensifyConfig()
+    s = np.float32(math.log(cfg.densify_size_thresh))
+    sweep = [s]
+    for _ in range(8):
+        sweep = [np.nextafter(sweep[0], np.float32(-np.inf))] + sweep + [np.nextafter(sweep[-1], np.float32(np.inf))]
+    rows = [(x, OPAQUE, g, 1.0, 0.0) for x in sweep for g in (HIGH, QUIET)] * 16          # 544 rows: three workgroups
+    n = len(rows)
+    p, m, v, st = _table_inputs(rows, seed=4)
+    high = st.xys_grad_norm > 0.5
+    model, opt = _gpu_model(p, m, v, cuda, (2, 2))
+    dz = Densifier(model, opt, cfg, num_train_data=10)
+    dz.xys_grad_norm, dz.vis_counts, dz.max_2Dsize = (t.to(cuda) for t in (st.xys_grad_norm, st.vis_counts, st.max_2Dsize))
+    info = dz.refinement_after(700)
+    n_high, n_split = int(high.sum()), info["n_split"]
+    assert info["n_dup"] == n_high and 0 <= n_split <= n_high and info["n_culled"] == n_split
+    k_old = n - n_split
+    assert info["n_after"] == model.num_points == k_old + cfg.n_split_samples * n_split + n_high
+    ids = model.features_dc.detach()[:, 0].long().cpu()
+    old, children, dups = ids[:k_old], ids[k_old:k_old + cfg.n_split_samples * n_split], ids[k_old + cfg.n_split_samples * n_split:]
+    assert torch.equal(dups, torch.nonzero(high).reshape(-1))                      # every high-gradient row, in order
+    assert bool(high[children].all())
+    split_ids = children[:n_split]
+    assert torch.equal(children, split_ids.repeat(cfg.n_split_samples))            # sample-major, each child once
+    kept = torch.ones(n, dtype=torch.bool)
+    kept[split_ids] = False
+    assert torch.equal(old, torch.nonzero(kept).reshape(-1))                       # quiet rows and unsplit ones stay
+    gm, _ = _moments(model, opt)
+    assert torch.equal(gm["means"][:k_old], m["means"][kept]) and float(gm["means"][k_old:].abs().sum()) == 0.0
+
+
+# ---- shapes of the outcome ----
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_split_samples,n", [(1, 257), (3, 255), (3, 1500)])
+def test_other_numbers_of_split_samples(cuda, n_split_samples, n):
+    p, m, v, st = _scenario(n, seed=n + n_split_samples, rest=3)
+    r = _refinement_matches_oracle(cuda, p, m, v, st, 700, dict(n_split_samples=n_split_samples))
+    assert r.info["n_split"] > 0
+
+
+def _uniform_rows(n, kinds):
+    return [kinds[i % len(kinds)] for i in range(n)]
+
+
+@pytest.mark.gpu
+def test_refinement_that_keeps_nothing(cuda):
+    """All rows transparent (some of them split or duplicated first): 0 Gaussians, empty buffers in the model and in
+    FlatAdam, and the next refinement has nothing to launch."""
+    n = 256
+    rows = _uniform_rows(n, [(SMALL, CLEAR, QUIET, 1.0, 0.0), (BIG, CLEAR, HIGH, 1.0, 0.0), (SMALL, CLEAR, HIGH, 1.0, 0.0)])
+    p, m, v, st = _table_inputs(rows, seed=1, rest=2)
+    r = _refinement_matches_oracle(cuda, p, m, v, st, 700, THRESHOLD_CFG, last_size=(2, 2))
+    assert r.info["n_split"] > 0 and r.info["n_dup"] > 0 and r.info["n_after"] == 0 == r.model.num_points
+    assert r.model.flat_params.numel() == r.opt.exp_avg.numel() == r.opt.exp_avg_sq.numel() == 0
+    assert all(r.model.gauss_params[k].shape[0] == 0 for k in PARAM_NAMES)
+    flat = r.model.flat_params
+    r.dz.xys_grad_norm, r.dz.max_2Dsize = (torch.zeros(0, device=cuda) for _ in range(2))
+    r.dz.vis_counts = torch.ones(0, device=cuda)
+    info = r.dz.refinement_after(800)
+    assert (info["n_before"], info["n_after"], info["n_split"], info["n_dup"], info["n_culled"]) == (0, 0, 0, 0, 0)
+    assert r.model.flat_params is flat and r.dz.vis_counts is None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_refinement_that_changes_nothing(cuda, n):
+    """All rows quiet and opaque: the parameters and the moments come back bit for bit, in new buffers."""
+    p, m, v, st = _table_inputs(_uniform_rows(n, [(SMALL, OPAQUE, QUIET, 1.0, 0.0)]), seed=n, rest=2)
+    r = _refinement_matches_oracle(cuda, p, m, v, st, 700, THRESHOLD_CFG, last_size=(2, 2))
+    assert (r.info["n_split"], r.info["n_dup"], r.info["n_culled"], r.info["n_after"]) == (0, 0, 0, n)
+    gm, gv = _moments(r.model, r.opt)
+    for name in PARAM_NAMES:
+        assert torch.equal(r.model.gauss_params[name].detach().cpu(), p[name]), name
+        assert torch.equal(gm[name], m[name]) and torch.equal(gv[name], v[name]), name
+    new_ptrs = (r.model.flat_params.data_ptr(), r.opt.exp_avg.data_ptr(), r.opt.exp_avg_sq.data_ptr())
+    assert not set(new_ptrs) & set(r.old_ptrs)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_every_row_splits_and_keeps_its_children(cuda, n):
+    """No old row survives (k_old = 0): the children start at row 0 of the new buffers."""
+    p, m, v, st = _table_inputs(_uniform_rows(n, [(BIG, OPAQUE, HIGH, 1.0, 0.0)]), seed=n, rest=2)
+    r = _refinement_matches_oracle(cuda, p, m, v, st, 700, THRESHOLD_CFG, last_size=(2, 2))
+    assert (r.info["n_split"], r.info["n_dup"], r.info["n_culled"], r.info["n_after"]) == (n, 0, n, 2 * n)
+    assert float(r.opt.exp_avg.abs().sum()) == 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_every_split_row_is_transparent(cuda, n):
+    """n_split > 0 needs its samples although no child is written (k_child = 0); the quiet rows stay."""
+    rows = _uniform_rows(n, [(BIG, CLEAR, HIGH, 1.0, 0.0), (SMALL, OPAQUE, QUIET, 1.0, 0.0), (BIG, CLEAR, HIGH, 1.0, 0.0)])
+    p, m, v, st = _table_inputs(rows, seed=n, rest=2)
+    r = _refinement_matches_oracle(cuda, p, m, v, st, 700, THRESHOLD_CFG, last_size=(2, 2))
+    n_split = sum(1 for row in rows if row[0] == BIG)
+    assert (r.info["n_split"], r.info["n_dup"], r.info["n_after"]) == (n_split, 0, n - n_split)
+    assert r.info["n_culled"] == 3 * n_split
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_only_duplicates(cuda, n):
+    p, m, v, st = _table_inputs(_uniform_rows(n, [(SMALL, OPAQUE, HIGH, 1.0, 0.0)]), seed=n, rest=2)
+    r = _refinement_matches_oracle(cuda, p, m, v, st, 700, THRESHOLD_CFG, last_size=(2, 2))
+    assert (r.info["n_split"], r.info["n_dup"], r.info["n_culled"], r.info["n_after"]) == (0, n, 0, 2 * n)
+    ids = r.model.features_dc.detach()[:, 0].cpu()
+    assert torch.equal(ids, torch.arange(n, dtype=torch.float32).repeat(2))
+
+
+# ---- qed_densify_accumulate through the C ABI ----
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,stride", [(1, 2), (255, 7), (257, 2), (5000, 7)])
+def test_accumulate_through_the_abi_matches_oracle(cuda, n, stride):
+    """Three successive calls with different image sizes on a strided view of absgrad, radii with zeros and negatives:
+    vis_counts exact, the float sums within rtol 1e-5, the running maximum of max_2Dsize."""
+    from qed_splatter_amd import _lib as L
+    lib = L.load()
+    g = torch.Generator().manual_seed(n + stride)
+    st = D.DensifyState()
+    grad_norm = torch.zeros(n, device=cuda)
+    vis_counts = torch.ones(n, device=cuda)
+    max_2d = torch.zeros(n, device=cuda)
+    for call, last_size in enumerate([(1080, 1920), (512, 384), (300, 200)]):
+        base = torch.rand(n, stride, generator=g) * 10.0 ** -call           # columns 2.. : never read
+        radii = torch.randint(-3, 60, (n,), generator=g).int()
+        radii[torch.rand(n, generator=g) < 0.3] = 0
+        if n == 1:
+            radii[0] = [7, 0, 40][call]
+        absgrad, radii_dev = base.to(cuda)[:, :2], radii.to(cuda)
+        assert absgrad.stride() == (stride, 1)
+        L.check(lib.qed_densify_accumulate(n, L.ptr(absgrad), stride, L.ptr(radii_dev), 1.0 / float(max(last_size)),
+                                           L.ptr(grad_norm), L.ptr(vis_counts), L.ptr(max_2d), L.current_stream()),
+                "qed_densify_accumulate")
+        D.after_train(st, base[:, :2].double(), radii, last_size, 10 + call, D.DensifyConfig())
+    torch.cuda.synchronize()
+    assert torch.equal(vis_counts.cpu(), st.vis_counts)
+    torch.testing.assert_close(grad_norm.cpu(), st.xys_grad_norm, rtol=1e-5, atol=1e-9)
+    torch.testing.assert_close(max_2d.cpu(), st.max_2Dsize)
+    assert n == 1 or (bool((st.vis_counts == 1).any()) and bool((st.vis_counts == 4).any()))
 
 
 @pytest.mark.gpu

@@ -176,11 +176,13 @@ def _relocation_sources(p, seed):
 # ---------------------------------------------------------------------------------------------------
 # GPU: relocation / add against the restatement
 # ---------------------------------------------------------------------------------------------------
-@pytest.mark.gpu
-def test_relocate_matches_reference(cuda):
+SCAN_ROUND_ROWS = 1024 * 256          # rows one round of mcmc_scan_blocks_kernel covers: 1024 workgroups of 256
+N_TWO_ROUNDS = SCAN_ROUND_ROWS + 257  # a second round that holds two workgroups, the last one with one row
+
+
+def _relocate_matches_reference(cuda, n, rest):
     from qed_splatter_amd.mcmc import McmcStrategy
-    n = 4000
-    p = _params(n, seed=1, dead_frac=0.1)
+    p = _params(n, seed=1, dead_frac=0.1, rest=rest)
     m, v = _moments(p, seed=2)
     model, opt = _model(p, cuda)
     _set_moments(model, opt, m, v)
@@ -213,14 +215,24 @@ def test_relocate_matches_reference(cuda):
     # unchanged groups of the sources
     for name in ("means", "quats", "features_dc", "features_rest"):
         assert torch.equal(gp[name][drawn], p[name][drawn]), name
+    return int(n_dead)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["flat", "qed"])
-def test_add_matches_reference(cuda, kind):
+def test_relocate_matches_reference(cuda):
+    _relocate_matches_reference(cuda, 4000, 15)
+
+
+@pytest.mark.gpu
+def test_relocate_matches_reference_past_one_scan_round(cuda):
+    """The dead count is summed over the rounds of mcmc_scan_blocks_kernel: two rounds at 262 401 rows."""
+    n_dead = _relocate_matches_reference(cuda, N_TWO_ROUNDS, 0)
+    print(f"relocate N={N_TWO_ROUNDS}: n_dead={n_dead}")
+
+
+def _add_matches_reference(cuda, kind, n, rest):
     from qed_splatter_amd.mcmc import McmcConfig, McmcStrategy
-    n = 3000
-    p = _params(n, seed=4, dead_frac=0.0)
+    p = _params(n, seed=4, dead_frac=0.0, rest=rest)
     m, v = _moments(p, seed=5)
     results = []
     model, opt = _model(p, cuda, kind)
@@ -233,7 +245,7 @@ def test_add_matches_reference(cuda, kind):
     added = strat.add(sources=sources.to(cuda))
     torch.cuda.synchronize()
     assert added == n_add and model.num_points == int(1.05 * n)
-    widths = [3, 3, 4, 1, 3, 45]
+    widths = [3, 3, 4, 1, 3, 3 * rest]
     assert model.group_begin == [sum(w * model.num_points for w in widths[:i]) for i in range(7)]
     rp, rm, rv = R.add(p, m, v, sources, MIN_OP)
     gp, gm, gv = _groups(model, model.flat_params), _groups(model, opt.exp_avg), _groups(model, opt.exp_avg_sq)
@@ -261,6 +273,17 @@ def test_add_matches_reference(cuda, kind):
         McmcStrategy(model2, opt2, McmcConfig(cap_max=10 ** 6), seed=1).add(sources=sources.to(cuda))
         assert torch.equal(model2.flat_params.cpu(), results[0])
         assert torch.equal(opt2.exp_avg.cpu(), opt.exp_avg.cpu())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["flat", "qed"])
+def test_add_matches_reference(cuda, kind):
+    _add_matches_reference(cuda, kind, 3000, 15)
+
+
+@pytest.mark.gpu
+def test_add_matches_reference_past_one_scan_round(cuda):
+    _add_matches_reference(cuda, "flat", N_TWO_ROUNDS, 0)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -295,6 +318,60 @@ def test_sampler_distribution_and_determinism(cuda):
     expected = w / w.sum() * draws
     chi2 = float(((counts[live] - expected) ** 2 / expected).sum())
     p = _chi2_sf(chi2, int(live.sum()) - 1)
+    assert p > 1e-3, (chi2, p)
+
+
+# The draws are a function of (seed, counter, index): each outcome below is fixed once and for all.  Seed and counter of
+# the test above; had a case come out below 1e-3, counters 4 and 5 would tell chance (one of three) from a defect (all).
+SAMPLER_SEED, SAMPLER_COUNTER = 11, 3
+
+
+@pytest.mark.gpu
+def test_sampler_exact_weights_past_three_scan_rounds(cuda):
+    """Nine live rows of sigmoid(0) = 0.5, weight 2^31 each, at the ends of workgroups and of scan rounds; every other row
+    dead.  The expected distribution is exactly uniform over the nine, and a base lost between rounds makes the prefix
+    non-monotone: the binary search then lands on dead rows."""
+    from qed_splatter_amd.mcmc import sample
+    n = 3 * SCAN_ROUND_ROWS + 77
+    live = [0, 255, 256, SCAN_ROUND_ROWS - 1, SCAN_ROUND_ROWS, SCAN_ROUND_ROWS + 1, 2 * SCAN_ROUND_ROWS - 1,
+            2 * SCAN_ROUND_ROWS, n - 1]
+    logits = torch.full((n,), math.log(0.001 / 0.999))
+    logits[live] = 0.0
+    draws = 90_000
+    dev_logits = logits.to(cuda)
+    a = sample(dev_logits, draws, min_opacity=MIN_OP, seed=SAMPLER_SEED, counter=SAMPLER_COUNTER)
+    b = sample(dev_logits, draws, min_opacity=MIN_OP, seed=SAMPLER_SEED, counter=SAMPLER_COUNTER)
+    assert torch.equal(a, b)
+    counts = torch.bincount(a.long().cpu(), minlength=n).double()
+    assert int(a.min()) >= 0 and int(a.max()) < n
+    assert float(counts[live].sum()) == draws, sorted(set(torch.nonzero(counts).reshape(-1).tolist()) - set(live))[:20]
+    expected = draws / len(live)
+    chi2 = float(((counts[live] - expected) ** 2 / expected).sum())
+    p = _chi2_sf(chi2, len(live) - 1)
+    print(f"sampler, nine exact weights in N={n}: chi2={chi2:.3f} p={p:.4f}")
+    assert p > 1e-3, (chi2, p)
+
+
+@pytest.mark.gpu
+def test_sampler_dense_past_one_scan_round(cuda):
+    """Every row weighted, a tenth of them dead, two scan rounds: no dead row is drawn, and the draws fall into 64 equal
+    index ranges in proportion to the float64 sums of sigmoid over the live rows of each."""
+    from qed_splatter_amd.mcmc import sample
+    n, draws, bins = N_TWO_ROUNDS, 1_000_000, 64
+    logits = _params(n, seed=1, dead_frac=0.1, rest=0)["opacities"][:, 0].contiguous()
+    a = sample(logits.to(cuda), draws, min_opacity=MIN_OP, seed=SAMPLER_SEED, counter=SAMPLER_COUNTER).long().cpu()
+    assert int(a.min()) >= 0 and int(a.max()) < n
+    sig = torch.sigmoid(logits.double())
+    live = sig > MIN_OP
+    assert 0.05 * n < int((~live).sum()) < 0.15 * n
+    assert bool(live[a].all())                                    # dead rows never drawn
+    which = torch.arange(n) * bins // n                           # 64 ranges of 4100 or 4101 rows
+    w = torch.zeros(bins, dtype=torch.float64).index_add_(0, which, torch.where(live, sig, torch.zeros_like(sig)))
+    expected = w / w.sum() * draws
+    counts = torch.bincount(which[a], minlength=bins).double()
+    chi2 = float(((counts - expected) ** 2 / expected).sum())
+    p = _chi2_sf(chi2, bins - 1)
+    print(f"sampler, dense N={n}: chi2={chi2:.3f} p={p:.4f}")
     assert p > 1e-3, (chi2, p)
 
 
