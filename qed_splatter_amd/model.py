@@ -45,7 +45,8 @@ from .optim import FlatAdam, QedAdam, QedAdamSet, exponential_decay_lr  # noqa: 
 from .optim import _RAW_GRAD, _all_groups_stepped_by_qed_adam, _raw_grad
 from .optim import _FLAT_STATES  # noqa: F401  (the registry object itself: tests stand in for QedAdam through it)
 from .binning import _workspace
-from .rasterization import rasterization, _stream
+from .rasterization import rasterization
+from .sh_grad import CompactSHGrad
 
 
 _FLIP_CACHE: Dict = {}
@@ -212,15 +213,19 @@ class StepContext:
       * ``ssim``: get_metrics_dict's SSIM forward on (rgb, ground truth) with the maps and sums the loss needs -- taken ONCE
         (``take_ssim``) and checked against the tensors the loss is actually handed before it is used;
       * ``handover``: the step's ``handover.Handover``: the loss's backward launch hands the compositing backward a zero-filled
-        gradient accumulator through it -- claimed once; a second loss on the same outputs makes the backward fill its own."""
+        gradient accumulator through it -- claimed once; a second loss on the same outputs makes the backward fill its own.
 
-    __slots__ = ("rgb", "handover", "_gt", "ssim")
+    And two facts about the forward call itself, which the data-parallel exchanges refuse (parallel.py):
+    ``pose_optimizer`` / ``grid_optimizer``, the camera and bilateral-grid optimisers ``fused_loss`` ran with."""
 
-    def __init__(self):
+    __slots__ = ("rgb", "handover", "_gt", "ssim", "pose_optimizer", "grid_optimizer")
+
+    def __init__(self, pose_optimizer=None, grid_optimizer=None):
         self.rgb = None
         self.handover = None
         self._gt = None
         self.ssim = None
+        self.pose_optimizer, self.grid_optimizer = pose_optimizer, grid_optimizer
 
     def owns(self, outputs) -> bool:
         return self.rgb is not None and outputs.get("rgb") is self.rgb
@@ -240,16 +245,6 @@ class StepContext:
     def take_ssim(self):
         shared, self.ssim = self.ssim, None
         return shared
-
-
-def write_sh_grads(means: Tensor, viewmat: Tensor, sh_degree: int, v_color: Tensor, v_rest: Tensor) -> None:
-    """In place: ``v_color`` [N,3] (the clamp-masked colour gradient qed_project_bwd leaves with QED_F_SH_GRAD_COMPACT)
-    becomes the gradient of features_dc, ``v_rest`` [N,KR,3] receives the active coefficients' gradients (one view)."""
-    n = v_color.shape[0]
-    with torch.no_grad():
-        L.check(L.load().qed_sh_grad_from_views(
-            n, 1, L.ptr(means), L.ptr(viewmat), 16, L.ptr(v_color), 3 * n, int(sh_degree), 1.0,
-            L.ptr(v_color), 3, L.ptr(v_rest), v_rest.numel() // max(n, 1), _stream()), "qed_sh_grad_from_views")
 
 
 def _reference_key_order(metrics: Dict) -> Dict:
@@ -274,18 +269,20 @@ def _has_grad_hooks(p: Tensor) -> bool:
 
 class _LazySHGradParameter(nn.Parameter):
     """features_dc / features_rest of a flat-buffer model.  A backward pass may leave their gradients in the compact form
-    (QEDSplatterModel._lazy_sh: clamp-masked colour gradient + view); the autograd engine then stores the views of the flat
+    (QEDSplatterModel.compact_sh: clamp-masked colour gradient + view); the autograd engine then stores the views of the flat
     gradient allocation in the ``.grad`` FIELD as always, but the memory does not hold the coefficient gradients yet.
     ``.grad`` read from Python first writes them there (one qed_sh_grad_from_views launch, in place), so every reader --
     torch.optim.*, clip_grad_norm_, GradScaler.unscale_, logging -- sees what the reference's backward pass produces; only
-    QedAdam, which evaluates the product itself, looks at the field without asking for that."""
+    QedAdam, which evaluates the product itself, looks at the field without asking for that.  (A form the caller asked for,
+    fused_loss(compact_sh_grad=True), is the caller's to consume: reads and writes of the fields leave that record alone.)"""
 
     @property
     def grad(self):
         owner = self.__dict__.get("_qed_owner")
         if owner is not None:
             m = owner()
-            if m is not None and m.__dict__.get("_lazy_sh") is not None:
+            rec = m.__dict__.get("compact_sh") if m is not None else None
+            if rec is not None and rec.implicit:
                 m._materialise_sh_grads()
         return _RAW_GRAD.__get__(self)
 
@@ -293,11 +290,13 @@ class _LazySHGradParameter(nn.Parameter):
     def grad(self, value):
         owner = self.__dict__.get("_qed_owner")
         m = owner() if owner is not None else None
-        if m is not None and m.__dict__.get("_lazy_sh") is not None:
+        rec = m.__dict__.get("compact_sh") if m is not None else None
+        if rec is not None and rec.implicit:
             if value is not None:                    # (somebody assigns one of the two: give the other its values first)
                 m._materialise_sh_grads()
             _RAW_GRAD.__set__(self, value)
-            m._lazy_sh_dropped()
+            if _raw_grad(m.gauss_params["features_dc"]) is None and _raw_grad(m.gauss_params["features_rest"]) is None:
+                m.__dict__["compact_sh"] = None      # (both fields are empty: the compact form is gone)
             return
         _RAW_GRAD.__set__(self, value)
 
@@ -324,6 +323,9 @@ class QEDSplatterModel(nn.Module):
         self.step = 0
         self.crop_box = None
         self.camera_optimizer = None
+        # the sh_grad.CompactSHGrad of the backward pass that left the SH gradients compact; None exactly when the .grad
+        # fields of features_dc / features_rest hold full gradients
+        self.compact_sh = None
         if separate_params:
             # Six independent tensors, as Nerfstudio's parent class holds them (model.py:12,50-58; one optimiser per
             # group, config.py:44-68).  get_outputs / get_loss_dict / fused_loss run unchanged; what needs the flat
@@ -421,16 +423,27 @@ class QEDSplatterModel(nn.Module):
         p._qed_owner = weakref.ref(self)
         return p
 
-    # ---- lazy SH gradients (config.lazy_sh_grad) ----
+    # ---- compact SH gradients (sh_grad.py; config.lazy_sh_grad) ----
+    def _resolve_sh_grad(self) -> bool:
+        """Asked by every forward call.  A compact record belongs to the backward pass that wrote it and to the ``.grad``
+        fields, so a forward without grad or in eval mode (a viewer's render between backward and step) leaves it alone.
+        A training forward with grad enabled is followed by a backward pass that is ADDED to the fields (no zero_grad in
+        between): an implicit record is completed now (True: gradients wait in the fields), an explicit one gives way to
+        the new step's own state."""
+        rec = self.__dict__.get("compact_sh")
+        if rec is None or not (self.training and torch.is_grad_enabled()):
+            return False
+        if rec.implicit:
+            self._materialise_sh_grads()
+        self.__dict__["compact_sh"] = None
+        return rec.implicit
+
     def _lazy_sh_wanted(self, sh_degree_to_use, crop_ids) -> bool:
         """May THIS training step's backward pass leave the SH gradients compact?  Only when all six groups of the flat
         buffer are stepped by QedAdam instances (their fused launch runs the SH groups before it moves the means the SH basis
         is evaluated at), nothing waits in the two ``.grad`` fields and the whole Gaussian set is rendered."""
         attrs = self.__dict__
-        if attrs.get("_lazy_sh") is not None and self.training and torch.is_grad_enabled():
-            # an earlier backward pass's compact gradients are still in the fields (no zero_grad in between): the pass that
-            # follows this forward will be ADDED to them, so they are completed now
-            self._materialise_sh_grads()
+        if attrs.get("compact_sh") is not None and self._resolve_sh_grad():
             return False
         if not (self.config.lazy_sh_grad and self.training and sh_degree_to_use is not None and crop_ids is None
                 and attrs.get("_flat") is not None and torch.is_grad_enabled()):
@@ -449,48 +462,28 @@ class QEDSplatterModel(nn.Module):
             return False
         if not _all_groups_stepped_by_qed_adam(self._flat, len(self.group_names)):
             return False
-        return attrs.get("_lazy_sh") is None and _raw_grad(dc) is None and _raw_grad(rest) is None
+        return _raw_grad(dc) is None and _raw_grad(rest) is None
 
     def _lazy_sh_begin(self, v_sh0: Tensor, v_shN: Optional[Tensor], viewmats: Tensor, sh_degree: int) -> bool:
         """Asked by the projection backward (rasterization(_lazy_sh=...)) right before its launch: True = write the compact
-        form into ``v_sh0`` (and leave ``v_shN``'s active coefficients unwritten), recorded here until it is consumed
-        (QedAdam), materialised (a ``.grad`` read) or dropped (``.grad = None``).  False (gradients of an earlier backward
-        pass are waiting in the fields: autograd is about to ADD to them): those are completed first and this pass writes
-        full gradients."""
+        form into ``v_sh0`` (and leave ``v_shN``'s active coefficients unwritten), recorded in ``compact_sh`` until it is
+        consumed (QedAdam), materialised (a ``.grad`` read) or dropped (``.grad = None``).  False (gradients of an earlier
+        backward pass are waiting in the fields: autograd is about to ADD to them): those are completed first and this pass
+        writes full gradients."""
         dc, rest = self.gauss_params["features_dc"], self.gauss_params["features_rest"]
-        if self.__dict__.get("_lazy_sh") is not None:
+        if self.__dict__.get("compact_sh") is not None:
             self._materialise_sh_grads()
             return False
         if _raw_grad(dc) is not None or _raw_grad(rest) is not None or v_shN is None or viewmats.shape[0] != 1:
             return False
-        means = self.gauss_params["means"]
-        # (aliases of the two views, not the objects themselves: the engine adopts an incoming gradient as the .grad field
-        # without a copy only while nobody else holds that tensor object -- a reference kept here would make it clone)
-        self.__dict__["_lazy_sh"] = {"v_color": v_sh0.detach(), "v_rest": v_shN.detach(), "viewmat": viewmats,
-                                     "deg": int(sh_degree),
-                                     "n": int(v_sh0.shape[0]), "means_version": means._version,
-                                     "means_ptr": means.data_ptr()}
+        self.__dict__["compact_sh"] = CompactSHGrad(viewmats, sh_degree, True, v_sh0, v_shN, self.gauss_params["means"])
         return True
 
-    def _lazy_sh_dropped(self) -> None:
-        """A ``.grad`` field of the two was overwritten: with both empty the compact form is gone."""
-        if _raw_grad(self.gauss_params["features_dc"]) is None and _raw_grad(self.gauss_params["features_rest"]) is None:
-            self.__dict__["_lazy_sh"] = None
-
     def _materialise_sh_grads(self) -> None:
-        """Write the coefficient gradients the compact form stands for into the very allocation the ``.grad`` fields view
-        (features_dc: b_0 x colour gradient in place of the colour gradient; features_rest: the active coefficients)."""
-        rec = self.__dict__.get("_lazy_sh")
-        if rec is None:
-            return
-        self.__dict__["_lazy_sh"] = None
-        means = self.gauss_params["means"]
-        if means._version != rec["means_version"] or means.data_ptr() != rec["means_ptr"] or means.shape[0] != rec["n"]:
-            raise RuntimeError(
-                "lazy SH gradients: the means were modified after the backward pass and before the gradients of features_dc "
-                "/ features_rest were read (the SH basis is evaluated at the means of the forward pass).  Step all six groups "
-                "with QedAdam, read the gradients before stepping, or set config.lazy_sh_grad = False")
-        write_sh_grads(means, rec["viewmat"], rec["deg"], rec["v_color"], rec["v_rest"])
+        """Have a pending implicit record write the full gradients in place (CompactSHGrad.write_out); it ends there."""
+        rec = self.__dict__.get("compact_sh")
+        if rec is not None and rec.implicit:
+            rec.write_out(self)
 
     def rebind_flat(self, flat: Tensor, n_points: int) -> None:
         """Adopt a new flat parameter buffer (densification changes N): the six Parameters are
@@ -509,7 +502,7 @@ class QEDSplatterModel(nn.Module):
             begin.append(off)
         self._flat = flat
         self.group_begin = begin
-        self.__dict__["_lazy_sh"] = None
+        self.__dict__["compact_sh"] = None
         self.gauss_params = nn.ParameterDict(params)
 
     # ---- parameter groups (same names as the reference reads at model.py:227-239) ----
@@ -897,7 +890,6 @@ class QEDSplatterModel(nn.Module):
         # dict the reference stores as self.info (model.py:267) -- and can drop that iteration's step / restore its state
         info["intersection_overflow_previous_frame"] = _workspace(self.device).take_overflow_flag()
         attrs["info"] = info
-        attrs["last_compact"] = False
         if self.training and info["means2d"].requires_grad:                   # model.py:289-290 (a no-op on the leaf)
             info["means2d"].retain_grad()
         attrs["xys"] = info["means2d"]                                        # [1,N,2]
@@ -1159,14 +1151,14 @@ class QEDSplatterModel(nn.Module):
                 raise NotImplementedError("a bilateral-grid optimiser inside a captured step (graph.py, segments.py): the "
                                           "grid's index and the learning rate are host arguments of its launches")
             grid_opt = grid_optimizer
-        if self.__dict__.get("_lazy_sh") is not None and torch.is_grad_enabled():
-            self._materialise_sh_grads()          # (compact gradients of a get_outputs step nobody consumed: see there)
-        cfg = self.config
-        self.__dict__["_step"] = StepContext()   # (conversions of the batch are shared within a step, never across steps)
         attrs = self.__dict__            # (plain attributes, as in get_outputs)
+        if attrs.get("compact_sh") is not None:
+            self._resolve_sh_grad()               # (compact gradients of an earlier step nobody consumed: see there)
+        cfg = self.config
         pose_opt = camera_optimizer if (camera_optimizer is not None and camera_optimizer.active and self.training) else None
-        attrs["pose_optimizer"] = pose_opt       # (parallel.py refuses a data-parallel step behind it)
-        attrs["grid_optimizer"] = grid_opt       # (likewise)
+        # (conversions of the batch are shared within a step, never across steps; parallel.py refuses a data-parallel step
+        # behind either optimiser)
+        attrs["_step"] = StepContext(pose_opt, grid_opt)
         grid_idx = None
         if grid_opt is not None:
             grid_idx = cam_idx
@@ -1196,9 +1188,10 @@ class QEDSplatterModel(nn.Module):
             # data parallel: features_dc.grad then holds the clamp-masked colour gradient and features_rest.grad
             # is not written; parallel.exchange_grads_compact() rebuilds both from all ranks' views
             flags |= L.F_SH_GRAD_COMPACT
-        attrs["last_viewmat"] = None
-        attrs["last_compact"] = bool(flags & L.F_SH_GRAD_COMPACT)
-        attrs["sh_views"] = None              # set by parallel.exchange_grads_compact(rebuild=False)
+            if torch.is_grad_enabled():
+                # the record of the backward pass that can follow: this rank's view (``viewmat`` is filled by the projection
+                # kernel); parallel.exchange_grads_compact(rebuild=False) adds the gathered views
+                attrs["compact_sh"] = CompactSHGrad(viewmat, deg)
         bg = (background if background is not None else self._get_background_color()).to(self.device, torch.float32)
         gt_rgb, gt_depth, mask = self._ground_truth(batch, bg, H, W)           # exactly as get_loss_dict prepares it
         # strategy="mcmc": the two regularisers of get_loss_dict, folded into ``loss``; their gradient is added to the flat
@@ -1230,7 +1223,6 @@ class QEDSplatterModel(nn.Module):
                 _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd,
                 _pose_grad=pose_opt.pose_grad if (pose_opt is not None and torch.is_grad_enabled()) else None)
             attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
-            attrs["last_viewmat"], attrs["last_sh_degree"] = viewmat, deg
             # (the compositing node keeps the forward pass's per-tile costs: the loss launch sorts them for its backward)
             tile_cost = getattr(render.grad_fn, "tile_cost", None) if torch.is_grad_enabled() else None
             total, parts = _FusedImageLoss.apply(render, alpha, bg.contiguous(), gt_rgb, gt_depth, mask,
@@ -1277,7 +1269,6 @@ class QEDSplatterModel(nn.Module):
             _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd, _post_background=bg,
             _pose_grad=pose_opt.pose_grad if (pose_opt is not None and grad) else None)
         attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
-        attrs["last_viewmat"], attrs["last_sh_degree"] = viewmat, deg
         rgb, tv = grid_opt.begin_fused(info.pop("post_rgb"), grid_idx, H, W)
         depth = info.pop("post_depth")
         main, depth_loss = _ImageLosses.apply(rgb.squeeze(0), depth.squeeze(0), gt_rgb, gt_depth, mask,

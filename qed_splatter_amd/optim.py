@@ -14,7 +14,9 @@ from torch import Tensor
 
 from . import _lib as L
 from .binning import _workspace
+from .parallel import exchange_state
 from .rasterization import _stream
+from .sh_grad import explicit_record
 
 
 _RAW_GRAD = torch.Tensor.grad                 # the C-level descriptor: reads / writes the field without the subclass's hooks
@@ -82,7 +84,7 @@ class FlatAdam:
         Not in a data-parallel job: there the skip is collective (parallel.py) but only the rank whose frame overflowed
         hears of it on the host -- taking the step back here alone would make the replicas' bias corrections differ.  All
         ranks' host counters then run one ahead of the moments together; step with device_state=True for exact counts."""
-        if getattr(self.model, "_dp_skip", None) is not None:
+        if exchange_state(self.model).skip is not None:
             return
         self.t = max(self.t - 1, 0)
 
@@ -114,7 +116,7 @@ class FlatAdam:
         """``skip_flag`` of the Adam entry points: the binning overflow word of this device (a frame whose intersection
         list overflowed renders empty; a step enqueued behind it without a host round trip must be a no-op)."""
         # data parallel: the MAXIMUM of the ranks' words, so that every replica skips the same steps (parallel.py)
-        dp = getattr(self.model, "_dp_skip", None)
+        dp = exchange_state(self.model).skip
         if dp is not None:
             return dp.data_ptr()
         return _workspace(self.model.device).skip_flag_ptr()
@@ -173,7 +175,7 @@ class FlatAdam:
         if m.flat_params is not self._flat_ref or m.flat_params.device != self.exp_avg.device:
             raise RuntimeError(f"FlatAdam.{who}: the model adopted a new flat parameter buffer (model.to() or "
                                "densification); call rebind(exp_avg, exp_avg_sq) or build a new optimiser")
-        if not compact_ok and getattr(m, "last_compact", False):
+        if not compact_ok and explicit_record(m) is not None:
             raise RuntimeError(f"FlatAdam.{who}: the last backward wrote compact SH gradients "
                                "(fused_loss(compact_sh_grad=True)); step with fused_sh=True")
 
@@ -240,14 +242,10 @@ class FlatAdam:
             _counted_step(self, self.model.device)
         if fused_sh:
             m = self.model
-            if not getattr(m, "last_compact", False):
+            rec = explicit_record(m)
+            if rec is None:
                 raise RuntimeError("fused_sh needs gradients from fused_loss(..., compact_sh_grad=True)")
             assert m.group_names[-2:] == ["features_dc", "features_rest"]
-            views = m.sh_views
-            if views is None:                                    # this rank's view only
-                b = m.group_begin
-                views = (1, m.last_viewmat, 16, g[b[-3]:b[-2]], 0, 1.0)
-            n_views, viewmats, vm_stride, v_views, view_stride, scale = views
             if getattr(self, "_ticked", False) and (part & 1):       # take_tick(): the state is advanced already
                 if not device_state:
                     raise RuntimeError("the device step state was advanced by fused_loss(optimizer=...): step with "
@@ -257,9 +255,8 @@ class FlatAdam:
                 L.ptr(p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), len(self.lr),
                 C.cast(self._begin, C.c_void_p), None if device_state else C.cast(self._lr, C.c_void_p),
                 L.ptr(self.dev_lr) if device_state else None, self.betas[0], self.betas[1], self.eps, self.t,
-                L.ptr(self.dev_state) if device_state else None, *sched, m.num_points, int(m.last_sh_degree or 0),
-                L.ptr(m.means), n_views, L.ptr(viewmats), vm_stride, L.ptr(v_views), view_stride, float(scale),
-                int(part), self._skip(), _stream()), "qed_adam_step_sh")
+                L.ptr(self.dev_state) if device_state else None, *sched, m.num_points, rec.deg, L.ptr(m.means),
+                *rec.optimiser_views(g, m.group_begin).c_args(), int(part), self._skip(), _stream()), "qed_adam_step_sh")
             return
         if device_state:
             L.check(lib.qed_adam_step_dev(L.ptr(p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
@@ -583,7 +580,9 @@ class QedAdam(torch.optim.Optimizer):
         # groups in one run (below); any other launch first has the coefficient gradients written out
         owner = ps[-1].__dict__.get("_qed_owner")
         model = owner() if owner is not None else None
-        lazy = model.__dict__.get("_lazy_sh") if model is not None else None
+        lazy = model.__dict__.get("compact_sh") if model is not None else None
+        if lazy is not None and not lazy.implicit:     # (the caller asked for that form: FlatAdam.step(fused_sh=True)'s)
+            lazy = None
         if lazy is not None and len(offs) != len(st.members):
             model._materialise_sh_grads()
             lazy = None
@@ -643,12 +642,11 @@ class QedAdam(torch.optim.Optimizer):
             if lazy is not None:
                 # the fused step's optimiser launches: the SH groups from the colour gradient + the view (before the means
                 # move), then the leading groups.  The two fields are emptied: the compact form is used up
-                n = lazy["n"]
                 L.check(lib.qed_adam_step_sh(
                     flat_ptr, gptr[first], m_ptr, v_ptr, k, C.cast(h_begin, C.c_void_p), C.cast(h_lr, C.c_void_p), None,
-                    float(beta1), float(beta2), float(eps), t, None, -1, 0.0, 0.0, 0, n, lazy["deg"], flat_ptr + 4 * offs[0],
-                    1, L.ptr(lazy["viewmat"]), 16, L.ptr(lazy["v_color"]), 0, 1.0, 3, skip, stream), "qed_adam_step_sh")
-                model.__dict__["_lazy_sh"] = None
+                    float(beta1), float(beta2), float(eps), t, None, -1, 0.0, 0.0, 0, lazy.n, lazy.deg,
+                    flat_ptr + 4 * offs[0], *lazy.optimiser_views().c_args(), 3, skip, stream), "qed_adam_step_sh")
+                model.__dict__["compact_sh"] = None
                 _RAW_GRAD.__set__(ps[-1], None)
                 _RAW_GRAD.__set__(ps[-2], None)
                 lazy = None

@@ -9,6 +9,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from .sh_grad import SHViews, explicit_record
+
 # Rehearsal hook (bench.py QED_BENCH_RCCL_SELF=1, tests): issue the collectives even in a process group of ONE rank, so
 # that a one-GPU box drives the real RCCL calls (AVG all-reduce, all_gather_into_tensor, async works waited on the
 # compute stream) of the N > 1 path.  Off in production: a single rank has nothing to exchange.
@@ -19,46 +21,102 @@ def _single(world_size: int) -> bool:
     return world_size <= 1 and not FORCE_COLLECTIVES
 
 
+class ExchangeState:
+    """What the exchanges keep per model from call to call (``exchange_state(model)``)."""
+
+    __slots__ = ("dense", "sparse", "skip", "early", "early_work")
+
+    def __init__(self):
+        # (send [row], receive [ranks, row]) of the dense and of the sparse message: persistent, so that captured graphs
+        # keep reading the right memory
+        self.dense = self.sparse = None
+        # int32[1], the MAXIMUM of the ranks' overflow words, which the optimiser launches of a data-parallel step take as
+        # ``skip_flag`` (FlatAdam._skip); None: the optimiser takes the device's own overflow word
+        self.skip = None
+        self.early, self.early_work = False, None    # early_gather: the message is packed; its gather in flight, if any
+
+    @staticmethod
+    def fitting(pair, row: int, n_rows: int, device):
+        """``pair`` if it still is (send [row], receive [n_rows, row]) on ``device``, else a new pair (zeroed)."""
+        if pair is None or pair[0].numel() != row or pair[1].shape != (n_rows, row) or pair[0].device != device:
+            pair = (torch.zeros(row, dtype=torch.float32, device=device),               # (the row's padding stays 0)
+                    torch.zeros(n_rows, row, dtype=torch.float32, device=device))
+        return pair
+
+    def skip_word(self, device) -> torch.Tensor:
+        """The persistent skip word.  A rank whose frame overflowed renders it empty and skips its update on the device;
+        unless its peers skip the same step, the replicas' parameters, moments and step counters part for good (per-rank
+        cameras make the list length rank dependent, so an overflow need not hit every rank in the same step)."""
+        if self.skip is None or self.skip.device != device:
+            self.skip = torch.zeros(1, dtype=torch.int32, device=device)
+        return self.skip
+
+
+def exchange_state(model) -> ExchangeState:
+    st = model.__dict__.get("_exchange")
+    if st is None:
+        st = model.__dict__["_exchange"] = ExchangeState()
+    return st
+
+
+def _gather_rows(recv: torch.Tensor, send: torch.Tensor, group, async_op: bool = False):
+    """Every rank's ``send`` row into ``recv`` [ranks, row]; the work handle when ``async_op``."""
+    if dist.get_backend(group) == "nccl":
+        return dist.all_gather_into_tensor(recv.view(-1), send, group=group, async_op=async_op)
+    return dist.all_gather(list(recv.unbind(0)), send, group=group, async_op=async_op)       # gloo (rehearsal / CPU tests)
+
+
+def _average(t: torch.Tensor, world_size: int, group, async_op: bool = False):
+    """All-reduce ``t`` towards its average over the ranks: (work handle when ``async_op``, factor still to apply)."""
+    if dist.get_backend(group) == "nccl":
+        return dist.all_reduce(t, op=dist.ReduceOp.AVG, group=group, async_op=async_op), 1.0    # ncclAvg: no scaling pass
+    return dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group, async_op=async_op), 1.0 / max(world_size, 1)  # gloo: no AVG
+
+
 def allreduce_flat_grad(model, world_size: int, group=None) -> torch.Tensor:
     """Average the model's six parameter gradients across ranks with a single all-reduce.
 
     The gradients already alias one contiguous allocation (``model.flat_grad()``), so nothing is
     packed or copied.  Loss is normalised by the global camera count, i.e. gradients are averaged.
     """
-    _refuse_camera_optimizer(model, "allreduce_flat_grad")
-    g = model.flat_grad()
-    if g is None:
-        raise RuntimeError("no gradients to reduce: call backward() first")
-    _refuse_compact(model, "allreduce_flat_grad")
+    g, _ = _checked_grad(model, "allreduce_flat_grad", compact=False)
     if _single(world_size):
-        model._dp_skip = None
+        exchange_state(model).skip = None
         return g
     collective_skip_flag(model, world_size, group)
-    if dist.get_backend(group) == "nccl":
-        dist.all_reduce(g, op=dist.ReduceOp.AVG, group=group)      # ncclAvg: no extra scaling pass
-    else:                                                            # gloo (CPU tests) has no AVG
-        dist.all_reduce(g, op=dist.ReduceOp.SUM, group=group)
-        g.mul_(1.0 / max(world_size, 1))
+    _, factor = _average(g, world_size, group)
+    if factor != 1.0:
+        g.mul_(factor)
     return g
 
 
 def _refuse_camera_optimizer(model, who: str) -> None:
     """A data-parallel step behind fused_loss(camera_optimizer=...): every rank renders another camera and would step
     another row of pose_adjustment from its own gradient; the rows and their Adam state are not exchanged."""
-    if model.__dict__.get("pose_optimizer") is not None:
+    ctx = model.__dict__.get("_step")                # (model.StepContext: what the last forward call ran with)
+    if ctx is not None and ctx.pose_optimizer is not None:
         raise NotImplementedError(f"{who}: the last fused_loss ran with a camera optimiser; pose optimisation under data "
                                   "parallelism is not supported")
-    if model.__dict__.get("grid_optimizer") is not None:
+    if ctx is not None and ctx.grid_optimizer is not None:
         raise NotImplementedError(f"{who}: the last fused_loss ran with a bilateral-grid optimiser; every rank would step "
                                   "the grids from its own frame, and neither they nor their Adam state are exchanged")
 
 
-def _refuse_compact(model, who: str) -> None:
-    """After fused_loss(compact_sh_grad=True) features_dc.grad holds colour gradients and features_rest.grad is
-    unwritten memory: only exchange_grads_compact / FlatAdam.step(fused_sh=True) may consume them."""
-    if getattr(model, "last_compact", False):
+def _checked_grad(model, who: str, compact: bool):
+    """(flat gradient, compact record | None) for the exchange ``who``.  After fused_loss(compact_sh_grad=True) features_dc.grad
+    holds colour gradients and features_rest.grad is unwritten memory: only exchange_grads_compact* / FlatAdam.step(fused_sh=
+    True) may consume them (``compact``), and they consume nothing else."""
+    _refuse_camera_optimizer(model, who)
+    g = model.flat_grad()
+    if g is None:
+        raise RuntimeError(f"no gradients to {'exchange' if compact else 'reduce'}: call backward() first")
+    rec = explicit_record(model)
+    if compact and rec is None:
+        raise RuntimeError(f"{who} needs gradients from fused_loss(..., compact_sh_grad=True)")
+    if rec is not None and not compact:
         raise RuntimeError(f"{who}: the last backward wrote compact SH gradients (fused_loss(compact_sh_grad=True)); "
                            "use exchange_grads_compact() / FlatAdam.step(fused_sh=True), or render without the flag")
+    return g, rec
 
 
 def exchange_grads_compact(model, world_size: int, group=None, views=None, rebuild: bool = True) -> torch.Tensor:
@@ -74,55 +132,30 @@ def exchange_grads_compact(model, world_size: int, group=None, views=None, rebui
 
     ``views`` (tests): a list of (colour-gradient [N,3], viewmat [1,4,4]) pairs standing in for the gather.
 
-    ``rebuild=False`` skips step 3 and leaves the gathered views in ``model.sh_views`` for
+    ``rebuild=False`` skips step 3 and leaves the gathered views in ``model.compact_sh.views`` for
     ``FlatAdam.step(fused_sh=True)``, which evaluates the coefficient gradients inside the optimiser pass
     (the message buffers are persistent, so a captured Adam graph keeps reading the right memory)."""
-    from . import _lib as L
-    _refuse_camera_optimizer(model, "exchange_grads_compact")
-    g = model.flat_grad()
-    if g is None:
-        raise RuntimeError("no gradients to exchange: call backward() first")
-    if not getattr(model, "last_compact", False):
-        raise RuntimeError("exchange_grads_compact needs gradients from fused_loss(..., compact_sh_grad=True)")
-    names, begin, N = model.group_names, model.group_begin, model.num_points
-    i_dc, i_rest = names.index("features_dc"), names.index("features_rest")
+    g, rec = _checked_grad(model, "exchange_grads_compact", compact=True)
+    state = exchange_state(model)
     n_rows = len(views) if views is not None else max(world_size, 1)
-    geo, send, recv_buf, nv, row = _compact_buffers(model, g, n_rows)
-    v_local = g[begin[i_dc]:begin[i_dc + 1]]
-    bufs = (send, recv_buf)
+    geo, send, recv, nv, row = _compact_buffers(model, g, n_rows)
     if views is not None:
-        n_views = len(views)
-        recv = bufs[1]
         for c, (v, m) in enumerate(views):
             recv[c, :nv] = v.reshape(-1)
             recv[c, nv:nv + 16] = m.reshape(-1)
-        model._dp_skip = None
+        state.skip = None
     elif not _single(world_size):
-        n_views = max(world_size, 1)
-        if dist.get_backend(group) == "nccl":
-            dist.all_reduce(geo, op=dist.ReduceOp.AVG, group=group)
-        else:
-            dist.all_reduce(geo, op=dist.ReduceOp.SUM, group=group)
-            geo.mul_(1.0 / n_views)
-        recv = bufs[1]
-        if dist.get_backend(group) == "nccl":
-            dist.all_gather_into_tensor(recv.view(-1), send, group=group)
-        else:                                                     # gloo (rehearsal / CPU tests)
-            dist.all_gather(list(recv.unbind(0)), send, group=group)
+        _, factor = _average(geo, world_size, group)
+        if factor != 1.0:
+            geo.mul_(factor)
+        _gather_rows(recv, send, group)
         _fold_skip_words(model, recv, nv)
     else:
-        n_views, recv = 1, send.view(1, row)
-        model._dp_skip = None
-    if not rebuild:
-        model.sh_views = (n_views, recv[:, nv:], row, recv, row, 1.0 / n_views)
-        return g
-    rest_w = (begin[i_rest + 1] - begin[i_rest]) // max(N, 1)
-    deg = int(model.last_sh_degree)
-    assert 3 * ((deg + 1) ** 2 - 1) <= rest_w
-    L.check(L.load().qed_sh_grad_from_views(N, n_views, L.ptr(model.means), L.ptr(recv[:, nv:]), row, L.ptr(recv), row,
-                                            deg, 1.0 / n_views, L.ptr(v_local), 3, L.ptr(g[begin[i_rest]:]), rest_w,
-                                            torch.cuda.current_stream().cuda_stream), "qed_sh_grad_from_views")
-    model.last_compact = False                     # the flat gradient is complete again
+        recv = send.view(1, row)
+        state.skip = None
+    rec.views = SHViews.rows(recv, nv)
+    if rebuild:
+        rec.write_out(model, g)                    # the flat gradient is complete again
     return g
 
 
@@ -173,26 +206,21 @@ class early_gather:
         assert total == N, "one camera per rank in the data-parallel exchange"
         dev = vsplat.device
         nv, row = 3 * N, 3 * N + 16 + 4
-        n_rows = max(self.world_size, 1)
-        send, recv = _message_buffers(m, row, n_rows, dev)
+        state = exchange_state(m)
+        send, recv = state.dense = state.fitting(state.dense, row, max(self.world_size, 1), dev)
         L.check(L.load().qed_pack_color_grad(total, L.ptr(vsplat), L.ptr(sh_jac), L.ptr(send),
                                              torch.cuda.current_stream().cuda_stream), "qed_pack_color_grad")
-        send[nv:nv + 16] = m.last_viewmat.reshape(-1).to(torch.float32)
+        send[nv:nv + 16] = m.compact_sh.viewmat.reshape(-1).to(torch.float32)
         send[nv + 16:nv + 17].view(torch.int32).copy_(_local_overflow_word(dev))
-        work = None
-        if not _single(self.world_size):
-            if dist.get_backend(self.group) == "nccl":
-                work = dist.all_gather_into_tensor(recv.view(-1), send, group=self.group, async_op=True)
-            else:
-                work = dist.all_gather(list(recv.unbind(0)), send, group=self.group, async_op=True)
-        m._early_gather = (work, send, recv)
+        state.early = True
+        state.early_work = None if _single(self.world_size) else _gather_rows(recv, send, self.group, async_op=True)
 
     def __enter__(self):
         from . import rasterization as R
         self._key = self.model.means.untyped_storage().data_ptr()       # this model's hook only (rasterization.PRE_PROJECT_BWD)
         self._prev = R.PRE_PROJECT_BWD.get(self._key)
         R.PRE_PROJECT_BWD[self._key] = self._hook
-        self.model._early_gather = None
+        exchange_state(self.model).early = False
         return self
 
     def __exit__(self, *exc):
@@ -227,8 +255,8 @@ def backward_with_early_gather(model, losses, world_size: int, group=None) -> No
     from .rasterization import _ProjectSH
     sh_jac = _ProjectSH.saved(node, "sh_jac")
     eg = early_gather(model, world_size, group)
-    if vsplat is not None and sh_jac is not None and getattr(model, "last_compact", False):
-        model._early_gather = None
+    exchange_state(model).early = False
+    if vsplat is not None and sh_jac is not None and explicit_record(model) is not None:
         eg._hook(vsplat, sh_jac, vsplat.shape[0])
     keep = [(t, gi) for t, gi in zip(inter, g) if gi is not None]
     torch.autograd.backward([t for t, _ in keep], [gi for _, gi in keep])
@@ -243,7 +271,7 @@ def backward_with_early_gather(model, losses, world_size: int, group=None) -> No
 # overflowed -- the word every rank's optimiser takes as skip_flag -- and the caller re-calibrates.  Row layout (floats):
 #   [0:16] view matrix | [16] overflow word (int32 bits) | [17] visible rows (int32 bits) | [18:20] pad |
 #   [20 : 20 + cap] indices (int32 bits) | [20 + cap : 20 + 4 cap] colour gradients
-# The receiver scatters the R lists into the dense [R, 3 N + 20] rows the optimiser pass reads (sh_views), header behind the
+# The receiver scatters the R lists into the dense [R, 3 N + 20] rows the optimiser pass reads (SHViews.rows), header behind the
 # colours as in the dense message, so nothing downstream changes.  Plain torch ops without a host read: the same code runs
 # on CPU tensors in the gloo tests and on the GPU inside a captured graph.
 SPARSE_HEADER = 20
@@ -311,29 +339,19 @@ def unpack_sparse_messages(rows: torch.Tensor, n: int, cap: int, dense: torch.Te
     dense[:, nv:nv + SPARSE_HEADER] = rows[:, :SPARSE_HEADER]
 
 
-def _message_buffers(model, row: int, n_rows: int, device):
-    bufs = getattr(model, "_dp_buffers", None)
-    if bufs is None or bufs[0].numel() != row or bufs[1].shape != (n_rows, row) or bufs[0].device != device:
-        bufs = model._dp_buffers = (torch.zeros(row, dtype=torch.float32, device=device),      # (the row's padding stays 0)
-                                    torch.zeros(n_rows, row, dtype=torch.float32, device=device))
-    return bufs
-
-
 def prepare_compact_message(model, world_size: int) -> None:
     """Assemble this rank's message (colour gradients, view matrix, overflow word) in the persistent send buffer.  What
     ``exchange_grads_compact_begin`` does first; as a call of its own it can be CAPTURED at the end of the forward+backward
     graph (three small launches that then cost graph nodes, not eager dispatches) -- pass ``prepared=True`` to the exchange."""
-    g = model.flat_grad()
-    if g is None or not getattr(model, "last_compact", False):
-        raise RuntimeError("prepare_compact_message needs gradients from fused_loss(..., compact_sh_grad=True)")
+    g, _ = _checked_grad(model, "prepare_compact_message", compact=True)
     _compact_buffers(model, g, max(world_size, 1), fill=True)
 
 
 def fold_skip_words(model) -> None:
-    """The gathered overflow words -> ``model._dp_skip`` (``exchange_grads_compact_begin(..., fold=False)`` leaves this to
-    the caller, who can capture it in front of the optimiser launches that read the flag)."""
-    bufs = model._dp_buffers
-    _fold_skip_words(model, bufs[1], bufs[0].numel() - 20)
+    """The gathered overflow words -> the collective skip word (``exchange_grads_compact_begin(..., fold=False)`` leaves
+    this to the caller, who can capture it in front of the optimiser launches that read the flag)."""
+    send, recv = exchange_state(model).dense
+    _fold_skip_words(model, recv, send.numel() - 20)
 
 
 def exchange_grads_compact_begin(model, world_size: int, group=None, prepared: bool = False,
@@ -355,87 +373,47 @@ def exchange_grads_compact_begin(model, world_size: int, group=None, prepared: b
 
     ``sparse_cap`` (from sparse_message_capacity, the same on every rank): the all-gather carries only the rows of the
     Gaussians this rank's camera saw (index + colour gradient, at most ``sparse_cap`` of them); ``wait_views()`` scatters
-    the gathered lists into the dense rows the optimiser reads.  Same ``model.sh_views``, same update as the dense message
+    the gathered lists into the dense rows the optimiser reads.  Same ``compact_sh.views``, same update as the dense message
     (a Gaussian a rank did not see has a zero colour gradient there either way)."""
-    _refuse_camera_optimizer(model, "exchange_grads_compact_begin")
-    if sparse_cap is not None:
-        return _exchange_sparse_begin(model, world_size, group, int(sparse_cap), visible, fold)
-    g = model.flat_grad()
-    if g is None:
-        raise RuntimeError("no gradients to exchange: call backward() first")
-    if not getattr(model, "last_compact", False):
-        raise RuntimeError("exchange_grads_compact_begin needs gradients from fused_loss(..., compact_sh_grad=True)")
-    early = getattr(model, "_early_gather", None)
-    model._early_gather = None
-    geo, send, recv, nv, row = _compact_buffers(model, g, max(world_size, 1), fill=early is None and not prepared)
+    g, rec = _checked_grad(model, "exchange_grads_compact_begin", compact=True)
+    state, N, n_rows = exchange_state(model), model.num_points, max(world_size, 1)
+    early, w_early = state.early, state.early_work
+    state.early, state.early_work = False, None       # (the early gather belongs to ONE backward pass)
+    sparse = sparse_cap is not None
+    geo, send, recv, nv, row = _compact_buffers(model, g, n_rows, fill=not (early or prepared or sparse))
+    dense, after_gather = recv, (lambda: _fold_skip_words(model, recv, nv)) if fold else None
+    if sparse:
+        # the all-gather carries the sparse rows; what the optimiser / fold_skip_words read stays the dense receive buffer
+        cap = int(sparse_cap)
+        send, recv = state.sparse = state.fitting(state.sparse, sparse_row_floats(cap), n_rows, g.device)
+        pack_sparse_message(g[geo.numel():geo.numel() + nv], _visible_rows(model, visible), rec.viewmat,
+                            _local_overflow_word(g.device), cap, send)
+
+        def after_gather():
+            unpack_sparse_messages(recv, N, cap, dense)
+            if fold:
+                _fold_skip_words(model, dense, nv)
     if _single(world_size):
-        model.sh_views = (1, send[nv:nv + 16].view(1, 16), row, send.view(1, row), row, 1.0)
-        model._dp_skip = None
+        if sparse:
+            recv[0].copy_(send)
+            after_gather()
+            state.skip_word(g.device)
+        else:
+            dense, state.skip = send.view(1, row), None
+        rec.views = SHViews.rows(dense, nv)
         return CompactExchange(None, None, geo, 1.0)
-    nccl = dist.get_backend(group) == "nccl"
-    if early is not None:                                         # the backward pass issued the gather itself (early_gather)
-        w_gather = early[0]
-    elif nccl:
-        w_gather = dist.all_gather_into_tensor(recv.view(-1), send, group=group, async_op=True)
-    else:                                                         # gloo (rehearsal / CPU tests)
-        w_gather = dist.all_gather(list(recv.unbind(0)), send, group=group, async_op=True)
-    if nccl:
-        w_reduce = dist.all_reduce(geo, op=dist.ReduceOp.AVG, group=group, async_op=True)
-    else:
-        w_reduce = dist.all_reduce(geo, op=dist.ReduceOp.SUM, group=group, async_op=True)
-    n_views = max(world_size, 1)
-    model.sh_views = (n_views, recv[:, nv:], row, recv, row, 1.0 / n_views)
-    _dp_skip_word(model, g.device)              # (exists before anything captures an optimiser launch that reads it)
-    return CompactExchange(w_gather, w_reduce, geo, 1.0 if nccl else 1.0 / n_views,
-                           fold=(lambda: _fold_skip_words(model, recv, nv)) if fold else None)
-
-
-def _exchange_sparse_begin(model, world_size: int, group, cap: int, visible, fold: bool) -> CompactExchange:
-    g = model.flat_grad()
-    if g is None:
-        raise RuntimeError("no gradients to exchange: call backward() first")
-    if not getattr(model, "last_compact", False):
-        raise RuntimeError("exchange_grads_compact_begin needs gradients from fused_loss(..., compact_sh_grad=True)")
-    names, begin, N = model.group_names, model.group_begin, model.num_points
-    i_dc = names.index("features_dc")
-    geo, v_local = g[:begin[i_dc]], g[begin[i_dc]:begin[i_dc + 1]]
-    nv, row, srow = 3 * N, 3 * N + SPARSE_HEADER, sparse_row_floats(cap)
-    n_rows = max(world_size, 1)
-    _, dense = _message_buffers(model, row, n_rows, g.device)                 # what sh_views / fold_skip_words read
-    sb = getattr(model, "_dp_sparse_buffers", None)
-    if sb is None or sb[0].numel() != srow or sb[1].shape != (n_rows, srow) or sb[0].device != g.device:
-        sb = model._dp_sparse_buffers = (torch.zeros(srow, dtype=torch.float32, device=g.device),
-                                         torch.zeros(n_rows, srow, dtype=torch.float32, device=g.device))
-    send, recv = sb
-    pack_sparse_message(v_local, _visible_rows(model, visible), model.last_viewmat, _local_overflow_word(g.device), cap, send)
-    n_views = n_rows
-    model.sh_views = (n_views, dense[:, nv:], row, dense, row, 1.0 / n_views)
-    _dp_skip_word(model, g.device)
-    if _single(world_size):
-        recv[0].copy_(send)
-        unpack_sparse_messages(recv, N, cap, dense)
-        if fold:
-            _fold_skip_words(model, dense, nv)
-        return CompactExchange(None, None, geo, 1.0)
-    nccl = dist.get_backend(group) == "nccl"
-    if nccl:
-        w_gather = dist.all_gather_into_tensor(recv.view(-1), send, group=group, async_op=True)
-        w_reduce = dist.all_reduce(geo, op=dist.ReduceOp.AVG, group=group, async_op=True)
-    else:
-        w_gather = dist.all_gather(list(recv.unbind(0)), send, group=group, async_op=True)
-        w_reduce = dist.all_reduce(geo, op=dist.ReduceOp.SUM, group=group, async_op=True)
-
-    def after_gather():
-        unpack_sparse_messages(recv, N, cap, dense)
-        if fold:
-            _fold_skip_words(model, dense, nv)
-    return CompactExchange(w_gather, w_reduce, geo, 1.0 if nccl else 1.0 / n_views, fold=after_gather)
+    # (the backward pass may have issued the gather itself: early_gather)
+    w_gather = w_early if early and not sparse else _gather_rows(recv, send, group, async_op=True)
+    w_reduce, factor = _average(geo, world_size, group, async_op=True)
+    rec.views = SHViews.rows(dense, nv)
+    state.skip_word(g.device)                   # (exists before anything captures an optimiser launch that reads it)
+    return CompactExchange(w_gather, w_reduce, geo, factor, fold=after_gather)
 
 
 def _fold_skip_words(model, recv: torch.Tensor, nv: int) -> None:
-    """model._dp_skip = max over the gathered rows' overflow words (one small launch; the words are counts >= 0)."""
+    """The collective skip word = max over the gathered rows' overflow words (one small launch; the words are counts >= 0)."""
     words = recv[:, nv + 16:nv + 17].view(torch.int32)            # [ranks, 1]
-    torch.amax(words, dim=0, out=_dp_skip_word(model, recv.device))
+    torch.amax(words, dim=0, out=exchange_state(model).skip_word(recv.device))
 
 
 def _compact_buffers(model, g, n_rows: int, fill: bool = True):
@@ -450,14 +428,13 @@ def _compact_buffers(model, g, n_rows: int, fill: bool = True):
     # one message per rank: colour gradients + view matrix + (bits of) this rank's intersection-overflow word (4 floats, so
     # that rows stay 16-byte aligned): the optimiser step is skipped on EVERY rank when ANY rank's frame overflowed
     row = nv + 16 + 4
-    bufs = _message_buffers(model, row, n_rows, g.device)
-    send = bufs[0]
-    if not fill:
-        return geo, send, bufs[1], nv, row
-    send[:nv] = v_local
-    send[nv:nv + 16] = model.last_viewmat.reshape(-1).to(torch.float32)
-    send[nv + 16:nv + 17].view(torch.int32).copy_(_local_overflow_word(g.device))
-    return geo, send, bufs[1], nv, row
+    state = exchange_state(model)
+    send, recv = state.dense = state.fitting(state.dense, row, n_rows, g.device)
+    if fill:
+        send[:nv] = v_local
+        send[nv:nv + 16] = model.compact_sh.viewmat.reshape(-1).to(torch.float32)
+        send[nv + 16:nv + 17].view(torch.int32).copy_(_local_overflow_word(g.device))
+    return geo, send, recv, nv, row
 
 
 def _local_overflow_word(device) -> torch.Tensor:
@@ -472,22 +449,11 @@ def _local_overflow_word(device) -> torch.Tensor:
 _CPU_OVERFLOW_WORD = torch.zeros(1, dtype=torch.int32)
 
 
-def _dp_skip_word(model, device) -> torch.Tensor:
-    """The persistent int32[1] the optimiser launches of a data-parallel step take as ``skip_flag`` (FlatAdam._skip): the
-    MAXIMUM over all ranks of the overflow words.  A rank whose frame overflowed renders it empty and skips its update on
-    the device; unless its peers skip the same step, the replicas' parameters, moments and step counters part for good
-    (per-rank cameras make the list length rank dependent, so an overflow need not hit every rank in the same step)."""
-    w = getattr(model, "_dp_skip", None)
-    if w is None or w.device != device:
-        w = model._dp_skip = torch.zeros(1, dtype=torch.int32, device=device)
-    return w
-
-
 def collective_skip_flag(model, world_size: int, group=None) -> torch.Tensor:
     """For the exchanges that gather no message (allreduce_flat_grad, allreduce_and_step): one MAX all-reduce of the
-    overflow word into ``model._dp_skip``."""
+    overflow word into the collective skip word."""
     g = model.flat_grad()
-    w = _dp_skip_word(model, g.device)
+    w = exchange_state(model).skip_word(g.device)
     w.copy_(_local_overflow_word(g.device))
     if not _single(world_size):
         dist.all_reduce(w, op=dist.ReduceOp.MAX, group=group)
@@ -505,28 +471,22 @@ def allreduce_and_step(model, optimizer, world_size: int, n_chunks: int = 4, gro
     hiding the ~0.13 ms Adam pass of config B is worth it only if four 30 MB all-reduces cost less than
     0.13 ms more than one 118 MB all-reduce.  bench.py keeps the single collective (not measurable on the
     one-GPU development box); ``scripts/dp_rehearsal.py`` checks the equivalence on two ranks."""
-    _refuse_camera_optimizer(model, "allreduce_and_step")
-    g = model.flat_grad()
-    if g is None:
-        raise RuntimeError("no gradients to reduce: call backward() first")
-    _refuse_compact(model, "allreduce_and_step")
+    g, _ = _checked_grad(model, "allreduce_and_step", compact=False)
     total = g.numel()
     if _single(world_size):
-        model._dp_skip = None
+        exchange_state(model).skip = None
         optimizer.begin_step()
         optimizer.step_range(0, total)
         return
     collective_skip_flag(model, world_size, group)
     n_chunks = max(1, min(int(n_chunks), total // 4 or 1))
     bounds = [min(total, (total * k // n_chunks) // 4 * 4) for k in range(n_chunks)] + [total]
-    avg = dist.get_backend(group) == "nccl"
-    works = [dist.all_reduce(g[a:b], op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, group=group, async_op=True)
-             for a, b in zip(bounds[:-1], bounds[1:])]
+    works = [_average(g[a:b], world_size, group, async_op=True) for a, b in zip(bounds[:-1], bounds[1:])]
     optimizer.begin_step()
-    for w, a, b in zip(works, bounds[:-1], bounds[1:]):
+    for (w, factor), a, b in zip(works, bounds[:-1], bounds[1:]):
         w.wait()                                   # the current stream waits for this piece only
-        if not avg:
-            g[a:b].mul_(1.0 / max(world_size, 1))
+        if factor != 1.0:
+            g[a:b].mul_(factor)
         optimizer.step_range(a, b)
 
 

@@ -37,6 +37,7 @@ from . import _lib as L
 from .binning import _workspace, pinned_slot
 from .handover import Handover
 from .rasterization import manual_backward
+from .sh_grad import SHViews, write_sh_grads
 
 
 class _SegmentFn(torch.autograd.Function):
@@ -79,19 +80,18 @@ class _SegmentFn(torch.autograd.Function):
         # the engine adopted them without a copy.  They are moved out first, so that AccumulateGrad adds the new gradients
         # to the old values and not to themselves.  (The flat layout of .grad is given up for that step.)
         from .optim import _RAW_GRAD, _raw_grad
+        owner = getattr(seg, "lazy_owner", None)         # the model, when the captured backward writes compact SH gradients
+        m = owner() if owner is not None else None
         for p, g in zip(seg.params, grads):
             old = _raw_grad(p) if g is not None else None
             if old is not None and old.untyped_storage().data_ptr() == g.untyped_storage().data_ptr():
-                owner_m = getattr(seg, "lazy_owner", None)
-                m_ = owner_m() if owner_m is not None else None
-                if m_ is not None:
-                    m_._materialise_sh_grads()      # (a compact SH gradient waiting there is completed before it is copied)
+                if m is not None:
+                    m._materialise_sh_grads()       # (a compact SH gradient waiting there is completed before it is copied)
                 _RAW_GRAD.__set__(p, old.clone())
         # the accumulator K7 adds into: zeroed by the loss's own backward launch when that was _ImageLosses (StepContext)
         if not seg.handover.take_static_zeroed():
             seg.vsplat.zero_()
         graph.replay()
-        owner = getattr(seg, "lazy_owner", None)
         if owner is not None:
             # the captured projection backward wrote the SH gradients in compact form (config.lazy_sh_grad): they stay so
             # until somebody reads them -- unless gradients of an earlier pass wait in the fields, which autograd is about
@@ -101,10 +101,8 @@ class _SegmentFn(torch.autograd.Function):
             v_dc, v_rest = grads[i_dc], grads[i_dc + 1]
             from .rasterization import _ProjectSH
             viewmats, deg = _ProjectSH.saved(c_proj, "viewmats"), _ProjectSH.saved(c_proj, "sh_degree")
-            m = owner()
             if m is None or not m._lazy_sh_begin(v_dc, v_rest, viewmats, deg):
-                from .model import write_sh_grads
-                write_sh_grads(seg.params[seg.param_names.index("means")], viewmats, deg, v_dc, v_rest)
+                write_sh_grads(seg.params[seg.param_names.index("means")], SHViews.own(viewmats, v_dc), deg, v_dc, v_rest)
         leaf = seg.info["means2d"]
         if leaf.requires_grad:                           # model.py:289-292: xys.grad / xys.absgrad for the densifier
             leaf.grad, leaf.absgrad = seg.leaf_grad, seg.leaf_absgrad

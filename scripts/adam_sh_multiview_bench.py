@@ -5,7 +5,7 @@ of the optimiser (qed_adam_step_sh) rebuilds every Gaussian's 48 coefficient gra
 link budget of DESIGN.md section 5 only prices the bytes on the wire.  Synthetic gathered messages (random colour gradients,
 yawed cameras), one GPU, HIP events, median over `iters` launches.
 
-    python scripts/adam_sh_views_bench.py [iters]
+    python scripts/adam_sh_multiview_bench.py [iters]
 """
 import ctypes as C
 import math
@@ -19,6 +19,7 @@ import torch  # noqa: E402
 from qed_splatter_amd import _lib as L  # noqa: E402
 from qed_splatter_amd.model import FlatAdam, QEDSplatterModel, QEDSplatterModelConfig  # noqa: E402
 from qed_splatter_amd.scene import synthetic_scene  # noqa: E402
+from qed_splatter_amd.sh_grad import CompactSHGrad, SHViews  # noqa: E402
 
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 dev = torch.device("cuda:0")
@@ -39,9 +40,8 @@ for n, sizes in ((500_000, (1, 2, 4, 8)), (2_000_000, (1, 4))):
             a = math.radians(5.0 * r)
             vm = torch.tensor([[math.cos(a), 0, -math.sin(a), 0], [0, -1, 0, 0], [math.sin(a), 0, -math.cos(a), 0], [0, 0, 0, 1.0]])
             recv[r, nv:nv + 16] = vm.reshape(-1).to(dev)
-        model.last_compact = True
-        model.last_sh_degree = 3
-        model.sh_views = (n_views, recv[:, nv:], row, recv, row, 1.0 / n_views)
+        model.compact_sh = CompactSHGrad(recv[:1, nv:], 3)
+        model.compact_sh.views = SHViews.rows(recv, nv)
         for p_, off in zip(model.parameters(), b):
             p_.grad = g[off:off + p_.numel()].view(p_.shape)
         times = []

@@ -498,6 +498,55 @@ def test_flat_adam_refuses_stale_buffers_and_compact_gradients(cuda):
         opt.step()
 
 
+def test_compact_record_survives_an_eval_render_and_a_route_switch_forgets_the_camera_optimiser(cuda):
+    """The compact SH gradient's record belongs to the backward pass and the ``.grad`` fields, not to a forward call: an
+    eval render without grad between backward_fused and FlatAdam.step(fused_sh=True) (a viewer) changes nothing, bit for
+    bit.  And what a fused_loss call ran with is a fact about THAT call: after a step behind a camera optimiser, a plain
+    get_outputs -> get_loss_dict -> backward step is accepted by the data-parallel all-reduce."""
+    from qed_splatter_amd.camera_optimizer import CameraOptimizer, CameraOptimizerConfig
+    from qed_splatter_amd.model import FlatAdam
+    from qed_splatter_amd.parallel import allreduce_flat_grad
+    sc = scene(64, 32, 32, seed=3)
+    m, cam, batch = _model(sc, cuda, graph_segments=False)
+    opt = FlatAdam(m)
+    # ONE backward pass feeds both steps (the compositing backward's atomic sums differ in the last bits from pass to pass):
+    # the second step starts again from the same parameters, moments and step count
+    m.backward_fused(m.fused_loss(cam, batch, compact_sh_grad=True))
+    rec = m.compact_sh
+    assert rec is not None and not rec.implicit
+    start, runs = m.flat_params.detach().clone(), []
+    for render_between in (False, True):
+        with torch.no_grad():
+            m.flat_params.copy_(start)
+        opt.exp_avg.zero_()
+        opt.exp_avg_sq.zero_()
+        opt.t = 0
+        if render_between:
+            m.eval()
+            with torch.no_grad():
+                m.get_outputs(cam)
+            m.train()
+            assert m.compact_sh is rec
+        opt.step(fused_sh=True)
+        torch.cuda.synchronize()
+        assert not torch.equal(m.flat_params, start)
+        runs.append((m.flat_params.detach().clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone()))
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+    # the route switch
+    pose = CameraOptimizer(CameraOptimizerConfig(mode="SO3xR3"), 1, cuda)
+    m.zero_grad()
+    m.backward_fused(m.fused_loss(cam, batch, camera_optimizer=pose, cam_idx=0))
+    with pytest.raises(NotImplementedError, match="camera optimiser"):
+        allreduce_flat_grad(m, 1)
+    m.zero_grad()
+    out = m.get_outputs(cam)
+    sum(m.get_loss_dict(out, batch).values()).backward()
+    assert m.compact_sh is None
+    g = allreduce_flat_grad(m, 1)
+    assert g.data_ptr() == m.gauss_params["means"].grad.data_ptr() and bool(torch.isfinite(g).all())
+
+
 @pytest.mark.parametrize("uint8_image", [False, True])
 def test_ssim_forward_shared_between_metrics_and_loss(cuda, uint8_image):
     """get_metrics_dict computes rgb_ssim of (rgb, gt) and get_loss_dict needs the SSIM of the same two images: in training
@@ -815,7 +864,7 @@ def test_flat_adam_state_dict_round_trip(cuda, tmp_path):
                 p = m.gauss_params[name]
                 p.grad = g[off:off + p.numel()].view(p.shape)
                 off += p.numel()
-            m.last_compact = False
+            m.compact_sh = None
             o.step(device_state=device_state)
         assert torch.equal(m1.flat_params, m2.flat_params) and torch.equal(o1.exp_avg_sq, o2.exp_avg_sq)
     with pytest.raises(ValueError, match="load the model"):
@@ -1273,9 +1322,9 @@ def test_lazy_sh_gradients_read_as_the_full_gradients(cuda):
     # (1) a read between backward and step
     m1, cam, batch, opts1 = prepared(True)
     one_backward(m1, cam, batch)
-    assert m1.__dict__["_lazy_sh"] is not None                   # compact: nobody has asked yet
+    assert m1.__dict__["compact_sh"] is not None                   # compact: nobody has asked yet
     got_rest = m1.gauss_params["features_rest"].grad             # ... now somebody has
-    assert m1.__dict__["_lazy_sh"] is None
+    assert m1.__dict__["compact_sh"] is None
     assert_close(got_rest, want["features_rest"].double(), 1e-5, "features_rest.grad (materialised)")
     assert_close(m1.gauss_params["features_dc"].grad, want["features_dc"].double(), 1e-5, "features_dc.grad (materialised)")
     assert_close(m1.means.grad, want["means"].double(), 1e-5, "means.grad")
@@ -1292,9 +1341,9 @@ def test_lazy_sh_gradients_read_as_the_full_gradients(cuda):
     one_backward(m0, cam, batch)
     one_backward(m0, cam, batch)
     one_backward(m1, cam, batch)
-    assert m1.__dict__["_lazy_sh"] is not None
+    assert m1.__dict__["compact_sh"] is not None
     one_backward(m1, cam, batch)                                 # completes the first pass's gradients, then adds its own
-    assert m1.__dict__["_lazy_sh"] is None
+    assert m1.__dict__["compact_sh"] is None
     for k in ("features_dc", "features_rest", "means"):
         assert_close(m1.gauss_params[k].grad, m0.gauss_params[k].grad.double(), 2e-5, f"{k}.grad summed over two passes")
 
@@ -1302,13 +1351,13 @@ def test_lazy_sh_gradients_read_as_the_full_gradients(cuda):
     for o in opts1.values():
         o.zero_grad(set_to_none=True)
     one_backward(m1, cam, batch)
-    assert m1.__dict__["_lazy_sh"] is not None
+    assert m1.__dict__["compact_sh"] is not None
     for o in opts1.values():
         o.zero_grad(set_to_none=True)
-    assert m1.__dict__["_lazy_sh"] is None and _raw_grad(m1.gauss_params["features_dc"]) is None
+    assert m1.__dict__["compact_sh"] is None and _raw_grad(m1.gauss_params["features_dc"]) is None
     one_backward(m1, cam, batch)
     m1.zero_grad()
-    assert m1.__dict__["_lazy_sh"] is None and all(p.grad is None for p in m1.parameters())
+    assert m1.__dict__["compact_sh"] is None and all(p.grad is None for p in m1.parameters())
 
     # (4) a group stepped out of turn: the waiting groups are launched alone -> plain gradients first
     for o in (*opts0.values(), *opts1.values()):
@@ -1334,7 +1383,7 @@ def test_lazy_sh_gradients_read_as_the_full_gradients(cuda):
     opts2["features_rest"] = torch.optim.Adam([m2.gauss_params["features_rest"]], lr=1e-3, eps=1e-15)
     for _ in range(3):
         _reference_sequence(m2, cam, batch, opts2)
-        assert m2.__dict__.get("_lazy_sh") is None and _raw_grad(m2.gauss_params["features_rest"]) is not None
+        assert m2.__dict__.get("compact_sh") is None and _raw_grad(m2.gauss_params["features_rest"]) is not None
 
 
 def test_camera_index_keeps_a_launch_order_per_camera_and_changes_no_result(cuda):

@@ -26,7 +26,9 @@ def _worker(rank, world, port, q):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         from qed_splatter_amd.model import QEDSplatterModel
+        from qed_splatter_amd import parallel as P
         from qed_splatter_amd.parallel import allreduce_densification_stats, allreduce_flat_grad
+        from qed_splatter_amd.sh_grad import CompactSHGrad
         sc = scene(50, 32, 32, seed=5)
         m = QEDSplatterModel(None, **{k: sc[k] for k in PARAM_NAMES})
         # rank-dependent gradients laid out as _ProjectSH.backward lays them out (one allocation)
@@ -38,7 +40,7 @@ def _worker(rank, world, port, q):
             p.grad = flat[off:off + p.numel()].view(p.shape)
             off += p.numel()
         g = allreduce_flat_grad(m, world)
-        ok0 = int(m._dp_skip) == 0                                    # no rank overflowed: nobody skips
+        ok0 = int(P.exchange_state(m).skip) == 0                                    # no rank overflowed: nobody skips
         want = torch.arange(total, dtype=torch.float32) * (sum(range(1, world + 1)) / world)
         ok = ok0 and torch.allclose(g, want) and g.data_ptr() == m.means.grad.data_ptr()
         # identical update on every rank keeps the replicas bit-identical
@@ -65,13 +67,12 @@ def _worker(rank, world, port, q):
         ok = ok and abs(float(dz.xys_grad_norm[0]) - 0.5 * sum(range(1, world + 1))) < 1e-6
         # compact exchange, both collectives left in flight (what bench.py runs for N > 1) == the blocking form:
         # averaged geometry gradients, one (colour gradients + view matrix) message per rank, scale 1 / world
-        from qed_splatter_amd import parallel as P
         from qed_splatter_amd.parallel import exchange_grads_compact, exchange_grads_compact_begin
         # ... and the optimiser's skip decision is collective: ONE rank's frame overflowed its intersection buffer (its
         # overflow word holds the count it needed) -> every rank's step takes the same non-zero skip word
         P._CPU_OVERFLOW_WORD[0] = 77 if rank == world - 1 else 0
         allreduce_flat_grad(m, world)
-        ok = ok and int(m._dp_skip) == 77
+        ok = ok and int(P.exchange_state(m).skip) == 77
         results = []
         for overlapped in (False, True, "prepared"):
             m2 = QEDSplatterModel(None, **{k: sc[k] for k in PARAM_NAMES})
@@ -81,13 +82,12 @@ def _worker(rank, world, port, q):
                 p = m2.gauss_params[name]
                 p.grad = flat2[off:off + p.numel()].view(p.shape)
                 off += p.numel()
-            m2.last_compact = True
-            m2.last_viewmat = torch.eye(4).reshape(1, 4, 4) * (rank + 2)
+            m2.compact_sh = CompactSHGrad(torch.eye(4).reshape(1, 4, 4) * (rank + 2), 0)
             if overlapped == "prepared":                             # message assembled and skip words folded by the caller
                 P.prepare_compact_message(m2, world)                 # (what bench.py captures inside its graphs)
                 ex = exchange_grads_compact_begin(m2, world, prepared=True, fold=False)
                 ex.wait_views()
-                ok = ok and int(m2._dp_skip) == 0                    # not folded yet
+                ok = ok and int(P.exchange_state(m2).skip) == 0                    # not folded yet
                 P.fold_skip_words(m2)
                 ex.wait_geometry()
             elif overlapped:
@@ -97,8 +97,8 @@ def _worker(rank, world, port, q):
                 ex.wait_geometry()                                   # idempotent
             else:
                 exchange_grads_compact(m2, world, rebuild=False)
-            ok = ok and int(m2._dp_skip) == 77
-            n_views, vms, vm_stride, v_views, view_stride, scale = m2.sh_views
+            ok = ok and int(P.exchange_state(m2).skip) == 77
+            n_views, vms, vm_stride, v_views, view_stride, scale = m2.compact_sh.views
             results.append((m2.flat_grad().clone(), v_views.clone(), n_views, vm_stride, view_stride, scale))
         b = m.group_begin
         nv = b[5] - b[4]
@@ -129,8 +129,7 @@ def _worker(rank, world, port, q):
                 p = m3.gauss_params[name]
                 p.grad = flat3[off:off + p.numel()].view(p.shape)
                 off += p.numel()
-            m3.last_compact = True
-            m3.last_viewmat = torch.eye(4).reshape(1, 4, 4) * (rank + 2)
+            m3.compact_sh = CompactSHGrad(torch.eye(4).reshape(1, 4, 4) * (rank + 2), 0)
             if form == "dense":
                 ex = exchange_grads_compact_begin(m3, world)
             else:
@@ -141,7 +140,7 @@ def _worker(rank, world, port, q):
                 ex = exchange_grads_compact_begin(m3, world, sparse_cap=cap, visible=visible)
             ex.wait_views()
             ex.wait_geometry()
-            views[form] = (m3.sh_views[3].clone(), m3.flat_grad().clone(), int(m3._dp_skip))
+            views[form] = (m3.compact_sh.views[3].clone(), m3.flat_grad().clone(), int(P.exchange_state(m3).skip))
         d, sp, so = views["dense"], views["sparse"], views["sparse-overflow"]
         ok = ok and torch.equal(d[0][:, :nv + 17], sp[0][:, :nv + 17]) and torch.equal(d[1][:b[4]], sp[1][:b[4]])
         ok = ok and d[2] == 0 and sp[2] == 0

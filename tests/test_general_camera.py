@@ -373,7 +373,7 @@ def test_adam_with_sh_gradients_from_several_views_equals_rebuild_then_step(cuda
         m, _, batch = _model(sc, cuda)
         cam = _camera(sc, c, w, h, cuda)
         m.backward_fused(m.fused_loss(cam, batch, compact_sh_grad=True))
-        views.append((m.gauss_params["features_dc"].grad.clone(), m.last_viewmat.clone()))
+        views.append((m.gauss_params["features_dc"].grad.clone(), m.compact_sh.viewmat.clone()))
     runs = []
     for rebuild in (True, False):
         m, _, batch = _model(sc, cuda)
@@ -406,7 +406,7 @@ def test_compact_sh_gradient_exchange_equals_averaged_full_gradients(cuda):
             cam = _camera(sc, c, w, h, cuda)
             m.backward_fused(m.fused_loss(cam, batch, compact_sh_grad=compact))
             if compact:
-                views.append((m.gauss_params["features_dc"].grad.clone(), m.last_viewmat.clone()))
+                views.append((m.gauss_params["features_dc"].grad.clone(), m.compact_sh.viewmat.clone()))
                 last = m
             else:
                 full.append(m.flat_grad().clone())

@@ -1068,7 +1068,7 @@ def test_compact_sh_gradient_exchange_equals_averaged_full_gradients(cuda):
             cam = PinholeCameras(sc["camera_to_worlds"][c:c + 1].to(cuda), K[0, 0], K[1, 1], K[0, 2], K[1, 2], w, h)
             m.backward_fused(m.fused_loss(cam, batch, compact_sh_grad=compact))
             if compact:
-                views.append((m.gauss_params["features_dc"].grad.clone(), m.last_viewmat.clone()))
+                views.append((m.gauss_params["features_dc"].grad.clone(), m.compact_sh.viewmat.clone()))
                 last = m
             else:
                 full.append(m.flat_grad().clone())
@@ -1088,7 +1088,7 @@ def test_colour_gradient_message_packed_ahead_of_the_projection_backward(cuda, d
     multi-GPU job puts the all-gather on the links.  The message must be exactly what the projection backward writes as
     compact colour gradient in the same pass, and all gradients must equal backward_fused's; the hook form (early_gather)
     gives the same message."""
-    from qed_splatter_amd.parallel import backward_with_early_gather, early_gather, exchange_grads_compact_begin
+    from qed_splatter_amd.parallel import backward_with_early_gather, early_gather, exchange_grads_compact_begin, exchange_state
     w, h, n = 200, 136, 6000
     sc = scene(n, w, h, seed=14)
     sc["features_dc"] = sc["features_dc"] - 1.2              # a good share of colours below the clamp: the mask matters
@@ -1110,14 +1110,14 @@ def test_colour_gradient_message_packed_ahead_of_the_projection_backward(cuda, d
             ref = g
             assert float((g[b[4]:b[5]] == 0).float().mean()) > 0.05          # clamped colours are really there
             continue
-        send = m._dp_buffers[0]
+        send = exchange_state(m).dense[0]
         assert torch.equal(send[:3 * n], g[b[4]:b[5]])                        # the message == the compact colour gradient
-        assert torch.equal(send[3 * n:3 * n + 16], m.last_viewmat.reshape(-1))
+        assert torch.equal(send[3 * n:3 * n + 16], m.compact_sh.viewmat.reshape(-1))
         assert_close(g[:b[5]], ref[:b[5]].double().cpu(), 2e-5, f"gradients ({how})")
         ex = exchange_grads_compact_begin(m, 1)                               # finds the message in place: no second packing
         ex.wait_views()
         ex.wait_geometry()
-        assert m.sh_views[0] == 1 and m.sh_views[3].data_ptr() == send.data_ptr()
+        assert m.compact_sh.views[0] == 1 and m.compact_sh.views[3].data_ptr() == send.data_ptr()
 
 
 @pytest.mark.parametrize("n,model_step,device_state", [(1237, 30000, False), (1000, 30000, True), (1001, 1, True),
@@ -1202,7 +1202,7 @@ def test_adam_with_sh_gradients_from_several_views_equals_rebuild_then_step(cuda
         m, _, batch = _model(sc, cuda)
         cam = PinholeCameras(sc["camera_to_worlds"][c:c + 1].to(cuda), K[0, 0], K[1, 1], K[0, 2], K[1, 2], w, h)
         m.backward_fused(m.fused_loss(cam, batch, compact_sh_grad=True))
-        views.append((m.gauss_params["features_dc"].grad.clone(), m.last_viewmat.clone()))
+        views.append((m.gauss_params["features_dc"].grad.clone(), m.compact_sh.viewmat.clone()))
     runs = []
     for rebuild in (True, False):
         m, _, batch = _model(sc, cuda)

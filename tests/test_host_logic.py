@@ -156,6 +156,7 @@ def test_lazy_sh_gradient_parameters_complete_the_gradients_for_every_python_rea
     import copy
     import torch
     from qed_splatter_amd.model import QEDSplatterModel, _LazySHGradParameter, _raw_grad
+    from qed_splatter_amd.sh_grad import CompactSHGrad
     from tests.util import PARAM_NAMES, scene
     sc = scene(40, 32, 32, seed=3)
     m = QEDSplatterModel(None, **{k: sc[k] for k in PARAM_NAMES})
@@ -167,13 +168,13 @@ def test_lazy_sh_gradient_parameters_complete_the_gradients_for_every_python_rea
 
     def fake_materialise():
         calls.append(1)
-        m.__dict__["_lazy_sh"] = None
+        m.__dict__["compact_sh"] = None
     monkeypatch.setattr(m, "_materialise_sh_grads", fake_materialise)
 
     def pend():
         _raw_grad_set(dc, torch.zeros_like(dc))
         _raw_grad_set(rest, torch.zeros_like(rest))
-        m.__dict__["_lazy_sh"] = {"stand-in": True}
+        m.__dict__["compact_sh"] = CompactSHGrad(None, 0, implicit=True)
 
     from qed_splatter_amd.model import _RAW_GRAD
     _raw_grad_set = _RAW_GRAD.__set__
@@ -188,9 +189,9 @@ def test_lazy_sh_gradient_parameters_complete_the_gradients_for_every_python_rea
     assert _raw_grad(dc) is not None and len(calls) == 1
     # .grad = None on both drops the compact form without completing it
     dc.grad = None
-    assert m.__dict__["_lazy_sh"] is not None and len(calls) == 1
+    assert m.__dict__["compact_sh"] is not None and len(calls) == 1
     rest.grad = None
-    assert m.__dict__["_lazy_sh"] is None and len(calls) == 1
+    assert m.__dict__["compact_sh"] is None and len(calls) == 1
     # assigning a tensor to one field completes the other first
     pend()
     dc.grad = torch.ones_like(dc)
@@ -203,9 +204,9 @@ def test_lazy_sh_gradient_parameters_complete_the_gradients_for_every_python_rea
     c = copy.deepcopy(dc)
     assert isinstance(c, torch.nn.Parameter) and c.grad is None
     # after densification (rebind_flat) the new Parameters are lazy ones again and nothing is pending
-    m.__dict__["_lazy_sh"] = {"stand-in": True}
+    m.__dict__["compact_sh"] = CompactSHGrad(None, 0, implicit=True)
     m.rebind_flat(m.flat_params.detach().clone(), m.num_points)
-    assert m.__dict__["_lazy_sh"] is None and type(m.gauss_params["features_rest"]) is _LazySHGradParameter
+    assert m.__dict__["compact_sh"] is None and type(m.gauss_params["features_rest"]) is _LazySHGradParameter
 
 
 def test_committed_counters_are_quoted_only_for_the_sources_they_were_taken_on(tmp_path):
