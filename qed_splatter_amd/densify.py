@@ -112,9 +112,9 @@ class Densifier:
         if step < cfg.stop_split_at and step % reset_interval == cfg.refine_every:
             n = m.num_points
             reset_value = cfg.cull_alpha_thresh * 2.0
-            b = m.group_begin[m.group_names.index("opacities")]
-            L.check(lib.qed_densify_reset_opacity(n, L.ptr(m.flat_params[b:b + n]), L.ptr(opt.exp_avg[b:b + n]),
-                                                  L.ptr(opt.exp_avg_sq[b:b + n]),
+            lo, hi = m.layout.span("opacities")
+            L.check(lib.qed_densify_reset_opacity(n, L.ptr(m.flat_params[lo:hi]), L.ptr(opt.exp_avg[lo:hi]),
+                                                  L.ptr(opt.exp_avg_sq[lo:hi]),
                                                   math.log(reset_value / (1.0 - reset_value)), _stream()),
                     "qed_densify_reset_opacity")
             info["opacity_reset"] = True
@@ -148,20 +148,13 @@ class Densifier:
                 samples = torch.randn(ns * n_split, 3, device=dev, generator=self._gen)   # split_gaussians' randn
             assert samples.shape == (ns * n_split, 3)
             samples = samples.to(device=dev, dtype=torch.float32).contiguous()
-        widths = [(m.group_begin[g + 1] - m.group_begin[g]) // n for g in range(6)]
-        new_begin = [0]
-        for w in widths:
-            new_begin.append(new_begin[-1] + w * n_new)
-        new_p = torch.empty(new_begin[-1], dtype=torch.float32, device=dev)
-        new_m = torch.empty_like(new_p)
-        new_v = torch.empty_like(new_p)
+        new = m.layout.resized(n_new)
+        new_p, new_m, new_v = new.empty_like_state(dev)
         h_tot = (C.c_int32 * 4)(n_split, k_old, k_child, k_dup)
-        h_old = (C.c_int64 * 7)(*m.group_begin)
-        h_new = (C.c_int64 * 7)(*new_begin)
         L.check(lib.qed_densify_emit(n, ns, L.ptr(flags), L.ptr(pos), C.cast(h_tot, C.c_void_p), L.ptr(samples),
                                      L.ptr(m.flat_params), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq),
-                                     C.cast(h_old, C.c_void_p), L.ptr(new_p), L.ptr(new_m), L.ptr(new_v),
-                                     C.cast(h_new, C.c_void_p), _stream()), "qed_densify_emit")
+                                     m.layout.c_begin_ptr, L.ptr(new_p), L.ptr(new_m), L.ptr(new_v),
+                                     new.c_begin_ptr, _stream()), "qed_densify_emit")
         m.rebind_flat(new_p, n_new)
         opt.rebind(new_m, new_v)
         n_dup = int((flags & 2).ne(0).sum()) if densify else 0

@@ -10,7 +10,6 @@ never reads anything back: once N sits at the cap, a captured step (graph.Graphe
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -97,9 +96,8 @@ class McmcStrategy:
             return self._n_dead[0]
         src = self._rows(sources, n, "relocate") if sources is not None else None
         ws = self._workspace(n, n)
-        h_begin = (C.c_int64 * 7)(*m.group_begin)
         L.check(L.load().qed_mcmc_relocate(n, L.ptr(m.flat_params), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq),
-                                           C.cast(h_begin, C.c_void_p), float(self.config.min_opacity), L.ptr(src),
+                                           m.layout.c_begin_ptr, float(self.config.min_opacity), L.ptr(src),
                                            self.seed, self.n_refinements, L.ptr(self._n_dead), L.ptr(ws), ws.numel(),
                                            _stream()), "qed_mcmc_relocate")
         self.n_refinements += 1
@@ -119,21 +117,13 @@ class McmcStrategy:
         src = self._rows(sources, n_add, "add") if sources is not None else None
         if src is not None and (int(src.min()) < 0 or int(src.max()) >= n):
             raise ValueError(f"McmcStrategy.add: sources must lie in [0, {n})")
-        widths = [(m.group_begin[g + 1] - m.group_begin[g]) // n for g in range(6)]
-        new_begin = [0]
-        for w in widths:
-            new_begin.append(new_begin[-1] + w * (n + n_add))
-        dev = m.device
-        new_p = torch.empty(new_begin[-1], dtype=torch.float32, device=dev)
-        new_m = torch.empty_like(new_p)
-        new_v = torch.empty_like(new_p)
+        new = m.layout.resized(n + n_add)
+        new_p, new_m, new_v = new.empty_like_state(m.device)
         ws = self._workspace(n, n_add)
-        h_old = (C.c_int64 * 7)(*m.group_begin)
-        h_new = (C.c_int64 * 7)(*new_begin)
         L.check(L.load().qed_mcmc_add(n, n_add, L.ptr(m.flat_params), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq),
-                                      C.cast(h_old, C.c_void_p), float(self.config.min_opacity), L.ptr(src), self.seed,
+                                      m.layout.c_begin_ptr, float(self.config.min_opacity), L.ptr(src), self.seed,
                                       self.n_refinements, L.ptr(new_p), L.ptr(new_m), L.ptr(new_v),
-                                      C.cast(h_new, C.c_void_p), L.ptr(ws), ws.numel(), _stream()), "qed_mcmc_add")
+                                      new.c_begin_ptr, L.ptr(ws), ws.numel(), _stream()), "qed_mcmc_add")
         self.n_refinements += 1
         m.rebind_flat(new_p, n + n_add)
         opt.rebind(new_m, new_v)

@@ -45,6 +45,7 @@ from .optim import FlatAdam, QedAdam, QedAdamSet, exponential_decay_lr  # noqa: 
 from .optim import _RAW_GRAD, _all_groups_stepped_by_qed_adam, _raw_grad
 from .optim import _FLAT_STATES  # noqa: F401  (the registry object itself: tests stand in for QedAdam through it)
 from .binning import _workspace
+from .layout import GROUP_ORDER, FlatLayout  # noqa: F401  (GROUP_ORDER is also importable from here)
 from .rasterization import rasterization
 from .sh_grad import CompactSHGrad
 
@@ -178,9 +179,6 @@ class PinholeCameras:
         self.width = (self.width * s).to(torch.int64)
         self.height = (self.height * s).to(torch.int64)
         self._intr = None
-
-
-GROUP_ORDER = ("means", "scales", "quats", "opacities", "features_dc", "features_rest")
 
 
 def _refuse_overwritten(rgb: Tensor, who: str) -> None:
@@ -330,7 +328,7 @@ class QEDSplatterModel(nn.Module):
             # Six independent tensors, as Nerfstudio's parent class holds them (model.py:12,50-58; one optimiser per
             # group, config.py:44-68).  get_outputs / get_loss_dict / fused_loss run unchanged; what needs the flat
             # layout (FlatAdam, Densifier, the data-parallel exchange) refuses.
-            self._flat = None
+            self._flat = self.layout = None
             self.group_begin = []
             self.gauss_params = nn.ParameterDict(
                 {n: nn.Parameter(srcs[n].detach().to(torch.float32).clone().contiguous()) for n in self.group_names})
@@ -339,32 +337,17 @@ class QEDSplatterModel(nn.Module):
         # leaf views into it.  _ProjectSH.backward lays the six gradients out in the same order in
         # one allocation, so the data-parallel all-reduce and the fused Adam step each
         # touch a single contiguous range and nothing is ever concatenated.
-        total = sum(srcs[n].numel() for n in self.group_names)
-        adopt = flat is not None
-        if adopt:
-            begins = [sum(srcs[n].numel() for n in self.group_names[:g]) for g in range(len(self.group_names))]
-            # (a group without elements -- features_rest with sh_degree 0 -- has no address to compare: torch gives
-            # every empty tensor the data_ptr 0)
-            if not (flat.dtype == torch.float32 and flat.is_contiguous() and flat.numel() == total and all(
-                    srcs[n].dtype == torch.float32 and srcs[n].is_contiguous() and srcs[n].device == flat.device
-                    and (srcs[n].numel() == 0 or srcs[n].data_ptr() == flat.data_ptr() + 4 * b)
-                    for n, b in zip(self.group_names, begins))):
-                raise ValueError("flat= needs the six tensors to be float32 views of it in GROUP_ORDER")
-        else:
-            flat = torch.empty(total, dtype=torch.float32, device=means.device)
-        self.group_begin: List[int] = [0]
-        params = {}
-        off = 0
-        for name in self.group_names:
-            src = srcs[name]
-            n = src.numel()
-            if not adopt:
-                flat[off:off + n] = src.reshape(-1).to(torch.float32)
-            params[name] = self._make_param(name, flat[off:off + n].view(src.shape))
-            off += n
-            self.group_begin.append(off)
+        self.layout = FlatLayout.of(srcs)
+        self.group_begin: List[int] = self.layout.begin
+        if flat is None:
+            flat = self.layout.empty(means.device)
+            for name, view in self.layout.views(flat).items():
+                view.copy_(srcs[name].detach().reshape(view.shape))
+        elif not self.layout.aliases(flat, [srcs[name] for name in GROUP_ORDER]):
+            raise ValueError("flat= needs the six tensors to be float32 views of it in GROUP_ORDER")
         self._flat = flat
-        self.gauss_params = nn.ParameterDict(params)          # same container name as SplatfactoModel
+        self.gauss_params = nn.ParameterDict(                 # same container name as SplatfactoModel
+            {name: self._make_param(name, view) for name, view in self.layout.views(flat).items()})
 
     @classmethod
     def from_seed_points(cls, config: Optional[QEDSplatterModelConfig], points, colors=None, *, random_init: bool = False,
@@ -488,22 +471,11 @@ class QEDSplatterModel(nn.Module):
     def rebind_flat(self, flat: Tensor, n_points: int) -> None:
         """Adopt a new flat parameter buffer (densification changes N): the six Parameters are
         re-created as leaf views into it, in group order, with their per-Gaussian shapes kept."""
-        old_n = max(self.num_points, 1)
-        shapes = {n: (n_points,) + tuple(self.gauss_params[n].shape[1:]) for n in self.group_names}
-        widths = {n: self.gauss_params[n].numel() // old_n for n in self.group_names}
-        if self.num_points == 0:
-            widths = {n: int(torch.tensor(shapes[n][1:]).prod()) if len(shapes[n]) > 1 else 1 for n in self.group_names}
-        assert flat.numel() == n_points * sum(widths.values()) and flat.dtype == torch.float32 and flat.is_contiguous()
-        params, begin, off = {}, [0], 0
-        for name in self.group_names:
-            n = n_points * widths[name]
-            params[name] = self._make_param(name, flat[off:off + n].view(shapes[name]))
-            off += n
-            begin.append(off)
-        self._flat = flat
-        self.group_begin = begin
+        layout = self.layout.resized(n_points)
+        assert flat.numel() == layout.total and flat.dtype == torch.float32 and flat.is_contiguous()
+        self._flat, self.layout, self.group_begin = flat, layout, layout.begin
         self.__dict__["compact_sh"] = None
-        self.gauss_params = nn.ParameterDict(params)
+        self.gauss_params = nn.ParameterDict({name: self._make_param(name, view) for name, view in layout.views(flat).items()})
 
     # ---- parameter groups (same names as the reference reads at model.py:227-239) ----
     means = property(lambda self: self.gauss_params["means"])
@@ -533,19 +505,13 @@ class QEDSplatterModel(nn.Module):
             return None
         if self._flat is None:
             self.flat_params                     # (raises: no flat layout)
-        g0 = grads[0]
-        base, ok = g0.storage_offset(), True
-        for g, beg in zip(grads, self.group_begin):
-            ok = ok and g.is_contiguous() and g.untyped_storage().data_ptr() == g0.untyped_storage().data_ptr() \
-                and g.storage_offset() == base + beg
-        total = self.group_begin[-1]
-        if ok and g0.untyped_storage().nbytes() >= 4 * (base + total):
+        g0, total = grads[0], self.layout.total
+        base = g0.storage_offset()
+        if self.layout.aliases(g0.data_ptr(), grads) and g0.untyped_storage().nbytes() >= 4 * (base + total):
             return torch.empty(0, dtype=torch.float32, device=g0.device).set_(g0.untyped_storage(), base, (total,))
         flat = torch.cat([g.reshape(-1) for g in grads])
-        off = 0
-        for n, g in zip(self.group_names, grads):           # re-alias so later steps stay zero-copy
-            self.gauss_params[n].grad = flat[off:off + g.numel()].view(g.shape)
-            off += g.numel()
+        for (n, view), g in zip(self.layout.views(flat).items(), grads):      # re-alias so later steps stay zero-copy
+            self.gauss_params[n].grad = view.view(g.shape)
         return flat
 
     @property
@@ -566,8 +532,7 @@ class QEDSplatterModel(nn.Module):
         if self._flat is None:
             return self
         ps = [self.gauss_params[n] for n in self.group_names]
-        if any(p.data_ptr() != self._flat.data_ptr() + 4 * b or p.device != self._flat.device
-               for p, b in zip(ps, self.group_begin)):
+        if not self.layout.aliases(self._flat, ps):
             flat = torch.cat([p.detach().reshape(-1).to(torch.float32) for p in ps])
             self.rebind_flat(flat, ps[0].shape[0])
         return self

@@ -63,8 +63,6 @@ class FlatAdam:
         lrs = {**self.DEFAULT_LRS, **(lrs or {})}
         self._means_lr_init = float(lrs["means"])
         self.lr = [float(lrs[n]) for n in model.group_names]
-        begins = list(model.group_begin)
-        self._begin = (C.c_int64 * len(begins))(*begins)
         self._lr = (C.c_float * len(self.lr))(*self.lr)
         self.betas, self.eps = betas, eps
         self.exp_avg = torch.zeros_like(model.flat_params)
@@ -163,14 +161,12 @@ class FlatAdam:
         """Adopt new moment buffers after the model adopted a new flat parameter buffer (densification);
         the step count carries on, as torch.optim.Adam's per-parameter ``step`` does in the reference."""
         assert exp_avg.numel() == self.model.flat_params.numel() == exp_avg_sq.numel()
-        begins = list(self.model.group_begin)
-        self._begin = (C.c_int64 * len(begins))(*begins)
         self.exp_avg, self.exp_avg_sq = exp_avg, exp_avg_sq
         self._flat_ref = self.model.flat_params
 
     def _check(self, who: str, compact_ok: bool = False) -> None:
-        """Refuse to train on garbage: a flat buffer the Parameters no longer alias (model.to() / densification
-        without rebind()), or compact SH gradients consumed by a plain step."""
+        """Refuse to train on garbage: moments of a flat buffer the model has left (model.to() / densification without
+        rebind(); the group begins are ``model.layout``'s at every launch), or compact SH gradients consumed by a plain step."""
         m = self.model
         if m.flat_params is not self._flat_ref or m.flat_params.device != self.exp_avg.device:
             raise RuntimeError(f"FlatAdam.{who}: the model adopted a new flat parameter buffer (model.to() or "
@@ -198,11 +194,10 @@ class FlatAdam:
             return
         self._check("step_range")
         g = self.model.flat_grad()
-        begins = [min(max(b - lo, 0), hi - lo) for b in self.model.group_begin]
-        h_begin = (C.c_int64 * len(begins))(*begins)
         p = self.model.flat_params
         L.check(L.load().qed_adam_step(L.ptr(p[lo:hi]), L.ptr(g[lo:hi]), L.ptr(self.exp_avg[lo:hi]),
-                                       L.ptr(self.exp_avg_sq[lo:hi]), len(self.lr), C.cast(h_begin, C.c_void_p),
+                                       L.ptr(self.exp_avg_sq[lo:hi]), len(self.lr),
+                                       C.cast(self.model.layout.clipped_begin(lo, hi), C.c_void_p),
                                        C.cast(self._lr, C.c_void_p), self.betas[0], self.betas[1], self.eps, self.t,
                                        self._skip(), _stream()), "qed_adam_step")
 
@@ -220,8 +215,9 @@ class FlatAdam:
         reduced geometry gradients), 2 = the leading groups, 3 = both.  A data-parallel step calls 1 then 2 around the
         wait for the geometry all-reduce (``parallel.exchange_grads_compact_begin``)."""
         assert part in (1, 2, 3) and (fused_sh or part == 3)
-        p = self.model.flat_params
-        g = self.model.flat_grad()
+        m = self.model
+        p = m.flat_params
+        g = m.flat_grad()
         if g is None:
             return
         self._check("step", compact_ok=fused_sh)
@@ -241,7 +237,6 @@ class FlatAdam:
             self.t += 1
             _counted_step(self, self.model.device)
         if fused_sh:
-            m = self.model
             rec = explicit_record(m)
             if rec is None:
                 raise RuntimeError("fused_sh needs gradients from fused_loss(..., compact_sh_grad=True)")
@@ -253,19 +248,19 @@ class FlatAdam:
                 part, self._ticked = part | 4, False
             L.check(lib.qed_adam_step_sh(
                 L.ptr(p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), len(self.lr),
-                C.cast(self._begin, C.c_void_p), None if device_state else C.cast(self._lr, C.c_void_p),
+                m.layout.c_begin_ptr, None if device_state else C.cast(self._lr, C.c_void_p),
                 L.ptr(self.dev_lr) if device_state else None, self.betas[0], self.betas[1], self.eps, self.t,
                 L.ptr(self.dev_state) if device_state else None, *sched, m.num_points, rec.deg, L.ptr(m.means),
                 *rec.optimiser_views(g, m.group_begin).c_args(), int(part), self._skip(), _stream()), "qed_adam_step_sh")
             return
         if device_state:
             L.check(lib.qed_adam_step_dev(L.ptr(p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                          len(self.lr), C.cast(self._begin, C.c_void_p), L.ptr(self.dev_lr),
+                                          len(self.lr), m.layout.c_begin_ptr, L.ptr(self.dev_lr),
                                           self.betas[0], self.betas[1], self.eps, L.ptr(self.dev_state), self._skip(),
                                           _stream()), "qed_adam_step_dev")
             return
         L.check(lib.qed_adam_step(L.ptr(p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                  len(self.lr), C.cast(self._begin, C.c_void_p), C.cast(self._lr, C.c_void_p),
+                                  len(self.lr), m.layout.c_begin_ptr, C.cast(self._lr, C.c_void_p),
                                   self.betas[0], self.betas[1], self.eps, self.t, self._skip(), _stream()),
                 "qed_adam_step")
 

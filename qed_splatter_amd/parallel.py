@@ -420,10 +420,8 @@ def _compact_buffers(model, g, n_rows: int, fill: bool = True):
     """(geometry slice of the flat gradient, this rank's message, the receive buffer, 3 N, message length): the
     message buffers are persistent, so captured graphs keep reading the right memory.  ``fill=False``: the message has been
     written already (early_gather)."""
-    names, begin = model.group_names, model.group_begin
-    i_dc, i_rest = names.index("features_dc"), names.index("features_rest")
-    assert i_dc == 4 and i_rest == 5, "group order: geometry groups first, then features_dc, features_rest"
-    geo, v_local = g[:begin[i_dc]], g[begin[i_dc]:begin[i_dc + 1]]
+    lo, hi = model.layout.span("features_dc")     # (the geometry groups lie ahead of it, features_rest behind it)
+    geo, v_local = g[:lo], g[lo:hi]
     nv = v_local.numel()                                          # 3 N
     # one message per rank: colour gradients + view matrix + (bits of) this rank's intersection-overflow word (4 floats, so
     # that rows stay 16-byte aligned): the optimiser step is skipped on EVERY rank when ANY rank's frame overflowed

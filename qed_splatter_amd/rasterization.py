@@ -30,6 +30,7 @@ from torch import Tensor
 
 from . import _lib as L
 from .binning import _WORKSPACES, _Workspace, _bin_and_sort, _workspace  # noqa: F401  (callers know them here)
+from .layout import FlatLayout
 
 
 _stream = L.current_stream
@@ -220,19 +221,19 @@ class _ProjectSH(torch.autograd.Function):
         dev = means.device
         vsplat = _packed_vsplat(C, N, v_means2d, v_depths, v_conics, v_opac, v_rgb, dev)
 
-        # All parameter gradients live in ONE allocation, in the order
-        # (means, scales, quats, opacities, sh0, shN) = qed_splatter_amd.model.GROUP_ORDER, so a
-        # caller can all-reduce / Adam-step them as a single contiguous range.
+        # All parameter gradients live in ONE allocation, in the order (means, scales, quats, opacities, sh0, shN) =
+        # layout.GROUP_ORDER, so a caller can all-reduce / Adam-step them as a single contiguous range.
         k_active = (sh_degree + 1) ** 2 if sh_degree >= 0 else 1
-        n_sh0 = sh0.numel()
-        n_shN = shN.numel() if shN is not None else 0
-        flat = torch.empty(11 * N + n_sh0 + n_shN, dtype=torch.float32, device=dev)
-        v_means = flat[0:3 * N].view(N, 3)
-        v_scales = flat[3 * N:6 * N].view(N, 3)
-        v_quats = flat[6 * N:10 * N].view(N, 4)
-        v_opacities = flat[10 * N:11 * N]
-        v_sh0 = flat[11 * N:11 * N + n_sh0].view(sh0.shape)
-        v_shN = flat[11 * N + n_sh0:].view(shN.shape) if shN is not None else None
+        # (colours [N,K,3] in one tensor: 3 K floats in the sh0 group, none in shN)
+        layout = FlatLayout.with_sh_widths(N, sh0.numel() // max(N, 1), shN.numel() // max(N, 1) if shN is not None else 0)
+        flat = layout.empty(dev)
+        v_means, v_scales, v_quats, v_opacities, v_sh0, v_shN = layout.views(flat).values()
+        if v_sh0.shape != sh0.shape:
+            v_sh0 = v_sh0.view(sh0.shape)
+        if shN is None:
+            v_shN = None
+        elif v_shN.shape != shN.shape:
+            v_shN = v_shN.view(shN.shape)
         if sh0.dim() == 3:                      # colours [N,K,3] in one tensor
             if k_active < sh0.shape[1]:
                 v_sh0.zero_()                   # coefficients above the active degree get zero gradient

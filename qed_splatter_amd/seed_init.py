@@ -34,7 +34,7 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
-from .model import GROUP_ORDER
+from .layout import GROUP_ORDER, FlatLayout, group_widths  # noqa: F401  (both names are also importable from here)
 from .pointcloud_metrics import DEFAULT_MAX_RINGS, NNIndex, _device_of, _raw_points
 
 MAX_K = 8
@@ -104,10 +104,6 @@ def load_3d_points(ply_path, transform_matrix, scale_factor: float) -> Optional[
     return {"points3D_xyz": pts, "points3D_rgb": rgb}
 
 
-def group_widths(sh_degree: int):
-    return (3, 3, 4, 1, 3, 3 * ((int(sh_degree) + 1) ** 2 - 1))
-
-
 @torch.no_grad()
 def random_points(num_random: int, random_scale: float, seed: int, device) -> Tensor:
     """splatfacto's random initialisation ``(rand(num_random, 3) - 0.5) * random_scale`` from the package's generator."""
@@ -144,13 +140,10 @@ def seed_gaussians(points, colors=None, *, sh_degree: int = 3, k: int = 3, seed:
         if col.dtype != torch.uint8 or tuple(col.shape) != (n, 3):
             raise ValueError(f"colors must be uint8 of shape [{n}, 3], got {col.dtype} {tuple(col.shape)}")
         col = col.to(dev).contiguous()
-    widths = group_widths(sh_degree)
-    flat = torch.empty(n * sum(widths), dtype=torch.float32, device=dev)
-    views, off = {}, 0
-    for name, w in zip(GROUP_ORDER, widths):
-        views[name] = flat[off:off + n * w]
-        off += n * w
-    views["means"].view(n, 3).copy_(given)                            # (rounds float64 to float32; not re-centred)
+    layout = FlatLayout.for_sh_degree(n, sh_degree)
+    flat = layout.empty(dev)
+    views = layout.views(flat)
+    views["means"].copy_(given)                           # (rounds float64 to float32; not re-centred)
     index = NNIndex(t, n, cell_size)
     dist, _, fallback = index.knn(t, k, max_rings, force_brute, skip_first=True)
     status = torch.zeros(L.STATUS_WORDS, dtype=torch.int32, device=dev)
@@ -158,12 +151,9 @@ def seed_gaussians(points, colors=None, *, sh_degree: int = 3, k: int = 3, seed:
         L.check(lib.qed_seed_gaussians(n, L.ptr(dist), int(k), L.ptr(col), (int(sh_degree) + 1) ** 2,
                                        int(seed) & (2 ** 64 - 1), float(min_distance), 0, L.ptr(views["scales"]),
                                        L.ptr(views["quats"]), L.ptr(views["opacities"]), L.ptr(views["features_dc"]),
-                                       L.ptr(views["features_rest"]) if widths[5] else 0, L.ptr(status),
+                                       L.ptr(views["features_rest"]) if sh_degree else 0, L.ptr(status),
                                        L.current_stream()), "qed_seed_gaussians")
-    out = {"means": views["means"].view(n, 3), "scales": views["scales"].view(n, 3), "quats": views["quats"].view(n, 4),
-           "opacities": views["opacities"].view(n, 1), "features_dc": views["features_dc"].view(n, 3),
-           "features_rest": views["features_rest"].view(n, widths[5] // 3, 3), "flat": flat, "clamped": status[:1],
-           "fallback": fallback[:1]}
+    out = {**views, "flat": flat, "clamped": status[:1], "fallback": fallback[:1]}
     n_clamped = int(status[0])
     if n_clamped:
         warnings.warn(f"seed_gaussians: {n_clamped} of {n} points have a mean distance to their {k} nearest neighbours below "

@@ -86,8 +86,9 @@ class CompactSHGrad:
         model.__dict__["compact_sh"] = None
         means = model.gauss_params["means"]
         if not self.implicit:
-            g, b = flat_grad if flat_grad is not None else model.flat_grad(), model.group_begin
-            return write_sh_grads(means, self.optimiser_views(g, b), self.deg, g[b[-3]:b[-2]], g[b[-2]:])
+            g = flat_grad if flat_grad is not None else model.flat_grad()
+            (dc, rest), (_, end) = model.layout.span("features_dc"), model.layout.span("features_rest")
+            return write_sh_grads(means, self.optimiser_views(g, model.group_begin), self.deg, g[dc:rest], g[rest:end])
         if means._version != self.means_version or means.data_ptr() != self.means_ptr or means.shape[0] != self.n:
             raise RuntimeError(
                 "lazy SH gradients: the means were modified after the backward pass and before the gradients of features_dc "
