@@ -69,8 +69,7 @@ extern "C" {
  *   3  round 5: qed_composite_fwd gained `tile_order` behind `tile_cost`.
  *   4  qed_adam_tick_t carries beta1 / beta2 as doubles (they were floats): the device-resident bias corrections are
  *      formed at double precision, as the host-state path forms them.
- * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_present_range,
- * qed_present_frame). */
+ * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_color_correct). */
 #define QED_ABI_VERSION 4
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
@@ -931,6 +930,29 @@ int qed_pose_step(int32_t n_rows, int32_t row, float* pose_adjustment, float* ex
                   const float* c2w_in, float* v_viewmats, float trans_l2_penalty, float rot_l2_penalty, float lr,
                   double beta1, double beta2, float eps, int32_t step, float* raw_grad, float* reg_out,
                   const int32_t* skip_flag, void* stream);
+
+/* ---- colour correction of an evaluation render against its ground truth (csrc/color_correct.hip) --------------------
+ * nerfstudio's lib_bilagrid.color_correct (a port of multinerf's), what SplatfactoModelConfig.color_corrected_metrics
+ * applies before cc_psnr / cc_ssim / cc_lpips.  With x = img, r = ref ([n_pix,3], values in [0,1]),
+ * unclipped(z) = (z >= eps) & (z <= 1 - eps) and mask0 = unclipped(img), num_iters times:
+ *   a(x) = (rr, rg, rb, gg, gb, bb, r, g, b, 1);  m_c = mask0[c] & unclipped(x[c]) & unclipped(r[c]);
+ *   w_c = the least-squares solution of (m_c a) w = m_c r[c];  x <- clip(a(x) [w_0 w_1 w_2], 0, 1) on ALL pixels.
+ * out[n_pix,3] receives the last x (num_iters == 0: img itself).  warps_out (device double[num_iters][3][10], may be
+ * NULL) receives every iteration's w_c, [iteration][channel][feature]; the pixels are warped with these values rounded to
+ * float32, in float32.  The sums of the normal equations are carried in double and solved in double by Cholesky with
+ * diagonal pivoting: a column whose remaining pivot is <= 1e-10 x the largest original diagonal entry is dropped and its
+ * coefficient is 0 (upstream's lstsq returns the minimum-norm solution instead; the fitted values on the pixels of the
+ * fit are the same).  A channel without an unmasked pixel gets w = 0.  A pixel with a non-finite value in img or ref
+ * takes part in no fit, for every eps; where it is warped its non-finite values are read as 0, and with num_iters >= 1 out
+ * holds no NaN (num_iters == 0 copies img bit for bit, non-finite values included).  2 num_iters + 1 launches, no allocation, nothing is read back, no floating-point atomics: the same input gives
+ * the same bits.  workspace: QED_COLOR_CORRECT_WS_DOUBLES doubles (no zeroing needed).  Rejected: num_iters outside
+ * [0, QED_COLOR_CORRECT_MAX_ITERS], eps outside [0, 0.5), NULL or misaligned pointers. */
+#define QED_COLOR_CORRECT_MAX_ITERS 8
+#define QED_COLOR_CORRECT_MAX_GRID 512        /* workgroups of the summing pass */
+#define QED_COLOR_CORRECT_SUMS_STRIDE 196     /* doubles per workgroup: 3 x (55 + 10) sums, padded */
+#define QED_COLOR_CORRECT_WS_DOUBLES (QED_COLOR_CORRECT_MAX_GRID * QED_COLOR_CORRECT_SUMS_STRIDE + 120)
+int qed_color_correct(int32_t n_pix, const float* img, const float* ref, int32_t num_iters, float eps,
+                      double* workspace, double* warps_out, float* out, void* stream);
 
 #ifdef __cplusplus
 }

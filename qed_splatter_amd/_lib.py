@@ -113,6 +113,7 @@ SIGNATURES = {
     "qed_pose_apply": (C.c_int, [_I, _I, _P, _P, _I, _P, _P, _F, _F, _P, _P]),
     "qed_pose_apply_bwd": (C.c_int, [_I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "qed_pose_step": (C.c_int, [_I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _D, _D, _F, _I, _P, _P, _P, _P]),
+    "qed_color_correct": (C.c_int, [_I, _P, _P, _I, _F, _P, _P, _P, _P]),
 }
 
 class Post(C.Structure):
@@ -140,6 +141,9 @@ BILAGRID_STEP_MAX_VOLUME = 16384         # QED_BILAGRID_STEP_MAX_VOLUME
 MCMC_REG_WS_DOUBLES = 2048               # QED_MCMC_REG_WS_DOUBLES
 LPIPS_WS_DOUBLES = 5 * 256               # QED_LPIPS_WS_DOUBLES
 LPIPS_TILE_K, LPIPS_TILE_N = 16, 64      # QED_LPIPS_TILE_K, QED_LPIPS_TILE_N
+COLOR_CORRECT_MAX_ITERS = 8              # QED_COLOR_CORRECT_MAX_ITERS
+COLOR_CORRECT_MAX_GRID = 512             # QED_COLOR_CORRECT_MAX_GRID
+COLOR_CORRECT_WS_DOUBLES = 512 * 196 + 120   # QED_COLOR_CORRECT_WS_DOUBLES
 F_ANTIALIASED = 1
 F_LOG_SCALES = 2
 F_LOGIT_OPAC = 4

@@ -286,3 +286,15 @@ class FullImageDatamanager:
     def eval_items(self) -> Iterator[Tuple[PinholeCameras, GpuBatch]]:
         for j, k in enumerate(self.i_eval):
             yield self._hand_out(self._eval_cameras[j]), self._batch(k, j)
+
+    def train_items(self) -> Iterator[Tuple[PinholeCameras, GpuBatch]]:
+        """The training frames in the split's order (``next_train`` shuffles them; this does not touch its state)."""
+        for j, k in enumerate(self.i_train):
+            yield self._hand_out(self._train_cameras[j]), self._batch(k, j)
+
+    def all_items(self) -> Iterator[Tuple[PinholeCameras, GpuBatch]]:
+        """Both splits in the dataset's frame order; ``image_idx`` stays the frame's index within its own split."""
+        rows = [(k, self._train_cameras[j], j) for j, k in enumerate(self.i_train)]
+        rows += [(k, self._eval_cameras[j], j) for j, k in enumerate(self.i_eval)]
+        for k, cam, j in sorted(rows, key=lambda row: row[0]):
+            yield self._hand_out(cam), self._batch(k, j)

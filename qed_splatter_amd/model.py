@@ -86,6 +86,9 @@ class QEDSplatterModelConfig:
     # SplatfactoModelConfig.grid_shape: (X, Y, L) of each image's bilateral grid (built when use_bilateral_grid is set and
     # the model is given num_train_data)
     grid_shape: Tuple[int, int, int] = (16, 16, 8)
+    # SplatfactoModelConfig.color_corrected_metrics: get_image_metrics_and_images also reports cc_psnr / cc_ssim / cc_lpips
+    # of the render colour-corrected towards its ground truth (color_correct.py)
+    color_corrected_metrics: bool = False
     # the defaults below are SplatfactoModelConfig's (nerfstudio 1.1.x), which the reference's config.py:39-42 leaves
     # untouched: random training background, two halvings of the resolution that end at steps 3000 / 6000
     background_color: str = "random"         # "random" | "black" | "white"
@@ -1021,6 +1024,30 @@ class QEDSplatterModel(nn.Module):
             out["gaussian_count"] = self.num_points
             out["avg_min_scale"] = nanmean_exp(self.scales[..., -1])                  # model.py:192-194
         return _reference_key_order(out)
+
+    # ---- get_image_metrics_and_images (splatfacto's, inherited by the reference: the evaluation dictionary) ----
+    @torch.no_grad()
+    def get_image_metrics_and_images(self, outputs, batch) -> Tuple[Dict[str, Tensor], Dict[str, Tensor]]:
+        """(metrics, images) of one evaluation frame: ``psnr`` / ``ssim`` / ``lpips`` of the ground truth (composited onto
+        the render's background) and ``outputs["rgb"]``; with ``config.color_corrected_metrics`` also ``cc_psnr`` /
+        ``cc_ssim`` / ``cc_lpips`` of the ground truth and ``color_correct(rgb, gt)``.  Every value is a 0-dim device tensor
+        (upstream converts each with ``float(.item())``); ``lpips`` / ``cc_lpips`` are NaN without ``config.lpips_weights``.
+        ``images["img"]`` is the ground truth and the render side by side, [H, 2W, 3]."""
+        from .metrics import _lpips_or_nan, image_metrics, ssim_value
+        gt_rgb = self.composite_with_background(self.get_gt_img(batch["image"]), outputs["background"])
+        gt_rgb = gt_rgb.to(torch.float32).contiguous()
+        _refuse_overwritten(outputs["rgb"], "get_image_metrics_and_images")
+        rgb = outputs["rgb"][0] if outputs["rgb"].dim() == 4 else outputs["rgb"]
+        rgb = rgb.detach().to(torch.float32).contiguous()
+        lpips_w = self._lpips_weights()
+        metrics = {"psnr": image_metrics(rgb, gt_rgb)[1], "ssim": ssim_value(rgb, gt_rgb),
+                   "lpips": _lpips_or_nan(rgb, gt_rgb, lpips_w)}
+        if self.config.color_corrected_metrics:
+            from .color_correct import color_correct
+            cc_rgb = color_correct(rgb, gt_rgb)
+            metrics.update({"cc_psnr": image_metrics(cc_rgb, gt_rgb)[1], "cc_ssim": ssim_value(cc_rgb, gt_rgb),
+                            "cc_lpips": _lpips_or_nan(cc_rgb, gt_rgb, lpips_w)})
+        return metrics, {"img": torch.cat([gt_rgb, rgb], dim=1)}
 
     def _lpips_weights(self):
         """config.lpips_weights, loaded and packed once per device (None when it is not set)."""

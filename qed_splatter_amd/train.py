@@ -3,7 +3,7 @@
     python -m qed_splatter_amd.train --data DIR --steps 30000 [--save ckpt.pt] [--resume ckpt.pt]
                                      [--export-ply splat.ply [--export-frame dataset]] [--render-eval DIR]
                                      [--camera-optimizer SO3xR3 [--camera-opt-lr 1e-4] [--save-poses poses.json]]
-                                     [--use-bilateral-grid [--grid-shape 16 16 8]]
+                                     [--use-bilateral-grid [--grid-shape 16 16 8]] [--color-corrected-metrics]
 
 The dataset is read by ``dataparser.parse_dataset``, cached by ``datamanager.FullImageDatamanager`` (uint8 images on
 the GPU), and every step takes the next training camera and its frame through the eager fused route: ``fused_loss``
@@ -16,7 +16,10 @@ CameraOptimizer, two extra launches per step); ``--save-poses`` writes the refin
 
 ``--use-bilateral-grid`` gives every training image a grid of affine colour transforms (bilagrid.py: splatfacto's
 use_bilateral_grid) that absorbs its exposure and white balance; the grids train on the same route (one slice launch each way
-and one launch, qed_bilagrid_step, for their TV gradient and Adam step).  Evaluation renders stay uncorrected, as upstream.
+and one launch, qed_bilagrid_step, for their TV gradient and Adam step).  Evaluation renders stay uncorrected, as upstream;
+``--color-corrected-metrics`` (splatfacto's color_corrected_metrics) adds, under ``"eval_images"``, the evaluation split's
+psnr / ssim / lpips and the same three of every render colour-corrected towards its ground truth (``Trainer.evaluate_images``,
+color_correct.py) -- the figures that do not measure the cameras' exposure differences.
 
 The Gaussians are seeded from the dataset's ``ply_file_path`` (``--init-from-ply`` overrides it) in the frame of the
 cameras, or from random points when there is none.  Every ``--eval-every`` steps and at the end the evaluation split
@@ -117,6 +120,10 @@ class Trainer:
         out["gaussian_count"] = model.num_points
         return out
 
+    def evaluate_images(self, get_std: bool = True) -> Dict[str, float]:
+        """The evaluation split through ``evaluate_image_items``: Nerfstudio's get_average_eval_image_metrics."""
+        return evaluate_image_items(self.model, self.datamanager.eval_items(), get_std)
+
     def save(self, path) -> None:
         """The six tensors, the step, the optimiser state -- and the dataparser's transform and scale and the SH degree,
         so that ``python -m qed_splatter_amd.gaussian_ply export --frame dataset`` works from the file alone."""
@@ -184,6 +191,61 @@ class Trainer:
         # (a checkpoint written without a camera optimiser: the poses start from zero adjustments)
         if self.camera_optimizer is not None and "camera_opt" in ckpt:
             self.camera_optimizer.load_state_dict(ckpt["camera_opt"])
+
+
+@torch.no_grad()
+def evaluate_image_items(model: QEDSplatterModel, items, get_std: bool = True) -> Dict[str, float]:
+    """``items`` ((camera, batch) pairs) through eval() / get_outputs / get_image_metrics_and_images (Nerfstudio's
+    get_average_eval_image_metrics, what ``ns-eval`` reports): for every key the mean over the frames and, with
+    ``get_std``, ``KEY_std``, the unbiased standard deviation (``torch.std_mean``: NaN for a single frame); ``fps`` and
+    ``num_rays_per_sec`` from the render time alone (events around get_outputs).  The per-frame values stay on the device
+    until all frames are done: one synchronisation, one read-back."""
+    was_training = model.training
+    model.eval()
+    per_frame, render_events, rays = [], [], []
+    timed = model.device.type == "cuda"
+    try:
+        for camera, batch in items:
+            if timed:
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+            outputs = model.get_outputs(camera)
+            if timed:
+                t1.record()
+                render_events.append((t0, t1))
+            rays.append(int(outputs["rgb"].shape[-3]) * int(outputs["rgb"].shape[-2]))
+            per_frame.append(model.get_image_metrics_and_images(outputs, batch)[0])
+    finally:
+        model.train(was_training)
+    out = aggregate_image_metrics(per_frame, get_std)
+    if render_events:
+        torch.cuda.synchronize(model.device)
+        seconds = [max(a.elapsed_time(b), 1e-6) * 1e-3 for a, b in render_events]
+        out.update(aggregate_image_metrics([{"num_rays_per_sec": n / s, "fps": 1.0 / s} for n, s in zip(rays, seconds)],
+                                           get_std))
+    return out
+
+
+def aggregate_image_metrics(per_frame, get_std: bool = True) -> Dict[str, float]:
+    """[{key: 0-dim tensor or number}] per frame -> {key: mean, key_std: unbiased standard deviation} as floats, the keys in
+    the first frame's order (Nerfstudio's get_average_eval_image_metrics: ``torch.std_mean`` of the per-frame values, so a
+    single frame has the standard deviation NaN).  All keys are stacked on their device and read back once."""
+    if not per_frame:
+        return {}
+    keys = list(per_frame[0])
+    as_f64 = lambda v: v.detach().reshape(()).to(torch.float64) if torch.is_tensor(v) else torch.tensor(float(v), dtype=torch.float64)
+    table = torch.stack([torch.stack([as_f64(m[k]) for m in per_frame]) for k in keys])       # [keys, frames]
+    if table.shape[1] > 1:
+        std, mean = torch.std_mean(table, dim=1)                           # (unbiased)
+    else:
+        std, mean = torch.full_like(table[:, 0], float("nan")), table[:, 0]
+    mean, std = torch.stack([mean, std]).tolist()
+    out: Dict[str, float] = {}
+    for i, k in enumerate(keys):
+        out[k] = float(mean[i])
+        if get_std:
+            out[f"{k}_std"] = float(std[i])
+    return out
 
 
 def exp_map_SO3xR3_f64(pose_adjustment: np.ndarray) -> np.ndarray:
@@ -274,11 +336,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="one grid of affine colour transforms per training image (splatfacto's use_bilateral_grid; bilagrid.py)")
     ap.add_argument("--grid-shape", type=int, nargs=3, metavar=("X", "Y", "L"), default=[16, 16, 8],
                     help="the extents of each bilateral grid (every one >= 2, X * Y * L <= 16384)")
+    # (argparse.SUPPRESS: the parsed namespace of a command line without the option is what it was before the option)
+    ap.add_argument("--color-corrected-metrics", action="store_true", default=argparse.SUPPRESS,
+                    help="after the last evaluation, run the evaluation split through get_image_metrics_and_images with "
+                         "splatfacto's color_corrected_metrics (color_correct.py) and add the result as \"eval_images\"")
     return ap
 
 
 def main(argv=None) -> Dict:
     a = build_parser().parse_args(argv)
+    color_corrected = bool(getattr(a, "color_corrected_metrics", False))
     if a.use_bilateral_grid:
         check_step_shape(*a.grid_shape)
     if not torch.cuda.is_available():
@@ -293,7 +360,8 @@ def main(argv=None) -> Dict:
     dm = FullImageDatamanager(a.data, dp_cfg, device=a.cache_device, seed=a.seed)
     config = QEDSplatterModelConfig(num_downscales=a.num_downscales, resolution_schedule=a.resolution_schedule,
                                     background_color=a.background_color, sh_degree=a.sh_degree,
-                                    use_bilateral_grid=a.use_bilateral_grid, grid_shape=tuple(a.grid_shape))
+                                    use_bilateral_grid=a.use_bilateral_grid, grid_shape=tuple(a.grid_shape),
+                                    color_corrected_metrics=color_corrected)
     model = build_model(config, dm, a.init_from_ply, a.seed)
     print(f"seeded {model.num_points} Gaussians")
     trainer = Trainer(model, dm, seed=a.seed,
@@ -328,6 +396,8 @@ def main(argv=None) -> Dict:
         result["camera_opt"] = trainer.camera_opt_metrics()
     if trainer.grid_optimizer is not None:
         result["tv_loss"] = float(losses["tv_loss"]) if losses is not None else None
+    if color_corrected:
+        result["eval_images"] = trainer.evaluate_images()
     if a.save_poses:
         result["save_poses"] = trainer.save_poses(a.save_poses, a.data)
         print(f"wrote {result['save_poses']} training poses to {a.save_poses}")
