@@ -69,7 +69,8 @@ extern "C" {
  *   3  round 5: qed_composite_fwd gained `tile_order` behind `tile_cost`.
  *   4  qed_adam_tick_t carries beta1 / beta2 as doubles (they were floats): the device-resident bias corrections are
  *      formed at double precision, as the host-state path forms them.
- * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_color_correct). */
+ * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_gaussian_normals,
+ * qed_normal_maps, qed_depth_normals, qed_angular_error). */
 #define QED_ABI_VERSION 4
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
@@ -953,6 +954,56 @@ int qed_pose_step(int32_t n_rows, int32_t row, float* pose_adjustment, float* ex
 #define QED_COLOR_CORRECT_WS_DOUBLES (QED_COLOR_CORRECT_MAX_GRID * QED_COLOR_CORRECT_SUMS_STRIDE + 120)
 int qed_color_correct(int32_t n_pix, const float* img, const float* ref, int32_t num_iters, float eps,
                       double* workspace, double* warps_out, float* out, void* stream);
+
+/* ---- normal maps at evaluation / rendering time (csrc/normals.hip) ----------------------------------------------------
+ * A Gaussian's normal, one (camera, Gaussian) slot per thread.  means[N,3], RAW quats[N,4] (wxyz), scales[N,3] (with
+ * QED_F_LOG_SCALES in `flags`: logarithms), viewmats[C,4,4]:
+ *   k = the index of the smallest scale (lowest index on an exact tie);  n_w = column k of R(q / |q|) (a zero quaternion:
+ *   n_w = 0, never NaN);  o = -R_v^T t the camera origin of the view matrix;  n_w is negated where dot(n_w, mean - o) > 0,
+ *   so it faces the camera;  the result is n_w (QED_NORMALS_WORLD) or R_v n_w (QED_NORMALS_CAMERA: the OpenCV frame of
+ *   `viewmats`, x right, y down, z forward -- a surface facing the camera has n_z < 0).
+ * normals_out[C,N,3] (may be NULL).  splats / splats_out (both may be NULL): splats_out[C*N][12] receives the record of
+ * qed_project_fwd with slots 6, 7, 8 (r, g, b) replaced by the normal and every other slot copied bit for bit (culled
+ * slots and the packed rectangle of slot 11 included); 16-byte aligned, must not overlap `splats`.  ONE call of
+ * qed_composite_fwd with channels = 3, splats_out, the colour pass's own flatten_ids / offsets and no background then
+ * gives the accumulated normal A(p) = Sum_i alpha_i T_i n_i with the weights of the colour image: no second projection, no
+ * second binning.  N == 0 or C == 0 launches nothing. */
+#define QED_NORMALS_WORLD 0
+#define QED_NORMALS_CAMERA 1
+int qed_gaussian_normals(int32_t N, int32_t C, const float* means, const float* quats, const float* scales,
+                         const float* viewmats, const float* splats, int32_t frame, uint32_t flags,
+                         float* normals_out, float* splats_out, void* stream);
+/* One pass over an image.  accum[H,W,3] = A, alpha[H,W], depth = the accumulated depth D, read at depth[p * depth_stride]
+ * (1: a plain [H,W] map; 4: channel 3 of an RGB+D render, passed as render + 3):
+ *   normal[H,W,3] = A / |A| where alpha >= min_alpha and |A| > 1e-8, else 0;
+ *   surface depth z = D / alpha where alpha >= min_alpha (alpha == NULL: z = D); invalid where not finite or <= 0;
+ *   P(x,y) = ((x + .5 - cx) / fx z, (y + .5 - cy) / fy z, z);  dx = P(x+1,y) - P(x-1,y), dy = P(x,y+1) - P(x,y-1);
+ *   depth_normal[H,W,3] = normalize(dy x dx) -- (0, 0, -1) for a fronto-parallel plane -- and 0 at every border pixel (so
+ *   everywhere in an image under 3 x 3), where the pixel or one of its four neighbours is invalid, and where
+ *   |dy x dx| <= 1e-20.  The stencil is evaluated in double from the float32 inputs.
+ *   valid[H,W] u8: QED_NV_NORMAL | QED_NV_DEPTH_NORMAL.  rgb8 (may be NULL; [H,W,3] u8): the usual colouring for files,
+ *   round(255 (.5 + .5 (n_x, -n_y, -n_z))), a facing surface blue-violet, black = undefined -- of `normal` in
+ *   qed_normal_maps (of the depth normal when accum == NULL), of the depth normal in qed_depth_normals.
+ * accum / normal may be NULL (bit 0 stays clear), depth_normal may be NULL.  qed_depth_normals is the alpha-free half with
+ * the same body, for a sensor depth map. */
+#define QED_NV_NORMAL 1
+#define QED_NV_DEPTH_NORMAL 2
+int qed_normal_maps(int32_t height, int32_t width, const float* accum, const float* alpha, const float* depth,
+                    int32_t depth_stride, float fx, float fy, float cx, float cy, float min_alpha, float* normal,
+                    float* depth_normal, uint8_t* valid, uint8_t* rgb8, void* stream);
+int qed_depth_normals(int32_t height, int32_t width, const float* depth, int32_t depth_stride, float fx, float fy,
+                      float cx, float cy, float* depth_normal, uint8_t* valid, uint8_t* rgb8, void* stream);
+/* Angular error between two normal images a, b [n_pix,3] (unit vectors where valid).  A pixel counts where
+ * (valid_a[i] & bits_a) and (valid_b[i] & bits_b) are non-zero and mask (u8, may be NULL) is non-zero.  Its angle is
+ * atan2(|a x b|, a . b) in radians (well conditioned at 0 and pi, where acos of a float32 dot product is not).
+ * angle[n_pix] (may be NULL) receives it, NaN where the pixel does not count.  out[5] (device doubles) = {sum of angles,
+ * count, count of angles < t0, < t1, < t2} (the first n_thresholds of them, 0 to 3; radians).  Sums are carried in double
+ * and folded in a fixed order (2 launches, no floating-point atomics): the same input gives the same bits.
+ * workspace: QED_ANGULAR_WS_DOUBLES doubles (no zeroing needed). */
+#define QED_ANGULAR_WS_DOUBLES (5 * 1024)
+int qed_angular_error(int32_t n_pix, const float* a, const float* b, const uint8_t* valid_a, uint32_t bits_a,
+                      const uint8_t* valid_b, uint32_t bits_b, const uint8_t* mask, int32_t n_thresholds, float t0,
+                      float t1, float t2, double* workspace, float* angle, double* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Evaluate a checkpoint on a dataset -- what ``ns-eval --load-config ... --output-path OUT.json`` does in the reference:
 
     python -m qed_splatter_amd.eval --load CKPT --data DIR --output-path OUT.json [--color-corrected-metrics]
-                                    [--lpips-weights W] [--split eval|train|all]
+                                    [--lpips-weights W] [--split eval|train|all] [--output-normals]
 
 The model and the cameras are built as ``render.py dataset`` builds them (``load_model``, the dataparser options of the
 training run, checked against the checkpoint's ``dataparser_scale``); every frame of the split goes through ``eval()`` /
@@ -12,7 +12,9 @@ training run, checked against the checkpoint's ``dataparser_scale``); every fram
 
 ``--color-corrected-metrics`` (splatfacto's color_corrected_metrics) adds ``cc_psnr`` / ``cc_ssim`` / ``cc_lpips``: the same
 metrics of every render colour-corrected towards its ground truth (color_correct.py).  ``lpips`` / ``cc_lpips`` are NaN
-without ``--lpips-weights`` (no weights are shipped or fetched).  The same object is printed as the last line of output.
+without ``--lpips-weights`` (no weights are shipped or fetched).  ``--output-normals`` adds the angular errors of the
+rendered normal maps, in degrees (``normal_depth_mae``, ``normal_sensor_mae``, ``normal_sensor_under_11.25`` ...;
+normals.py).  The same object is printed as the last line of output.
 """
 from __future__ import annotations
 
@@ -36,6 +38,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--output-path", required=True, metavar="OUT.json")
     ap.add_argument("--color-corrected-metrics", action="store_true",
                     help="also cc_psnr / cc_ssim / cc_lpips (splatfacto's color_corrected_metrics; color_correct.py)")
+    ap.add_argument("--output-normals", action="store_true",
+                    help="also normal_depth_mae / normal_sensor_mae / normal_sensor_under_*: angular errors, in degrees, of the "
+                         "rendered normal maps against the normals of the rendered and of the sensor depth (normals.py)")
     ap.add_argument("--lpips-weights", metavar="W", default=None,
                     help="LPIPS weights: one merged file, or AlexNet's and the lin layers' files joined by the path separator")
     ap.add_argument("--split", choices=("eval", "train", "all"), default="eval")
@@ -71,6 +76,7 @@ def main(argv=None) -> Dict:
     model, ckpt = load_model(a.load, device, a.background_color)
     model.config.color_corrected_metrics = bool(a.color_corrected_metrics)
     model.config.lpips_weights = a.lpips_weights
+    model.config.output_normals = bool(a.output_normals)
     dp_cfg = DataparserConfig(orientation_method=a.orientation_method, center_method=a.center_method,
                               auto_scale_poses=a.auto_scale_poses == "True",
                               depth_unit_scale_factor=a.depth_unit_scale_factor,

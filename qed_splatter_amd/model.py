@@ -128,6 +128,13 @@ class QEDSplatterModelConfig:
     # LPIPS weights for the rgb_lpips entry of get_metrics_dict (lpips.py): one merged file, or AlexNet's and the lin
     # layers' files joined by os.pathsep.  None: the entry stays NaN.  Nothing is ever fetched
     lpips_weights: Optional[str] = None
+    # get_outputs() outside training also returns "normal" (the rendered normal map, OpenCV camera frame: a facing surface
+    # has n_z < 0), "depth_normal" (the normals of the rendered depth), "normal_valid" (uint8: bit 0 / bit 1 say where each
+    # is defined) and "normal_vis" (the uint8 colouring of "normal"); get_image_metrics_and_images then reports their
+    # angular errors (normals.py).  Pixels whose accumulation is under normals_min_alpha have no normal.  Training is
+    # unaffected: there is no normal loss
+    output_normals: bool = False
+    normals_min_alpha: float = 0.5
 
     @classmethod
     def synthetic(cls, **kw) -> "QEDSplatterModelConfig":
@@ -807,6 +814,8 @@ class QEDSplatterModel(nn.Module):
             flags |= L.F_SH_GRAD_COMPACT
 
         background = self._get_background_color()
+        # config.output_normals: evaluation and rendering only (the records of the projection stay reachable for it)
+        want_normals = bool(getattr(self.config, "output_normals", False)) and not self.training
 
         # the camera's launch order (fused_loss: frame_key): the reference's trainer hands the camera index in
         # camera.metadata["cam_idx"]; only on the eager route -- a captured segment is replayed for every camera
@@ -830,7 +839,7 @@ class QEDSplatterModel(nn.Module):
                 _flags=flags, _sh_rest=sh_rest, _sync=not (self.config.async_intersection_count and self.training),
                 _c2w=(c2w, intr) if c2w is not None else None, _post_background=bg, _handover=handover,
                 _means2d_leaf=True,     # xys is only retained and read (below; densify.py): its gradient arrives as a view
-                _capture_slot=capture_slot, _manual=manual,
+                _capture_slot=capture_slot, _manual=manual, _keep_records=want_normals,
                 # (a captured backward pass always writes the compact form; _SegmentFn.backward asks per replay)
                 _lazy_sh=self._lazy_sh_begin if (lazy and manual is None) else None)
 
@@ -883,12 +892,33 @@ class QEDSplatterModel(nn.Module):
         # gradient goes straight to the compositing backward: they are bound to the image BEFORE a bilateral grid, so a
         # corrected image takes the general path of get_loss_dict / get_metrics_dict
         ctx.bind(rgb if pre_grid is None else pre_grid, handover)
-        return {
+        outputs = {
             "rgb": rgb,
             "depth": depth_im,
             "accumulation": alpha.squeeze(0),
             "background": background,
         }
+        if want_normals:
+            outputs.update(self._normal_outputs(means_crop, quats_crop, scales_crop, viewmat, K, info, render, alpha))
+        return outputs
+
+    @torch.no_grad()
+    def _normal_outputs(self, means, quats, scales, viewmat, K, info, render, alpha) -> Dict[str, Tensor]:
+        """config.output_normals: the normal planes of the (cropped) set this call rendered, from the colour pass's own
+        records and tile lists (normals.render_normals: three launches, no second projection or binning).  The intrinsics
+        are read back from ``K`` (one small copy; evaluation only)."""
+        from .normals import render_normals
+        if render is None or render.shape[-1] != 4 or viewmat.shape[0] != 1:
+            raise NotImplementedError("output_normals needs the RGB+D render of one camera (evaluation mode)")
+        k = K[0].detach().cpu()
+        intr = (float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2]))
+        out = render_normals(means, quats, scales, viewmat, info, alpha[0], render[0, ..., 3], intr,
+                             min_alpha=float(self.config.normals_min_alpha), log_scales=True, colors=True)
+        info.pop("_splats", None)                # (24 MB at 500 k Gaussians: not kept alive by self.info)
+        info.pop("_isect_offsets_full", None)
+        out["normal"]._qed_intrinsics = intr     # (get_image_metrics_and_images: the sensor depth's normals)
+        return {"normal": out["normal"], "depth_normal": out["depth_normal"], "normal_valid": out["valid"],
+                "normal_vis": out["rgb8"]}
 
     # ---- a11: get_loss_dict (model.py:73-118) ----
     def _scale_reg(self) -> Tensor:
@@ -1047,7 +1077,32 @@ class QEDSplatterModel(nn.Module):
             cc_rgb = color_correct(rgb, gt_rgb)
             metrics.update({"cc_psnr": image_metrics(cc_rgb, gt_rgb)[1], "cc_ssim": ssim_value(cc_rgb, gt_rgb),
                             "cc_lpips": _lpips_or_nan(cc_rgb, gt_rgb, lpips_w)})
+        if outputs.get("normal") is not None and outputs.get("normal_valid") is not None:
+            metrics.update(self._normal_metrics(outputs, batch))
         return metrics, {"img": torch.cat([gt_rgb, rgb], dim=1)}
+
+    def _normal_metrics(self, outputs, batch) -> Dict[str, Tensor]:
+        """config.output_normals: mean angular errors in DEGREES (0-dim device tensors; NaN where no pixel is valid on both
+        sides).  ``normal_depth_mae``: the rendered normals against the normals of the rendered depth.  With a
+        ``depth_image`` in the batch, ``normal_sensor_mae`` and ``normal_sensor_under_11.25`` / ``_22.5`` / ``_30``: the
+        rendered normals against the normals of the sensor depth (downscaled as the other ground truth is, at the render's
+        intrinsics, inside ``batch["mask"]`` if present) and the fractions of pixels under those angles."""
+        from .normals import angular_error, depth_to_normals
+        normal, valid = outputs["normal"], outputs["normal_valid"]
+        H, W = int(normal.shape[0]), int(normal.shape[1])
+        own = angular_error(normal, outputs["depth_normal"], valid, valid, bits_a=L.NV_NORMAL, bits_b=L.NV_DEPTH_NORMAL)
+        out = {"normal_depth_mae": own["mean_deg"].float()}
+        intr = getattr(normal, "_qed_intrinsics", None)         # (fx, fy, cx, cy) of the render, left by get_outputs
+        if "depth_image" in batch and intr is not None:
+            gt_depth = _f32_image(self.get_gt_img(batch["depth_image"]), H * W, "batch['depth_image']", self.device)
+            sensor, sensor_ok = depth_to_normals(gt_depth.reshape(H, W), *intr)
+            mask = self._loss_mask(batch, (H, W))
+            err = angular_error(normal, sensor, valid, sensor_ok, mask=(mask.reshape(H, W) > 0) if mask is not None else None,
+                                bits_a=L.NV_NORMAL)
+            out["normal_sensor_mae"] = err["mean_deg"].float()
+            for key in ("under_11.25", "under_22.5", "under_30"):
+                out[f"normal_sensor_{key}"] = err[key].float()
+        return out
 
     def _lpips_weights(self):
         """config.lpips_weights, loaded and packed once per device (None when it is not set)."""

@@ -1,0 +1,264 @@
+"""Surface normals at evaluation / rendering time: a Gaussian's normal, the rendered normal map, the normals of a depth map
+and the angular error between two normal images (csrc/normals.hip; include/qed_splat.h states every definition).
+
+    python -m qed_splatter_amd.normals --depth FILE --fx FX [--fy FY --cx CX --cy CY --depth-unit U] --out PNG
+
+The frame convention: normals live in the OpenCV camera frame of the view matrices (x right, y down, z forward), so a
+surface that faces the camera has ``n_z < 0``; a fronto-parallel plane has the normal (0, 0, -1).  ``frame="world"`` gives a
+Gaussian's normal in the world frame instead.  A Gaussian's normal is the axis of its smallest scale, turned towards the
+camera -- the convention of dn-splatter / AGS-Mesh, RESTATED FROM MEMORY of those projects, not checked against them.
+
+``mean_angular_error`` holds the reference's statements (metrics.py:66-80), ``acos`` of the clamped dot product per row;
+the device metric ``angular_error`` uses ``atan2(|a x b|, a . b)`` instead -- a stated deviation: the two agree on unit
+vectors, and the second is well conditioned at 0 and pi, where ``acos`` of a float32 dot product loses half the digits.
+
+The normal render (``render_normals``) makes no second projection and no second binning: ``qed_gaussian_normals`` writes a
+second set of the projection's records with the normal in the colour slots, and ONE more call of the forward compositing
+kernel over the colour pass's own tile lists accumulates A = Sum_i alpha_i T_i n_i.  Nothing here is differentiable: there
+is no normal loss in training.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Sequence, Tuple
+
+import torch
+from torch import Tensor
+
+from . import _lib as L
+
+_stream = L.current_stream
+
+
+def mean_angular_error(pred: Tensor, gt: Tensor) -> Tensor:
+    """The reference's ``mean_angular_error`` (metrics.py:66-80) on whatever device the tensors live.  Despite the name it
+    returns the PER-ROW angle in radians, [B], of vectors [B,C]: ``acos(clamp(sum(gt * pred, dim=1), -1, 1))``."""
+    dot_products = torch.sum(gt * pred, dim=1)
+    dot_products = torch.clamp(dot_products, -1.0, 1.0)
+    mae = torch.acos(dot_products)
+    return mae
+
+
+def _f32(t: Tensor, name: str) -> Tensor:
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise TypeError(f"{name} must be a float32 tensor")
+    if not t.is_cuda:
+        raise L.QedSplatError(f"{name} must live on the GPU: the normal kernels have no CPU path")
+    return t.detach().contiguous()
+
+
+def _frame_id(frame: str) -> int:
+    if frame not in ("camera", "world"):
+        raise ValueError(f"frame {frame!r}: 'camera' or 'world'")
+    return L.NORMALS_CAMERA if frame == "camera" else L.NORMALS_WORLD
+
+
+def gaussian_normals(means: Tensor, quats: Tensor, scales: Tensor, viewmats: Tensor, frame: str = "camera",
+                     log_scales: bool = True, splats: Optional[Tensor] = None):
+    """[C,N,3]: per camera, every Gaussian's normal -- the axis of its smallest scale (lowest index on a tie) of
+    R(q / |q|), turned to face the camera, in the camera frame or the world frame.  ``quats`` are raw (wxyz), ``scales``
+    logarithms when ``log_scales``.  With ``splats`` (qed_project_fwd's records [C*N,12]) returns ``(normals, records)``:
+    the records with the normal in the colour slots 6..8 and everything else copied bit for bit."""
+    means, quats, scales = _f32(means, "means"), _f32(quats, "quats"), _f32(scales, "scales")
+    viewmats = _f32(viewmats, "viewmats")
+    N, C = means.shape[0], viewmats.shape[0]
+    if means.shape != (N, 3) or quats.shape != (N, 4) or scales.shape != (N, 3) or viewmats.shape != (C, 4, 4):
+        raise ValueError("means [N,3], quats [N,4], scales [N,3], viewmats [C,4,4]")
+    out = torch.empty(C, N, 3, dtype=torch.float32, device=means.device)
+    records = None
+    if splats is not None:
+        splats = _f32(splats, "splats")
+        if splats.numel() != C * N * L.SPLAT_FLOATS:
+            raise ValueError(f"splats: {C * N} records of {L.SPLAT_FLOATS} floats")
+        records = torch.empty_like(splats)
+    L.check(L.load().qed_gaussian_normals(N, C, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(viewmats), L.ptr(splats),
+                                          _frame_id(frame), L.F_LOG_SCALES if log_scales else 0, L.ptr(out),
+                                          L.ptr(records), _stream()), "qed_gaussian_normals")
+    return out if splats is None else (out, records)
+
+
+def accumulate_normals(records: Tensor, info: Dict, C: int, N: int) -> Tensor:
+    """A[C,H,W,3] = Sum_i alpha_i T_i n_i: one call of the forward compositing kernel on ``records``
+    (``gaussian_normals(..., splats=...)``) with the tile lists of the colour pass that produced ``info``."""
+    W, H, tw, th = int(info["width"]), int(info["height"]), int(info["tile_width"]), int(info["tile_height"])
+    dev = records.device
+    offsets = info["_isect_offsets_full"]
+    flatten_ids = info["flatten_ids"]
+    accum = torch.empty(C, H, W, 3, dtype=torch.float32, device=dev)
+    alpha = torch.empty(C, H, W, 1, dtype=torch.float32, device=dev)
+    last_ids = torch.empty(C, H, W, dtype=torch.int32, device=dev)
+    L.check(L.load().qed_composite_fwd(C, N, L.ptr(records), L.ptr(flatten_ids), L.ptr(offsets), W, H, tw, th, 3, None,
+                                       L.ptr(accum), L.ptr(alpha), None, L.ptr(last_ids), None, None, None,
+                                       L.composite_launch_flags(), _stream()), "qed_composite_fwd")
+    return accum
+
+
+def normal_maps(accum: Tensor, alpha: Tensor, depth: Tensor, fx: float, fy: float, cx: float, cy: float,
+                min_alpha: float = 0.5, colors: bool = False) -> Dict[str, Tensor]:
+    """One pass over one image: ``accum`` [H,W,3] (the accumulated normal), ``alpha`` [H,W(,1)], ``depth`` [H,W(,1)] the
+    ACCUMULATED depth (any view with a constant element stride, e.g. ``render[..., 3]``).  -> {"normal" [H,W,3] = A / |A|,
+    "depth_normal" [H,W,3] (of z = depth / alpha), "valid" uint8 [H,W] (bit 0: normal, bit 1: depth normal)} and, with
+    ``colors``, "rgb8" uint8 [H,W,3], the usual colouring of "normal" (black = undefined)."""
+    accum, alpha = _f32(accum, "accum"), _f32(alpha, "alpha")
+    H, W = int(accum.shape[0]), int(accum.shape[1])
+    depth, stride = _strided_plane(depth, H, W)
+    if accum.shape != (H, W, 3) or alpha.numel() != H * W:
+        raise ValueError("accum [H,W,3], alpha [H,W]")
+    dev = accum.device
+    out = {"normal": torch.empty(H, W, 3, dtype=torch.float32, device=dev),
+           "depth_normal": torch.empty(H, W, 3, dtype=torch.float32, device=dev),
+           "valid": torch.empty(H, W, dtype=torch.uint8, device=dev)}
+    if colors:
+        out["rgb8"] = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    L.check(L.load().qed_normal_maps(H, W, L.ptr(accum), L.ptr(alpha), L.ptr(depth), stride, fx, fy, cx, cy, min_alpha,
+                                     L.ptr(out["normal"]), L.ptr(out["depth_normal"]), L.ptr(out["valid"]),
+                                     L.ptr(out.get("rgb8")), _stream()), "qed_normal_maps")
+    return out
+
+
+def _strided_plane(depth: Tensor, H: int, W: int) -> Tuple[Tensor, int]:
+    """(tensor whose data_ptr is pixel 0, element stride between pixels) of an [H,W] or [H,W,1] float32 GPU view; a view that
+    is not evenly strided is copied."""
+    if not torch.is_tensor(depth) or depth.dtype != torch.float32 or not depth.is_cuda:
+        raise TypeError("depth must be a float32 GPU tensor")
+    depth = depth.detach()
+    if depth.dim() == 3 and depth.shape[2] == 1:
+        depth = depth[..., 0]
+    if depth.shape != (H, W):
+        raise ValueError(f"depth {tuple(depth.shape)}: expected {H}x{W}")
+    s = depth.stride()
+    st = int(s[1]) if W > 1 else (int(s[0]) if H > 1 else 1)       # pixel (y, x) must sit at (y W + x) * st
+    if st < 1 or (H > 1 and W > 1 and s[0] != W * st):
+        return depth.contiguous(), 1
+    return depth, st
+
+
+def depth_to_normals(depth: Tensor, fx: float, fy: float, cx: float, cy: float, alpha: Optional[Tensor] = None,
+                     min_alpha: float = 0.5, colors: bool = False):
+    """``(normals [H,W,3], valid bool [H,W])`` of a depth map [H,W(,1)] by central differences of the back-projected points
+    P(x,y) = ((x + .5 - cx) / fx z, (y + .5 - cy) / fy z, z): normalize(dy x dx), (0, 0, -1) for a fronto-parallel plane.
+    Without ``alpha`` the map is a sensor's (z = depth); with it, an accumulated depth (z = depth / alpha where
+    alpha >= min_alpha).  Undefined (0, valid False) at border pixels and where the pixel or a 4-neighbour has no finite
+    positive depth.  ``colors``: a third result, the uint8 [H,W,3] colouring."""
+    if not torch.is_tensor(depth):
+        raise TypeError("depth must be a tensor")
+    if depth.dim() == 3 and depth.shape[2] == 1:
+        depth = depth[..., 0]
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    depth, stride = _strided_plane(depth, H, W)
+    dev = depth.device
+    normals = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    valid = torch.empty(H, W, dtype=torch.uint8, device=dev)
+    rgb8 = torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if colors else None
+    lib = L.load()
+    if alpha is None:
+        L.check(lib.qed_depth_normals(H, W, L.ptr(depth), stride, fx, fy, cx, cy, L.ptr(normals), L.ptr(valid), L.ptr(rgb8),
+                                      _stream()), "qed_depth_normals")
+    else:
+        alpha = _f32(alpha, "alpha")
+        if alpha.numel() != H * W:
+            raise ValueError("alpha [H,W]")
+        L.check(lib.qed_normal_maps(H, W, None, L.ptr(alpha), L.ptr(depth), stride, fx, fy, cx, cy, min_alpha, None,
+                                    L.ptr(normals), L.ptr(valid), L.ptr(rgb8), _stream()), "qed_normal_maps")
+    ok = (valid & L.NV_DEPTH_NORMAL) != 0
+    return (normals, ok, rgb8) if colors else (normals, ok)
+
+
+_WS: Dict[torch.device, Tensor] = {}
+
+
+def _valid_plane(v: Tensor, n_pix: int, name: str) -> Tensor:
+    if v.dtype == torch.bool:
+        v = v.view(torch.uint8) if v.is_contiguous() else v.contiguous().view(torch.uint8)
+    if v.dtype != torch.uint8 or not v.is_cuda or v.numel() != n_pix:
+        raise ValueError(f"{name}: a bool or uint8 GPU tensor of {n_pix} values")
+    return v.contiguous()
+
+
+def angular_error(a: Tensor, b: Tensor, valid_a: Tensor, valid_b: Tensor, mask: Optional[Tensor] = None,
+                  thresholds_deg: Sequence[float] = (11.25, 22.5, 30.0), bits_a: int = 0xff, bits_b: int = 0xff) -> Dict:
+    """Angular error of two normal images [...,3] over the pixels valid on both sides (``valid_*``: bool, or uint8 planes
+    tested against ``bits_*``) and inside ``mask`` (bool / uint8, optional).  -> {"mean_deg", "count", "under_<t>" for up to
+    three thresholds in degrees (the FRACTION of counted pixels with a smaller angle), "angle" (radians, the image's shape,
+    NaN where not counted)}; the scalars are 0-dim device tensors (float64), NaN -- count 0 -- where no pixel counts.  Nothing
+    is read back; two runs give the same bits."""
+    a, b = _f32(a, "a"), _f32(b, "b")
+    if a.shape != b.shape or a.shape[-1] != 3:
+        raise ValueError("a, b: two [...,3] images of one shape")
+    if len(thresholds_deg) > 3:
+        raise ValueError("at most three thresholds")
+    n_pix = a.numel() // 3
+    dev = a.device
+    va, vb = _valid_plane(valid_a, n_pix, "valid_a"), _valid_plane(valid_b, n_pix, "valid_b")
+    m = _valid_plane(mask.to(dev), n_pix, "mask") if mask is not None else None
+    ws = _WS.get(dev)
+    if ws is None:
+        ws = _WS[dev] = torch.empty(L.ANGULAR_WS_DOUBLES, dtype=torch.float64, device=dev)
+    angle = torch.empty(a.shape[:-1], dtype=torch.float32, device=dev)
+    out = torch.empty(5, dtype=torch.float64, device=dev)
+    t = [math.radians(float(x)) for x in thresholds_deg] + [0.0, 0.0, 0.0]
+    L.check(L.load().qed_angular_error(n_pix, L.ptr(a), L.ptr(b), L.ptr(va), int(bits_a), L.ptr(vb), int(bits_b), L.ptr(m),
+                                       len(thresholds_deg), t[0], t[1], t[2], L.ptr(ws), L.ptr(angle), L.ptr(out),
+                                       _stream()), "qed_angular_error")
+    res = {"mean_deg": out[0] / out[1] * (180.0 / math.pi), "count": out[1]}          # (0 / 0: NaN)
+    for k, deg in enumerate(thresholds_deg):
+        res[f"under_{float(deg):g}"] = out[2 + k] / out[1]
+    res["angle"] = angle
+    return res
+
+
+def render_normals(means: Tensor, quats: Tensor, scales: Tensor, viewmats: Tensor, info: Dict, alpha: Tensor, depth: Tensor,
+                   intrinsics: Sequence[float], min_alpha: float = 0.5, log_scales: bool = True,
+                   colors: bool = False) -> Dict[str, Tensor]:
+    """The normal outputs of ONE camera's colour pass: ``info`` is that pass's (rasterization's third result, with its
+    ``_splats`` / ``_isect_offsets_full`` entries), ``alpha`` [H,W(,1)] its alpha and ``depth`` its accumulated depth.
+    Three launches: qed_gaussian_normals, qed_composite_fwd, qed_normal_maps.  -> ``normal_maps``' dict plus "accum"."""
+    C, N = viewmats.shape[0], means.shape[0]
+    if C != 1:
+        raise NotImplementedError("render_normals takes one camera (get_outputs renders one at a time)")
+    _, records = gaussian_normals(means, quats, scales, viewmats, "camera", log_scales, splats=info["_splats"])
+    accum = accumulate_normals(records, info, C, N)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    out = normal_maps(accum[0], alpha, depth, fx, fy, cx, cy, min_alpha, colors=colors)
+    out["accum"] = accum[0]
+    return out
+
+
+def main(argv=None) -> dict:
+    import argparse
+    import json
+
+    import numpy as np
+    ap = argparse.ArgumentParser(prog="python -m qed_splatter_amd.normals",
+                                 description="The normal map of one depth file (16-bit PNG or .npy), as an 8-bit RGB PNG.")
+    ap.add_argument("--depth", required=True, metavar="FILE")
+    ap.add_argument("--fx", type=float, required=True)
+    ap.add_argument("--fy", type=float, default=None, help="default: fx")
+    ap.add_argument("--cx", type=float, default=None, help="default: width / 2")
+    ap.add_argument("--cy", type=float, default=None, help="default: height / 2")
+    ap.add_argument("--depth-unit", type=float, default=0.001, help="metres per step of an integer depth file")
+    ap.add_argument("--out", required=True, metavar="PNG")
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("qed_splatter_amd.normals needs a GPU")
+    if a.depth.endswith(".npy"):
+        d = np.load(a.depth)
+    else:
+        from PIL import Image
+        d = np.asarray(Image.open(a.depth))
+    scale = a.depth_unit if np.issubdtype(d.dtype, np.integer) else 1.0
+    d = np.ascontiguousarray(d.astype(np.float32).reshape(d.shape[0], d.shape[1])) * np.float32(scale)
+    H, W = d.shape
+    depth = torch.from_numpy(d).to("cuda:0")
+    _, ok, rgb8 = depth_to_normals(depth, a.fx, a.fy if a.fy is not None else a.fx, a.cx if a.cx is not None else W / 2.0,
+                                   a.cy if a.cy is not None else H / 2.0, colors=True)
+    from .render import encode_png
+    with open(a.out, "wb") as f:
+        f.write(encode_png(rgb8.cpu().numpy()))
+    result = {"output": a.out, "height": H, "width": W, "valid_fraction": float(ok.float().mean()) if H * W else 0.0}
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main()

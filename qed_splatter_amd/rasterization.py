@@ -465,6 +465,7 @@ def rasterization(
     _sync: bool = True, _handover=None, _c2w: Optional[Tuple[Tensor, Tensor]] = None,
     _post_background: Optional[Tensor] = None, _means2d_leaf: bool = False, _capture_slot=None,
     _manual: Optional[list] = None, _lazy_sh=None, _post_bwd=None, _pose_grad: Optional[Tensor] = None,
+    _keep_records: bool = False,
 ) -> Tuple[Tensor, Tensor, Dict]:
     """Same call surface as the reference's call (model.py:267-288).
 
@@ -479,6 +480,8 @@ def rasterization(
     its own to them in place (the views alias the flat gradient).  ``_pose_grad`` [C,4,4]: a persistent, zeroed buffer the
     projection backward adds the view matrices' gradient to (qed_project_bwd's v_viewmats) although ``viewmats`` does not
     require grad: the camera optimiser of the fused route (camera_optimizer.py), whose qed_pose_step reads and zeroes it.
+    ``_keep_records``: ``info["_splats"]`` (the projection's packed records [C*N,12]) and ``info["_isect_offsets_full"]`` (the
+    tile offsets with their end sentinel) stay reachable for a further compositing pass over the same lists (normals.py).
     """
     if packed or sparse_grad:
         raise NotImplementedError("packed=True / sparse_grad=True are not used by the reference (model.py:278,283)")
@@ -565,4 +568,6 @@ def rasterization(
     if _post_background is not None:
         info["post_rgb"] = outs[3]
         info["post_depth"] = outs[4] if channels == 4 else None
+    if _keep_records:
+        info["_splats"], info["_isect_offsets_full"] = splats, offsets
     return render, alpha, info

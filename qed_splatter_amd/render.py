@@ -15,7 +15,8 @@ stream while the next frame renders, PNG encoding in a thread pool.
 
 Files: ``rgb/00042.png``, ``depth/00042.png`` (16-bit, in the dataset's own unit: ``depth_unit_scale_factor`` metres of
 the ORIGINAL scene per step, i.e. value = rendered depth / (dataparser_scale * depth_unit_scale_factor); 0 = no surface,
-as the datasets store "no measurement"), ``depth_vis/00042.png`` (colour map over white), ``accumulation/00042.png``.
+as the datasets store "no measurement"), ``depth_vis/00042.png`` (colour map over white), ``accumulation/00042.png``;
+with ``--planes ... normal`` also ``normal/00042.png``, the rendered normal map (normals.py) in the usual colouring.
 The depth files are read back by datamanager._load_depth, init_pointcloud and PDMetrics like any dataset's.
 
 Camera paths are float64 host arithmetic.  ``load_camera_path`` reads the viewer's ``camera_path.json``; its layout is
@@ -47,7 +48,10 @@ from . import _lib as L
 from .model import GROUP_ORDER, PinholeCameras, QEDSplatterModel, QEDSplatterModelConfig
 
 PLANES = ("rgb", "depth16", "depthmap", "alpha")
-PLANE_DIRS = {"rgb": "rgb", "depth16": "depth", "depthmap": "depth_vis", "alpha": "accumulation"}
+# planes that are not part of the default: "normal" (the rendered normal map as 8-bit RGB, normals.py) turns
+# config.output_normals on for the run
+EXTRA_PLANES = ("normal",)
+PLANE_DIRS = {"rgb": "rgb", "depth16": "depth", "depthmap": "depth_vis", "alpha": "accumulation", "normal": "normal"}
 MAX_WORKERS = 16
 
 _TURBO_HEX = (
@@ -116,10 +120,14 @@ def present_frame(outputs, *, depth_unit: float, near: Optional[float] = None, f
                  over white by the accumulation.  Both None: the frame's own range of valid depths, found on the device
                  and never read back
 
+      "normal"   uint8 [H,W,3] (not in the default): ``outputs["normal_vis"]``, the colouring of the rendered normal map that
+                 get_outputs made with config.output_normals -- round(255 (.5 + .5 (n_x, -n_y, -n_z))) of the camera-frame
+                 normal, a facing surface blue-violet, black where there is none
+
     An ``outputs["depth"]`` of None leaves both depth planes out of the result.  Launched on the current stream."""
-    unknown = [p for p in planes if p not in PLANES]
+    unknown = [p for p in planes if p not in PLANES + EXTRA_PLANES]
     if unknown:
-        raise ValueError(f"planes {unknown}: choose from {PLANES}")
+        raise ValueError(f"planes {unknown}: choose from {PLANES + EXTRA_PLANES}")
     if (near is None) != (far is None):
         raise ValueError("near and far: give both or neither")
     rgb, depth, alpha = outputs["rgb"], outputs.get("depth"), outputs["accumulation"]
@@ -127,10 +135,15 @@ def present_frame(outputs, *, depth_unit: float, near: Optional[float] = None, f
     rgb = _plane(rgb, "rgb", h, w, 3)
     alpha = _plane(alpha, "accumulation", h, w, 1)
     dev = rgb.device
-    want = [p for p in planes if depth is not None or p not in ("depth16", "depthmap")]
+    want = [p for p in planes if p in PLANES and (depth is not None or p not in ("depth16", "depthmap"))]
     if depth is not None:
         depth = _plane(depth, "depth", h, w, 1)
     out: Dict[str, Tensor] = {}
+    if "normal" in planes:
+        vis = outputs.get("normal_vis")
+        if vis is None:
+            raise ValueError("planes: 'normal' needs outputs of a model with config.output_normals (outputs['normal_vis'])")
+        out["normal"] = vis
     if not want:
         return out
     shapes = {"rgb": ((h, w, 3), torch.uint8), "depth16": ((h, w), torch.uint16), "depthmap": ((h, w, 3), torch.uint8),
@@ -186,9 +199,9 @@ class FrameWriter:
 
     def __init__(self, out_dir, planes: Sequence[str] = PLANES, n_slots: int = 3, n_workers: int = 8,
                  png_compress_level: int = 1):
-        unknown = [p for p in planes if p not in PLANES]
+        unknown = [p for p in planes if p not in PLANES + EXTRA_PLANES]
         if unknown:
-            raise ValueError(f"planes {unknown}: choose from {PLANES}")
+            raise ValueError(f"planes {unknown}: choose from {PLANES + EXTRA_PLANES}")
         if n_slots < 1 or n_workers < 1:
             raise ValueError("n_slots and n_workers must be at least 1")
         self.out_dir = Path(out_dir)
@@ -471,6 +484,9 @@ def render_frames(model: QEDSplatterModel, cameras: Sequence[PinholeCameras], wr
     under "render" and "finish" for measurements."""
     was_training = model.training
     model.eval()
+    had_normals = bool(getattr(model.config, "output_normals", False))
+    if "normal" in writer.planes:
+        model.config.output_normals = True      # (asking for the plane turns the normal pass on for this run)
     n = 0
     try:
         with torch.no_grad():
@@ -491,6 +507,7 @@ def render_frames(model: QEDSplatterModel, cameras: Sequence[PinholeCameras], wr
                 n += 1
     finally:
         model.train(was_training)
+        model.config.output_normals = had_normals
     return n
 
 
@@ -543,7 +560,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--steps-per-pair", type=int, default=10)
     ap.add_argument("--order-poses", action="store_true", help="interpolate: visit the cameras nearest-first")
     ap.add_argument("--camera-path-file", metavar="JSON", default=None)
-    ap.add_argument("--planes", nargs="+", choices=PLANES, default=list(PLANES))
+    ap.add_argument("--planes", nargs="+", choices=PLANES + EXTRA_PLANES, default=list(PLANES),
+                    help="'normal' (not in the default) adds normal/: the rendered normal map as 8-bit RGB")
     ap.add_argument("--colormap", choices=("turbo", "gray"), default="turbo")
     ap.add_argument("--near", type=float, default=None)
     ap.add_argument("--far", type=float, default=None, help="depth map range in model units (default: every frame's own)")

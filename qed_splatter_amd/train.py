@@ -340,12 +340,16 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--color-corrected-metrics", action="store_true", default=argparse.SUPPRESS,
                     help="after the last evaluation, run the evaluation split through get_image_metrics_and_images with "
                          "splatfacto's color_corrected_metrics (color_correct.py) and add the result as \"eval_images\"")
+    ap.add_argument("--output-normals", action="store_true", default=argparse.SUPPRESS,
+                    help="after training: render normal maps (normals.py) in the final \"eval_images\" evaluation, which then "
+                         "reports their angular errors, and write a normal/ plane with --render-eval; training is unaffected")
     return ap
 
 
 def main(argv=None) -> Dict:
     a = build_parser().parse_args(argv)
     color_corrected = bool(getattr(a, "color_corrected_metrics", False))
+    output_normals = bool(getattr(a, "output_normals", False))
     if a.use_bilateral_grid:
         check_step_shape(*a.grid_shape)
     if not torch.cuda.is_available():
@@ -396,15 +400,18 @@ def main(argv=None) -> Dict:
         result["camera_opt"] = trainer.camera_opt_metrics()
     if trainer.grid_optimizer is not None:
         result["tv_loss"] = float(losses["tv_loss"]) if losses is not None else None
-    if color_corrected:
+    if output_normals:
+        trainer.model.config.output_normals = True      # (from here on: the final evaluation and --render-eval only)
+    if color_corrected or output_normals:
         result["eval_images"] = trainer.evaluate_images()
     if a.save_poses:
         result["save_poses"] = trainer.save_poses(a.save_poses, a.data)
         print(f"wrote {result['save_poses']} training poses to {a.save_poses}")
     if a.render_eval:
-        from .render import dataset_path, render_to_directory
+        from .render import EXTRA_PLANES, PLANES, dataset_path, render_to_directory
         unit = float(dm.outputs.dataparser_scale) * float(dm.outputs.depth_unit_scale_factor)
-        result["render_eval"] = render_to_directory(trainer.model, dataset_path(dm, "eval"), a.render_eval, depth_unit=unit)
+        result["render_eval"] = render_to_directory(trainer.model, dataset_path(dm, "eval"), a.render_eval, depth_unit=unit,
+                                                    planes=PLANES + (EXTRA_PLANES if output_normals else ()))
         print(f"rendered {result['render_eval']['frames']} evaluation views to {a.render_eval}")
     print(json.dumps(result))
     return result
