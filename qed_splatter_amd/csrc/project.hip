@@ -501,19 +501,16 @@ __device__ __forceinline__ void sh_bwd(const float* __restrict__ sh0, const floa
     }
 }
 
-// The SH backward from the forward pass's hand-over (sh_color_jac): no coefficient is read.  STREAM: the coefficient
+// The SH backward from the forward pass's hand-over (sh_color_jac): no coefficient is read; J and mask_bits are this
+// slot's entries of the ten planes, loaded by the caller with the rest of its inputs.  STREAM: the coefficient
 // gradients go straight to memory (one camera); otherwise they are accumulated in v_coef.
 template <int DEG, bool STREAM>
-__device__ __forceinline__ void sh_bwd_jac(const float* __restrict__ jac /* this slot's first plane entry */, size_t plane,
-                                           const float* dir, const float* v_rgb_in, float* __restrict__ o0,
-                                           float* __restrict__ oN, float* v_coef, float* v_dir /*3, +=*/, bool compact,
+__device__ __forceinline__ void sh_bwd_jac(const float (&J)[9], float mask_bits, const float* dir,
+                                           const float* v_rgb_in, float* __restrict__ o0, float* __restrict__ oN, float* v_coef, float* v_dir /*3, +=*/, bool compact,
                                            float* stage_b = nullptr /*LDS: this lane's basis row*/,
                                            float* stage_v = nullptr) {
     constexpr int K = (DEG + 1) * (DEG + 1);
-    float J[9];
-#pragma unroll
-    for (int i = 0; i < (DEG > 0 ? 9 : 0); ++i) J[i] = jac[(size_t)i * plane];
-    const unsigned mask = __float_as_uint(jac[(size_t)9 * plane]);
+    const unsigned mask = __float_as_uint(mask_bits);
     const float n2 = dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2];
     const float inorm = rsqrtf(n2);
     const float x = dir[0] * inorm, y = dir[1] * inorm, z = dir[2] * inorm;
@@ -639,8 +636,43 @@ __device__ __forceinline__ void sh_grad_store_staged(const float* __restrict__ s
     }
 }
 
+// What project_bwd_kernel reads per Gaussian and camera: the radius, the three words of the gradient row and (JAC) the ten
+// planes of the hand-over.  Requested TOGETHER from a clamped slot, unconditionally, and pinned (pin): read where they
+// are used -- radii, then vsplat inside `if (vis)`, then the planes inside sh_bwd_jac -- they were three dependent
+// round trips behind the parameters' one, at two waves per SIMD.
+template <bool JAC, bool DEG_POS>
+struct PbwdLoads {
+    int rad;
+    float4 g0, g1, g2;
+    float J[9], mask_bits;
+    __device__ __forceinline__ void load(const int* __restrict__ radii, const float4* __restrict__ vsplat,
+                                         const float* __restrict__ sh_jac, size_t slot, size_t plane) {
+        rad = radii[slot];
+        load_rest(vsplat, sh_jac, slot, plane);
+    }
+    __device__ __forceinline__ void load_rest(const float4* __restrict__ vsplat, const float* __restrict__ sh_jac,
+                                              size_t slot, size_t plane) {
+        g0 = vsplat[4 * slot]; g1 = vsplat[4 * slot + 1]; g2 = vsplat[4 * slot + 2];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) J[i] = (JAC && DEG_POS) ? sh_jac[(size_t)i * plane + slot] : 0.f;
+        mask_bits = JAC ? sh_jac[(size_t)9 * plane + slot] : 0.f;
+    }
+    __device__ __forceinline__ void pin() {
+        asm volatile("" : "+v"(rad), "+v"(g0.x), "+v"(g0.y), "+v"(g0.z), "+v"(g0.w), "+v"(g1.x), "+v"(g1.y), "+v"(g1.z),
+                          "+v"(g1.w), "+v"(g2.x), "+v"(g2.y), "+v"(g2.z), "+v"(g2.w));
+        if constexpr (JAC) {
+            if constexpr (DEG_POS)
+                asm volatile("" : "+v"(J[0]), "+v"(J[1]), "+v"(J[2]), "+v"(J[3]), "+v"(J[4]), "+v"(J[5]), "+v"(J[6]),
+                                  "+v"(J[7]), "+v"(J[8]), "+v"(mask_bits));
+            else
+                asm volatile("" : "+v"(mask_bits));
+        }
+    }
+};
+
 // JAC: the SH part works from qed_project_fwd's sh_jac hand-over (sh_bwd_jac) instead of the coefficients: no basis-
-// derivative tables beside the projection state (183 registers without spills where the degree-3 kernel spills 22 of 256).
+// derivative tables beside the projection state (232 registers with the batch of loads held, without spills, where the
+// degree-3 kernel that reads the coefficients spills at 256).
 template <int DEG, bool ONE_CAM, bool JAC = false>
 #ifndef QED_PBWD_WAVES
 #define QED_PBWD_WAVES 2
@@ -673,18 +705,31 @@ project_bwd_kernel(int N, int C, const float* __restrict__ means, const float* _
     constexpr int kStageFloats = kStageSH ? 64 * (kKS + 4) : 1;
     __shared__ __attribute__((aligned(16))) float s_stage[4 * kStageFloats];
     float* const stage_wave = s_stage + (threadIdx.x >> 6) * kStageFloats;
+    __shared__ float s_vm[2][4][12];                        // the view-matrix gradient's per-wave partials
     const bool staged = kStageSH && !(flags & QED_F_SH_GRAD_COMPACT);
     float* const stage_b = staged ? stage_wave + (threadIdx.x & 63) * kKS : nullptr;
     float* const stage_v = staged ? stage_wave + 64 * kKS + 4 * (threadIdx.x & 63) : nullptr;
 
-    float mean[3] = {0.f, 0.f, 0.f}, qraw[4] = {1.f, 0.f, 0.f, 0.f}, q[4], sraw[3] = {0.f, 0.f, 0.f}, s[3];
-    float qin = 1.f, oraw = 0.f, oact = 0.f;
-    if (active) {
-        mean[0] = means[3 * n]; mean[1] = means[3 * n + 1]; mean[2] = means[3 * n + 2];
-        qraw[0] = quats[4 * n]; qraw[1] = quats[4 * n + 1]; qraw[2] = quats[4 * n + 2]; qraw[3] = quats[4 * n + 3];
-        sraw[0] = scales[3 * n]; sraw[1] = scales[3 * n + 1]; sraw[2] = scales[3 * n + 2];
-        oraw = opacities[n];
-    }
+    // Everything the Gaussian needs is requested here in one batch (ONE_CAM; with more cameras the per-camera part at the
+    // top of each iteration) from the clamped index: lanes beyond N read Gaussian 0's and never use or store anything
+    const int nc = active ? n : 0;
+    const size_t plane = (size_t)C * N;
+    float mean[3] = {means[3 * nc], means[3 * nc + 1], means[3 * nc + 2]};
+    float qraw[4] = {quats[4 * nc], quats[4 * nc + 1], quats[4 * nc + 2], quats[4 * nc + 3]};
+    float sraw[3] = {scales[3 * nc], scales[3 * nc + 1], scales[3 * nc + 2]};
+    float oraw = opacities[nc];
+    // (Not pinned where the batch does not fit: the coefficient routes of degree 2 and 3 carry the basis-derivative
+    // tables and the many-camera hand-over route of degree 3 its 48 accumulators, all at the 256-register limit, and
+    // 13-23 more registers held across project_one became 20-100 bytes more scratch there.  Their loads stay behind
+    // the tests that guard their first use, as before.)
+    constexpr bool kPin = DEG <= 1 || (JAC && (ONE_CAM || DEG == 2));
+    PbwdLoads<JAC, (DEG > 0)> ld;
+    if constexpr (ONE_CAM && kPin) ld.load(radii, vsplat, sh_jac, (size_t)nc, plane);
+    if constexpr (kPin)
+        asm volatile("" : "+v"(mean[0]), "+v"(mean[1]), "+v"(mean[2]), "+v"(qraw[0]), "+v"(qraw[1]), "+v"(qraw[2]),
+                          "+v"(qraw[3]), "+v"(sraw[0]), "+v"(sraw[1]), "+v"(sraw[2]), "+v"(oraw));
+    if constexpr (ONE_CAM && kPin) ld.pin();
+    float q[4], s[3], qin, oact;
     qin = rsqrtf(qraw[0] * qraw[0] + qraw[1] * qraw[1] + qraw[2] * qraw[2] + qraw[3] * qraw[3]);
 #pragma unroll
     for (int i = 0; i < 4; ++i) q[i] = qraw[i] * qin;
@@ -694,8 +739,12 @@ project_bwd_kernel(int N, int C, const float* __restrict__ means, const float* _
 
     for (int c = 0; c < C; ++c) {
         const Cam cam = load_cam(viewmats, Ks, c);
-        const size_t slot = (size_t)c * N + n;
-        const bool vis = active && radii[slot] > 0;
+        if constexpr (!ONE_CAM && kPin) {
+            ld.load(radii, vsplat, sh_jac, (size_t)c * N + nc, plane);
+            ld.pin();
+        }
+        if constexpr (!kPin) ld.rad = active ? radii[(size_t)c * N + n] : 0;
+        const bool vis = active && ld.rad > 0;
         float vR[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, vt[3] = {0.f, 0.f, 0.f};
         if constexpr (kStageSH) {
             if (staged && !vis) {                               // culled (or beyond N): a row of zeros
@@ -708,7 +757,8 @@ project_bwd_kernel(int N, int C, const float* __restrict__ means, const float* _
             Proj p;
             // radius_clip / near / far already decided in the forward pass (radii > 0)
             project_one(cam, mean, q, s, width, height, eps2d, -3.0e38f, 3.0e38f, -1.f, p);
-            const float4 g0 = vsplat[4 * slot], g1 = vsplat[4 * slot + 1], g2 = vsplat[4 * slot + 2];
+            if constexpr (!kPin) ld.load_rest(vsplat, sh_jac, (size_t)c * N + n, plane);
+            const float4 g0 = ld.g0, g1 = ld.g1, g2 = ld.g2;
             const float v_mx = g0.x, v_my = g0.y;
             float v_ca = g1.x, v_cb = g1.y, v_cc = g1.z;
             const float v_op = g1.w;
@@ -811,8 +861,7 @@ project_bwd_kernel(int N, int C, const float* __restrict__ means, const float* _
             if constexpr (DEG >= 0) {
                 const float dir[3] = {mean[0] - cam.campos[0], mean[1] - cam.campos[1], mean[2] - cam.campos[2]};
                 if constexpr (JAC) {
-                    const size_t plane = (size_t)C * N;
-                    sh_bwd_jac<(DEG < 0 ? 0 : DEG), kStreamSH>(sh_jac + slot, plane, dir, v_rgb,
+                    sh_bwd_jac<(DEG < 0 ? 0 : DEG), kStreamSH>(ld.J, ld.mask_bits, dir, v_rgb,
                                                                 v_sh0 + (size_t)n * v_sh0_stride,
                                                                 v_shN + (size_t)n * v_shN_stride, vcoef, vdir,
                                                                 (flags & QED_F_SH_GRAD_COMPACT) != 0, stage_b, stage_v);
@@ -897,16 +946,22 @@ project_bwd_kernel(int N, int C, const float* __restrict__ means, const float* _
                                         N - n0);
             }
         }
-        if (v_viewmats != nullptr) {
-            // block reduction -> 12 atomics per block per camera
+        if (v_viewmats != nullptr) {                            // (uniform over the launch)
+            // reduced over the wave, then over the workgroup's four waves in LDS in the fixed order (w0 + w1) + (w2 + w3):
+            // at most 12 atomics per workgroup and camera, issued by one wave.  Two buffers taking turns: one barrier
+            // per camera (a buffer is written again two iterations on, behind the next iteration's barrier).
+            float (*part)[12] = s_vm[c & 1];
 #pragma unroll
             for (int i = 0; i < 12; ++i) {
-                float v = i < 9 ? vR[i] : vt[i - 9];
-                v = wave_sum(v);
-                if ((threadIdx.x & 63) == 0 && v != 0.f) {
-                    const int row = i < 9 ? i / 3 : i - 9, col = i < 9 ? i % 3 : 3;
-                    atomicAdd(&v_viewmats[16 * c + 4 * row + col], v);
-                }
+                const float v = wave_sum(i < 9 ? vR[i] : vt[i - 9]);
+                if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][i] = v;
+            }
+            __syncthreads();
+            if (threadIdx.x < 12) {
+                const int i = threadIdx.x;
+                const float v = (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]);
+                const int row = i < 9 ? i / 3 : i - 9, col = i < 9 ? i % 3 : 3;
+                if (v != 0.f) atomicAdd(&v_viewmats[16 * c + 4 * row + col], v);
             }
         }
     }

@@ -422,6 +422,31 @@ ssim_bwd_kernel(int H, int W, int channels, const float* __restrict__ pred, cons
     float mo[CB];
 #pragma unroll
     for (int o = 0; o < CB; ++o) mo[o] = MASKED ? mask[(size_t)min(oy + ty0 + o, H - 1) * W + min(ix, W - 1)] : 1.f;
+    // The thread's own CB pixels, all channels, fetched ONCE ahead of the channel passes (as the forward kernel does).
+    // Read channel by channel inside the passes, the lines that hold them were wanted again in each pass (a 16-byte
+    // render pixel, a 12-byte colour: every pass touches every line), and between two passes of the ~96 workgroups on
+    // an XCD its 4 MB L2 also takes their 6 MB of coefficient patches: a third of what the launch fetched was a line
+    // it had fetched before (233 MB against 149 needed at 1080p; 166 MB now, 65 -> 61 us).
+    // Not in the FUSE 1 instances: at four waves per SIMD they spill 12-40 bytes with the 28 registers this holds.
+    constexpr bool kPreload = FUSE != 1;
+    float pc[CB][3], gc[CB][3], ac[CB];
+    if constexpr (kPreload) {
+        const bool four = FUSE == 4 || (FUSE != 3 && COMPOSITE && channels == 4);
+#pragma unroll
+        for (int o = 0; o < CB; ++o) {
+            const size_t pix = (size_t)min(oy + ty0 + o, H - 1) * W + min(ix, W - 1);
+            const Float3 gv = *reinterpret_cast<const Float3*>(gt + pix * 3);
+            gc[o][0] = gv.a; gc[o][1] = gv.b; gc[o][2] = gv.c;
+            if (four) {
+                const float4 pv = *reinterpret_cast<const float4*>(pred + pix * 4);
+                pc[o][0] = pv.x; pc[o][1] = pv.y; pc[o][2] = pv.z;
+            } else {
+                const Float3 pv = *reinterpret_cast<const Float3*>(pred + pix * 3);
+                pc[o][0] = pv.a; pc[o][1] = pv.b; pc[o][2] = pv.c;
+            }
+            ac[o] = COMPOSITE ? alpha[pix] : 1.f;
+        }
+    }
 #pragma unroll 1
     for (int k = 0; k < 3; ++k) {
         const float* m = maps + (size_t)k * 3 * n_out;
@@ -436,20 +461,30 @@ ssim_bwd_kernel(int H, int W, int channels, const float* __restrict__ pred, cons
             const bool in = qy >= 0 && qy < Ho && qx >= 0 && qx < Wo;
             mv[j][0] = in ? al : 0.f; mv[j][1] = in ? bl : 0.f; mv[j][2] = in ? cl : 0.f;
         }
-        // the output pixels' own colours, requested with the maps so their latency hides behind both passes
+        // the output pixels' own colours (FUSE 1: requested with the maps so their latency hides behind both passes)
         float xo[CB], yo[CB], pre[CB];
         const float bgk = COMPOSITE ? bg[k] : 0.f;
 #pragma unroll
         for (int o = 0; o < CB; ++o) {
-            const size_t pix = (size_t)min(oy + ty0 + o, H - 1) * W + min(ix, W - 1);
+            float pk, gk, ak;
+            if constexpr (kPreload) {
+                pk = k == 0 ? pc[o][0] : (k == 1 ? pc[o][1] : pc[o][2]);
+                gk = k == 0 ? gc[o][0] : (k == 1 ? gc[o][1] : gc[o][2]);
+                ak = ac[o];
+            } else {
+                const size_t pix = (size_t)min(oy + ty0 + o, H - 1) * W + min(ix, W - 1);
+                pk = pred[pix * (COMPOSITE ? channels : 3) + k];
+                gk = gt[pix * 3 + k];
+                ak = COMPOSITE ? alpha[pix] : 1.f;
+            }
             if constexpr (COMPOSITE) {
-                pre[o] = pred[pix * channels + k] + (1.f - alpha[pix]) * bgk;     // model.py:296 before the clamp
+                pre[o] = pk + (1.f - ak) * bgk;                                   // model.py:296 before the clamp
                 xo[o] = fminf(fmaxf(pre[o], 0.f), 1.f);
             } else {
                 pre[o] = 0.f;
-                xo[o] = pred[pix * 3 + k];
+                xo[o] = pk;
             }
-            yo[o] = gt[pix * 3 + k];
+            yo[o] = gk;
             if constexpr (MASKED) { xo[o] *= mo[o]; yo[o] *= mo[o]; }
         }
         __syncthreads();
