@@ -70,7 +70,7 @@ extern "C" {
  *   4  qed_adam_tick_t carries beta1 / beta2 as doubles (they were floats): the device-resident bias corrections are
  *      formed at double precision, as the host-state path forms them.
  * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_gaussian_normals,
- * qed_normal_maps, qed_depth_normals, qed_angular_error). */
+ * qed_normal_maps, qed_depth_normals, qed_angular_error; qed_normal_loss, qed_gaussian_normals_bwd, qed_normal_rows_merge). */
 #define QED_ABI_VERSION 4
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
@@ -1004,6 +1004,49 @@ int qed_depth_normals(int32_t height, int32_t width, const float* depth, int32_t
 int qed_angular_error(int32_t n_pix, const float* a, const float* b, const uint8_t* valid_a, uint32_t bits_a,
                       const uint8_t* valid_b, uint32_t bits_b, const uint8_t* mask, int32_t n_thresholds, float t0,
                       float t1, float t2, double* workspace, float* angle, double* out, void* stream);
+
+/* ---- normal supervision in training (csrc/normal_loss.hip) ---------------------------------------------------------------
+ * The loss is dn-splatter's normal loss RESTATED FROM MEMORY of that project, not checked against it.  Per pixel p:
+ *   n^(p) = A(p) / |A(p)| where alpha(p) >= min_alpha and |A(p)| > 1e-8 (qed_normal_maps' rule), undefined elsewhere;
+ *   g(p)  = the target, a unit normal in the OpenCV camera frame of the view matrix, valid where target_valid[p] & valid_bits
+ *           (qed_depth_normals' plane with QED_NV_DEPTH_NORMAL, or any u8 plane);
+ *   V     = the pixels where n^ is defined, g is valid and mask (float32, may be NULL) is non-zero.
+ *   normal_loss = normal_lambda * [ mean over V and the 3 channels of |n^_c - g_c|
+ *                                   + (use_cosine ? mean over V of (1 - n^ . g) : 0) ],   0 with zero gradients when V is empty.
+ * Gradients flow through A (d n^ / d A = (I - n^ n^T) / |A|), through every alpha_i T_i (qed_composite_bwd on the normal
+ * records, then qed_project_bwd, both unchanged) and through every n_i = +-R_v column k of R(q / |q|) to the RAW quaternion,
+ * normalisation Jacobian included (a zero quaternion: 0, never NaN).  The axis k and the facing sign are piecewise constant
+ * and carry no gradient; the direct dependence of n_i on the view rotation R_v is NOT differentiated (the host layers refuse
+ * a camera optimiser beside this loss).  Stated deviation from gsplat's absgrad (the sum over pixels of the absolute
+ * per-pixel gradient of the TOTAL loss, which two separate compositing passes cannot form): the normal pass adds to the
+ * signed 2-D mean gradient and NOT to the absgrad slots, which stay those of the colour and depth loss.
+ *
+ * qed_normal_loss: accum[n_pix,3] = A, alpha[n_pix], target[n_pix,3].  v_accum[n_pix,3] receives the UNSCALED per-pixel
+ *   d l / d A of l(p) = mean_c |n^_c - g_c| (+ 1 - n^ . g), zero outside V: d loss / d A = normal_lambda / max(|V|, 1) times
+ *   it, and since the compositing backward is linear in its upstream gradient that factor may be applied later, per row
+ *   (`scale` below), without a second pass over the image or a host read-back.  out[4] (device doubles) = {normal_loss,
+ *   the L1 mean, the cosine mean (0 without use_cosine), |V|}; out_f[2] (device floats, may be NULL) = {normal_loss,
+ *   normal_lambda / max(|V|, 1)}.  The per-pixel arithmetic is double from the float32 inputs; sums are carried in double
+ *   and folded in a fixed order (2 launches, no floating-point atomics): the same input gives the same bits.
+ *   workspace: QED_NORMAL_LOSS_WS_DOUBLES doubles (no zeroing needed).  n_pix == 0 writes zeros to out.
+ * qed_gaussian_normals_bwd: one thread per Gaussian, looping over the C cameras (no atomics).  normal_rows[C*N][16] = the
+ *   accumulator qed_composite_bwd filled for the records of qed_gaussian_normals(QED_NORMALS_CAMERA): slots 8..10 are
+ *   d L / d n_i in the camera frame.  means / quats / scales / viewmats / flags as qed_gaussian_normals, whose k, sign and
+ *   frame rules are applied to the same float32 inputs.  radii[C,N] (may be NULL): slots with radius <= 0 (culled) contribute
+ *   nothing.  scale (device float, may be NULL = 1) multiplies the result.  v_quats[N,4] is overwritten (add == 0) or added
+ *   to (add != 0).  normal_rows 16-byte aligned; quats / v_quats need float alignment only.
+ * qed_normal_rows_merge: rows[r][s] += scale * normal_rows[r][s] for slots s = 0, 1 (2-D mean) and 4..7 (conic, opacity)
+ *   of `total` rows of 16 floats, in place; slots 2, 3 (absgrad), 8..10 (colour), 11 (depth) and 12..15 of `rows` keep
+ *   their bits.  scale: device float, may be NULL = 1.  Both 16-byte aligned; one row per thread, 16-byte accesses. */
+#define QED_NORMAL_LOSS_WS_DOUBLES (3 * 1024)
+int qed_normal_loss(int32_t n_pix, const float* accum, const float* alpha, const float* target,
+                    const uint8_t* target_valid, uint32_t valid_bits, const float* mask, float min_alpha,
+                    int32_t use_cosine, float normal_lambda, double* workspace, float* v_accum, double* out,
+                    float* out_f, void* stream);
+int qed_gaussian_normals_bwd(int32_t N, int32_t C, const float* means, const float* quats, const float* scales,
+                             const float* viewmats, const int32_t* radii, const float* normal_rows, const float* scale,
+                             uint32_t flags, int32_t add, float* v_quats, void* stream);
+int qed_normal_rows_merge(int64_t total, const float* normal_rows, const float* scale, float* rows, void* stream);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,9 @@ SIGNATURES = {
     "qed_normal_maps": (C.c_int, [_I, _I, _P, _P, _P, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
     "qed_depth_normals": (C.c_int, [_I, _I, _P, _I, _F, _F, _F, _F, _P, _P, _P, _P]),
     "qed_angular_error": (C.c_int, [_I, _P, _P, _P, _U, _P, _U, _P, _I, _F, _F, _F, _P, _P, _P, _P]),
+    "qed_normal_loss": (C.c_int, [_I, _P, _P, _P, _P, _U, _P, _F, _I, _F, _P, _P, _P, _P, _P]),
+    "qed_gaussian_normals_bwd": (C.c_int, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _U, _I, _P, _P]),
+    "qed_normal_rows_merge": (C.c_int, [_L, _P, _P, _P, _P]),
 }
 
 class Post(C.Structure):
@@ -149,6 +152,7 @@ COLOR_CORRECT_MAX_ITERS = 8              # QED_COLOR_CORRECT_MAX_ITERS
 COLOR_CORRECT_MAX_GRID = 512             # QED_COLOR_CORRECT_MAX_GRID
 COLOR_CORRECT_WS_DOUBLES = 512 * 196 + 120   # QED_COLOR_CORRECT_WS_DOUBLES
 ANGULAR_WS_DOUBLES = 5 * 1024              # QED_ANGULAR_WS_DOUBLES
+NORMAL_LOSS_WS_DOUBLES = 3 * 1024          # QED_NORMAL_LOSS_WS_DOUBLES
 NORMALS_WORLD, NORMALS_CAMERA = 0, 1       # QED_NORMALS_WORLD, QED_NORMALS_CAMERA
 NV_NORMAL, NV_DEPTH_NORMAL = 1, 2          # QED_NV_NORMAL, QED_NV_DEPTH_NORMAL
 F_ANTIALIASED = 1

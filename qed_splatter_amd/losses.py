@@ -1,6 +1,6 @@
 """The image losses of a training step as autograd nodes over the loss kernels: the stand-alone SSIM (``ssim``), the
 statements around the operator (``_PostProcess``), get_loss_dict's two terms (``_ImageLosses``), the fused step's K8 node
-(``_FusedImageLoss``) and splatfacto's MCMC regularisers (``_McmcReg``), with the helpers that prepare their inputs and
+(``_FusedImageLoss``), splatfacto's MCMC regularisers (``_McmcReg``) and the normal loss (``_NormalLoss``), with the helpers that prepare their inputs and
 scratch buffers.  Nothing in here touches the model: ``model.py`` and ``metrics.py`` call in, this module imports the
 library binding only."""
 from __future__ import annotations
@@ -344,3 +344,43 @@ class _McmcReg(torch.autograd.Function):
                     "qed_mcmc_reg")
         return v_opac, v_scales, None, None
 
+
+
+class _NormalLoss(torch.autograd.Function):
+    """The normal loss on the accumulated normal (normals.normal_loss; include/qed_splat.h states it): qed_normal_loss writes
+    the value and the unscaled per-pixel d l / d A in one pass; the backward multiplies that image by the upstream gradient
+    and normal_lambda / max(|V|, 1), both read from device memory.  ``out_f`` (float32 [2], the kernel's {loss, normal_lambda
+    / max(|V|, 1)}) given: the caller applies that factor downstream (normals.accumulated_normals(grad_scale=out_f[1:])
+    multiplies the per-Gaussian rows by it, the compositing backward being linear in its upstream gradient), and the
+    backward returns the unscaled image as it is for backward_fused()'s unit gradient -- no pass over the image at all."""
+
+    @staticmethod
+    def forward(ctx, accum, alpha, target, target_valid, mask, normal_lambda, use_cosine, min_alpha, valid_bits, out_f=None):
+        ctx.set_materialize_grads(False)
+        ctx.deferred = out_f is not None
+        if not accum.is_cuda or accum.dtype != torch.float32:
+            raise L.QedSplatError("the normal loss needs float32 GPU tensors: there is no CPU path in the product")
+        accum = accum.detach().contiguous()
+        dev = accum.device
+        n_pix = accum.numel() // 3
+        ws = torch.empty(L.NORMAL_LOSS_WS_DOUBLES, dtype=torch.float64, device=dev)
+        v_accum = torch.empty_like(accum)
+        parts = torch.empty(4, dtype=torch.float64, device=dev)
+        if out_f is None:
+            out_f = torch.empty(2, dtype=torch.float32, device=dev)
+        L.check(L.load().qed_normal_loss(n_pix, L.ptr(accum), L.ptr(alpha), L.ptr(target), L.ptr(target_valid), valid_bits,
+                                         L.ptr(mask), min_alpha, 1 if use_cosine else 0, normal_lambda, L.ptr(ws),
+                                         L.ptr(v_accum), L.ptr(parts), L.ptr(out_f), _stream()), "qed_normal_loss")
+        ctx.save_for_backward(v_accum, out_f)
+        ctx.mark_non_differentiable(parts)
+        return out_f[0:1].view(()), parts
+
+    @staticmethod
+    def backward(ctx, g, _g_parts):
+        if g is None:
+            return (None,) * 10
+        v_accum, out_f = ctx.saved_tensors
+        if ctx.deferred:
+            unit = g.data_ptr() == _unit_grad(g.device).data_ptr()
+            return (v_accum if unit else v_accum * g.to(torch.float32),) + (None,) * 9
+        return (v_accum * (g.to(torch.float32) * out_f[1]),) + (None,) * 9

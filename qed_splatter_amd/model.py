@@ -132,9 +132,19 @@ class QEDSplatterModelConfig:
     # has n_z < 0), "depth_normal" (the normals of the rendered depth), "normal_valid" (uint8: bit 0 / bit 1 say where each
     # is defined) and "normal_vis" (the uint8 colouring of "normal"); get_image_metrics_and_images then reports their
     # angular errors (normals.py).  Pixels whose accumulation is under normals_min_alpha have no normal.  Training is
-    # unaffected: there is no normal loss
+    # unaffected by this flag
     output_normals: bool = False
     normals_min_alpha: float = 0.5
+    # Normal supervision in training (dn-splatter's normal loss, restated from memory; normals.py, include/qed_splat.h):
+    # normal_lambda * [mean |n^ - g| + (use_normal_cosine_loss ? mean (1 - n^ . g) : 0)] over the pixels where the rendered
+    # normal n^ (accumulation >= normals_min_alpha) and the target g are defined and the loss mask is non-zero.  g = the
+    # normals of the step's ground-truth depth at the render's resolution, or batch["normal"] ([H,W,3] float32 in the
+    # OpenCV camera frame, zero rows = undefined, the render's size).  get_outputs then adds outputs["normal_accum"],
+    # get_loss_dict / fused_loss "normal_loss".  Refused beside an active camera optimiser, in a captured step and by the
+    # data-parallel exchange; such a step takes the eager route (no captured segment)
+    use_normal_loss: bool = False
+    normal_lambda: float = 0.1
+    use_normal_cosine_loss: bool = False
 
     @classmethod
     def synthetic(cls, **kw) -> "QEDSplatterModelConfig":
@@ -224,12 +234,14 @@ class StepContext:
         gradient accumulator through it -- claimed once; a second loss on the same outputs makes the backward fill its own.
 
     And two facts about the forward call itself, which the data-parallel exchanges refuse (parallel.py):
-    ``pose_optimizer`` / ``grid_optimizer``, the camera and bilateral-grid optimisers ``fused_loss`` ran with."""
+    ``pose_optimizer`` / ``grid_optimizer``, the camera and bilateral-grid optimisers ``fused_loss`` ran with, and
+    ``normal_loss``, whether the step carries the normal loss."""
 
-    __slots__ = ("rgb", "handover", "_gt", "ssim", "pose_optimizer", "grid_optimizer")
+    __slots__ = ("rgb", "handover", "_gt", "ssim", "pose_optimizer", "grid_optimizer", "normal_loss")
 
-    def __init__(self, pose_optimizer=None, grid_optimizer=None):
+    def __init__(self, pose_optimizer=None, grid_optimizer=None, normal_loss=False):
         self.rgb = None
+        self.normal_loss = bool(normal_loss)          # the step renders normals for config.use_normal_loss
         self.handover = None
         self._gt = None
         self.ssim = None
@@ -796,7 +808,12 @@ class QEDSplatterModel(nn.Module):
         # what get_metrics_dict / get_loss_dict / backward share about THIS step lives in one object, replaced here: a
         # loader that refills its batch tensors in place without bumping their version counter must not be served last
         # step's conversion, and nothing of last step's outputs may reach this step's loss
-        ctx = attrs["_step"] = StepContext()
+        # config.use_normal_loss: the step also renders the accumulated normal, differentiably (normals.py)
+        want_nloss = bool(self.config.use_normal_loss) and self.training and torch.is_grad_enabled()
+        if want_nloss and self.camera_optimizer is not None and getattr(self.camera_optimizer, "active", True):
+            raise NotImplementedError("use_normal_loss beside an active camera optimiser: a Gaussian's normal depends on the "
+                                      "view rotation, which the normal render does not differentiate")
+        ctx = attrs["_step"] = StepContext(normal_loss=want_nloss)
 
         if self.config.rasterize_mode not in ["antialiased", "classic"]:      # model.py:253-254
             raise ValueError("Unknown rasterize_mode: %s", self.config.rasterize_mode)
@@ -816,6 +833,10 @@ class QEDSplatterModel(nn.Module):
         background = self._get_background_color()
         # config.output_normals: evaluation and rendering only (the records of the projection stay reachable for it)
         want_normals = bool(getattr(self.config, "output_normals", False)) and not self.training
+        quat_sink = None
+        if want_nloss:
+            from .normals import QuatGradSink
+            quat_sink = QuatGradSink()           # (the normals' part of quats.grad, added by the projection backward)
 
         # the camera's launch order (fused_loss: frame_key): the reference's trainer hands the camera index in
         # camera.metadata["cam_idx"]; only on the eager route -- a captured segment is replayed for every camera
@@ -839,13 +860,13 @@ class QEDSplatterModel(nn.Module):
                 _flags=flags, _sh_rest=sh_rest, _sync=not (self.config.async_intersection_count and self.training),
                 _c2w=(c2w, intr) if c2w is not None else None, _post_background=bg, _handover=handover,
                 _means2d_leaf=True,     # xys is only retained and read (below; densify.py): its gradient arrives as a view
-                _capture_slot=capture_slot, _manual=manual, _keep_records=want_normals,
+                _capture_slot=capture_slot, _manual=manual, _keep_records=want_normals or want_nloss, _post_bwd=quat_sink,
                 # (a captured backward pass always writes the compact form; _SegmentFn.backward asks per replay)
                 _lazy_sh=self._lazy_sh_begin if (lazy and manual is None) else None)
 
         seg = None
         if (self.training and self.config.graph_segments and cam_c2w is not None and crop_ids is None
-                and torch.is_grad_enabled() and self.config.async_intersection_count):
+                and torch.is_grad_enabled() and self.config.async_intersection_count and not want_nloss):
             seg = self._outputs_segment(W, H, render_mode, sh_degree_to_use, flags, render_fn, cam_c2w, background)
         if seg is not None:
             rgb, alpha, depth_im = seg.run(cam_c2w[0], cam_c2w[1], background)
@@ -900,7 +921,46 @@ class QEDSplatterModel(nn.Module):
         }
         if want_normals:
             outputs.update(self._normal_outputs(means_crop, quats_crop, scales_crop, viewmat, K, info, render, alpha))
+        if want_nloss:
+            from .normals import accumulated_normals
+            accum = accumulated_normals(means_crop, quats_crop, scales_crop, viewmat, info, render, log_scales=True,
+                                        quat_sink=quat_sink).squeeze(0)      # (a view: its backward is no pass over the image)
+            info.pop("_splats", None)            # (as in _normal_outputs: not kept alive by self.info)
+            info.pop("_isect_offsets_full", None)
+            accum._qed_intrinsics = self._host_intrinsics(cam_c2w, K)      # (get_loss_dict: the depth target's normals)
+            outputs["normal_accum"] = accum
         return outputs
+
+    def _host_intrinsics(self, cam_c2w, K) -> Tuple[float, float, float, float]:
+        """(fx, fy, cx, cy) of the step's (rescaled) camera as host floats, which qed_depth_normals takes as arguments.  One
+        small read-back, kept on the camera's cached intrinsics tensor: at full resolution a camera is read once."""
+        src = cam_c2w[1] if cam_c2w is not None else None
+        if src is None:
+            k = K[0].detach().cpu()
+            return float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+        host = getattr(src, "_qed_host", None)
+        if host is None:
+            host = src._qed_host = tuple(float(v) for v in src[0].detach().cpu())
+        return host
+
+    def _normal_target(self, batch, gt_depth: Tensor, H: int, W: int, intr):
+        """(target [H,W,3], valid uint8 [H,W], valid bits) of the normal loss: batch["normal"] when the batch carries one
+        (refused unless it has the render's size), else the normals of the step's ground-truth depth."""
+        from .normals import batch_normal_target, depth_normal_target
+        given = None
+        try:
+            given = batch["normal"] if "normal" in batch else None
+        except (KeyError, TypeError):
+            given = None
+        if given is not None:
+            return batch_normal_target(given, H, W, self.device) + (0xff,)
+        return depth_normal_target(gt_depth.reshape(H, W), *intr) + (L.NV_DEPTH_NORMAL,)
+
+    def _normal_loss_term(self, accum: Tensor, alpha: Tensor, target, mask, scale_out=None) -> Tensor:
+        from .normals import normal_loss
+        cfg = self.config
+        return normal_loss(accum, alpha, target[0], target[1], mask, float(cfg.normal_lambda),
+                           bool(cfg.use_normal_cosine_loss), float(cfg.normals_min_alpha), target[2], scale_out=scale_out)
 
     @torch.no_grad()
     def _normal_outputs(self, means, quats, scales, viewmat, K, info, render, alpha) -> Dict[str, Tensor]:
@@ -1000,6 +1060,10 @@ class QEDSplatterModel(nn.Module):
         if self.training and pose_losses is not None:                        # the parent's camera_opt_regularizer
             pose_losses(out)
         out["depth_loss"] = depth
+        accum = outputs.get("normal_accum") if (cfg.use_normal_loss and self.training) else None
+        if accum is not None:
+            target = self._normal_target(batch, depth_batch, H, W, accum._qed_intrinsics)
+            out["normal_loss"] = self._normal_loss_term(accum, outputs["accumulation"], target, mask)
         return out
 
     # ---- get_metrics_dict (model.py:120-197) ----
@@ -1205,7 +1269,14 @@ class QEDSplatterModel(nn.Module):
         pose_opt = camera_optimizer if (camera_optimizer is not None and camera_optimizer.active and self.training) else None
         # (conversions of the batch are shared within a step, never across steps; parallel.py refuses a data-parallel step
         # behind either optimiser)
-        attrs["_step"] = StepContext(pose_opt, grid_opt)
+        want_nloss = bool(cfg.use_normal_loss) and self.training
+        if want_nloss and pose_opt is not None:
+            raise NotImplementedError("use_normal_loss beside an active camera optimiser: a Gaussian's normal depends on the "
+                                      "view rotation, which the normal render does not differentiate")
+        if want_nloss and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("use_normal_loss inside a captured step (graph.py, segments.py): the normal pass hands "
+                                      "its rows from one autograd node to another on the host, per step")
+        attrs["_step"] = StepContext(pose_opt, grid_opt, want_nloss)
         grid_idx = None
         if grid_opt is not None:
             grid_idx = cam_idx
@@ -1251,13 +1322,22 @@ class QEDSplatterModel(nn.Module):
                 post_bwd = _mcmc_reg_grad_adder(self.opacities, self.scales, lo, ls)
         # the launch-order buffer of this camera (see ``frame_key``): [C T + 1] int32, written by every training frame's
         # loss launch, read by the next frame's compositing forward -- persistent, so that a captured step replays against it
+        # config.use_normal_loss: the target first (a batch["normal"] of another size is refused before any launch of the
+        # step), then the hook through which the projection backward adds the normals' part of the quaternion gradient
+        normal = None
+        if want_nloss:
+            from .normals import QuatGradSink
+            target = self._normal_target(batch, gt_depth, H, W, self._host_intrinsics(cam_c2w, K))
+            if torch.is_grad_enabled():
+                post_bwd = QuatGradSink(post_bwd)
+            normal = (target, post_bwd if torch.is_grad_enabled() else None, viewmat)
         frame_order = self._frame_order_slot(frame_key, H, W) if frame_key is not None else None
         # (the fused loss launch offers the compositing backward its zeroed accumulator and launch order through this)
         handover = Handover(self.num_points, frame_order)
         if grid_opt is not None:
             return self._fused_loss_with_grid(grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags,
                                               sync, handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask,
-                                              lo, ls, mcmc_vals)
+                                              lo, ls, mcmc_vals, normal)
         # ``optimizer`` (a FlatAdam stepped with device_state=True, fused_sh=True right after this step's backward): the
         # loss pass's fold launch advances its device step state, so that the optimiser needs no launch of its own for it
         tick = None
@@ -1268,7 +1348,8 @@ class QEDSplatterModel(nn.Module):
                 means=self.means, quats=self.quats, scales=self.scales, opacities=self.opacities, colors=colors,
                 viewmats=viewmat, Ks=K, width=W, height=H, render_mode="RGB+D", sh_degree=deg, _flags=flags,
                 _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd,
-                _pose_grad=pose_opt.pose_grad if (pose_opt is not None and torch.is_grad_enabled()) else None)
+                _pose_grad=pose_opt.pose_grad if (pose_opt is not None and torch.is_grad_enabled()) else None,
+                _keep_records=normal is not None)
             attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
             # (the compositing node keeps the forward pass's per-tile costs: the loss launch sorts them for its backward)
             tile_cost = getattr(render.grad_fn, "tile_cost", None) if torch.is_grad_enabled() else None
@@ -1293,13 +1374,32 @@ class QEDSplatterModel(nn.Module):
             out = {"loss": total + mcmc_vals[2], "main_loss": parts[0]}
             self._put_mcmc_regs(out, lo, ls, mcmc_vals)
             out["depth_loss"] = parts[1]
+        if normal is not None:
+            self._add_fused_normal_loss(out, normal, info, render, alpha, mask)
         if pose_reg is not None:
             out["loss"] = out["loss"] + pose_reg
             out["camera_opt_regularizer"] = pose_reg
         return out
 
+    def _add_fused_normal_loss(self, out: Dict[str, Tensor], normal, info, render: Tensor, alpha: Tensor, mask) -> None:
+        """config.use_normal_loss on the fused route: the accumulated normal behind this step's colour pass and the loss on
+        it, added to ``loss`` and returned (detached) as ``normal_loss``."""
+        from .normals import accumulated_normals
+        target, sink, viewmat = normal
+        # the accumulated normal is this call's own, so the loss's factor normal_lambda / max(|V|, 1) goes to the
+        # per-Gaussian rows as a device scalar (qed_normal_rows_merge, qed_gaussian_normals_bwd) instead of the image
+        scale = torch.empty(2, dtype=torch.float32, device=self.device) if torch.is_grad_enabled() else None
+        accum = accumulated_normals(self.means, self.quats, self.scales, viewmat, info, render, log_scales=True,
+                                    quat_sink=sink, grad_scale=scale[1:] if scale is not None else None)
+        info.pop("_splats", None)
+        info.pop("_isect_offsets_full", None)
+        term = self._normal_loss_term(accum.squeeze(0), alpha[0], target, mask, scale_out=scale)
+        out["loss"] = out["loss"] + term
+        out["normal_loss"] = term.detach()
+
     def _fused_loss_with_grid(self, grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags, sync,
-                              handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask, lo, ls, mcmc_vals):
+                              handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask, lo, ls, mcmc_vals,
+                              normal=None):
         """fused_loss behind ``grid_optimizer``: the loss is taken on the CORRECTED colour, so the gridless route's one
         launch from ``render`` to its gradient does not apply.  The launches are those of get_outputs -> get_loss_dict:
         the compositing forward with its post-processing epilogue (clamped colour, fixed-up depth), the slice, the SSIM
@@ -1314,7 +1414,7 @@ class QEDSplatterModel(nn.Module):
             means=self.means, quats=self.quats, scales=self.scales, opacities=self.opacities, colors=colors,
             viewmats=viewmat, Ks=K, width=W, height=H, render_mode="RGB+D", sh_degree=deg, _flags=flags,
             _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd, _post_background=bg,
-            _pose_grad=pose_opt.pose_grad if (pose_opt is not None and grad) else None)
+            _pose_grad=pose_opt.pose_grad if (pose_opt is not None and grad) else None, _keep_records=normal is not None)
         attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
         rgb, tv = grid_opt.begin_fused(info.pop("post_rgb"), grid_idx, H, W)
         depth = info.pop("post_depth")
@@ -1327,6 +1427,8 @@ class QEDSplatterModel(nn.Module):
             out["loss"] = total + mcmc_vals[2]
             self._put_mcmc_regs(out, lo, ls, mcmc_vals)
         out["depth_loss"] = depth_loss.detach()
+        if normal is not None:                   # (the term does not touch colour: it is taken on the accumulated normal)
+            self._add_fused_normal_loss(out, normal, info, render, alpha, mask)
         if pose_reg is not None:
             out["loss"] = out["loss"] + pose_reg
             out["camera_opt_regularizer"] = pose_reg

@@ -1,5 +1,6 @@
-"""Surface normals at evaluation / rendering time: a Gaussian's normal, the rendered normal map, the normals of a depth map
-and the angular error between two normal images (csrc/normals.hip; include/qed_splat.h states every definition).
+"""Surface normals: a Gaussian's normal, the rendered normal map, the normals of a depth map, the angular error between two
+normal images (csrc/normals.hip) and -- in training -- the normal loss with its backward pass (csrc/normal_loss.hip);
+include/qed_splat.h states every definition.
 
     python -m qed_splatter_amd.normals --depth FILE --fx FX [--fy FY --cx CX --cy CY --depth-unit U] --out PNG
 
@@ -14,8 +15,20 @@ vectors, and the second is well conditioned at 0 and pi, where ``acos`` of a flo
 
 The normal render (``render_normals``) makes no second projection and no second binning: ``qed_gaussian_normals`` writes a
 second set of the projection's records with the normal in the colour slots, and ONE more call of the forward compositing
-kernel over the colour pass's own tile lists accumulates A = Sum_i alpha_i T_i n_i.  Nothing here is differentiable: there
-is no normal loss in training.
+kernel over the colour pass's own tile lists accumulates A = Sum_i alpha_i T_i n_i.
+
+Training (config.use_normal_loss; dn-splatter's normal loss, again RESTATED FROM MEMORY): ``accumulated_normals`` is that
+accumulation as an autograd node behind the colour pass, ``normal_loss`` the loss
+``normal_lambda * [mean_V |n^ - g| + (cosine ? mean_V (1 - n^ . g) : 0)]`` on n^ = A / |A| against a target ``g`` -- the
+normals of the step's ground-truth depth (``depth_normal_target``) unless the batch carries ``"normal"``.  Backwards, a second
+call of the unchanged compositing backward on the normal records fills a second accumulator; its 2-D mean, conic and opacity
+slots are merged into the colour pass's rows (so the projection backward runs once, on the sum), its colour slots hold
+d L / d n_i, which ``qed_gaussian_normals_bwd`` takes to the raw quaternions.  Stated deviations: the axis choice and the
+facing sign carry no gradient; a normal's dependence on the VIEW rotation is not differentiated (a camera optimiser beside
+the loss is refused); the normal pass does not add to ``absgrad`` (gsplat's statistic is that of the total loss per pixel,
+which two passes cannot form), so the densifier sees the colour and depth loss only.  Out of scope: a total-variation term on
+the normals, a rendered-normal to rendered-depth-normal consistency term (it needs a backward pass through the depth stencil),
+ground-truth normal files in the dataparser, and meshing.
 """
 from __future__ import annotations
 
@@ -91,6 +104,175 @@ def accumulate_normals(records: Tensor, info: Dict, C: int, N: int) -> Tensor:
                                        L.ptr(accum), L.ptr(alpha), None, L.ptr(last_ids), None, None, None,
                                        L.composite_launch_flags(), _stream()), "qed_composite_fwd")
     return accum
+
+
+# ---- training: the accumulation as an autograd node, the loss ------------------------------------------------------------
+class NormalRows:
+    """What one normal pass's backward leaves for the colour pass's compositing backward (rasterization._Composite): its
+    accumulator ``rows`` [C N, 16] and the device scalar (or None = 1) they are multiplied by when merged."""
+
+    __slots__ = ("rows", "scale")
+
+    def __init__(self, rows: Tensor, scale: Optional[Tensor]):
+        self.rows, self.scale = rows, scale
+
+
+class QuatGradSink:
+    """A ``_post_bwd`` hook of rasterization() that takes the quaternions' gradient too: ``accumulated_normals(...,
+    quat_sink=sink)`` leaves its d L / d n_i here instead of returning a gradient of its own for ``quats``, and the projection
+    backward calls the sink right after it has written the flat gradient -- the normal part is added IN PLACE, so the six
+    ``.grad`` tensors stay views of one allocation.  ``inner``: a hook of the older two-argument form to call first."""
+
+    wants_quats = True
+
+    def __init__(self, inner=None):
+        self.inner, self.jobs = inner, []
+
+    def __call__(self, v_scales: Tensor, v_opacities: Tensor, v_quats: Tensor) -> None:
+        if self.inner is not None:
+            self.inner(v_scales, v_opacities)
+        jobs, self.jobs = self.jobs, []
+        for job in jobs:
+            _quat_grad(*job, add=True, out=v_quats)
+
+
+def _quat_grad(means, quats, scales, viewmats, radii, rows, scale, log_scales, add: bool, out: Optional[Tensor] = None) -> Tensor:
+    """qed_gaussian_normals_bwd: d L / d (raw quaternions) [N,4] from the normal rows, written to or added to ``out``."""
+    N, C = means.shape[0], viewmats.shape[0]
+    if out is None:
+        out = torch.empty(N, 4, dtype=torch.float32, device=means.device)
+    if not out.is_contiguous() or out.dtype != torch.float32 or out.numel() != 4 * N:
+        raise ValueError("v_quats: a contiguous float32 [N,4] tensor")
+    L.check(L.load().qed_gaussian_normals_bwd(N, C, L.ptr(means), L.ptr(quats), L.ptr(scales), L.ptr(viewmats), L.ptr(radii),
+                                              L.ptr(rows), L.ptr(scale), L.F_LOG_SCALES if log_scales else 0, 1 if add else 0,
+                                              L.ptr(out), _stream()), "qed_gaussian_normals_bwd")
+    return out
+
+
+class _AccumulatedNormals(torch.autograd.Function):
+    """A = Sum_i alpha_i T_i n_i behind a colour pass.  ``render`` is an input only for its EDGE: the colour pass's
+    compositing backward then runs after this node's backward, finds the rows left on it and merges them into its own."""
+
+    @staticmethod
+    def forward(ctx, render, quats, means, scales, viewmats, info, node, log_scales, quat_sink, grad_scale):
+        ctx.set_materialize_grads(False)
+        C, N = viewmats.shape[0], means.shape[0]
+        _, records = gaussian_normals(means, quats, scales, viewmats, "camera", log_scales, splats=info["_splats"])
+        accum = accumulate_normals(records, info, C, N)
+        ctx.save_for_backward(records, _f32(means, "means"), _f32(quats, "quats"), _f32(scales, "scales"),
+                              _f32(viewmats, "viewmats"), info["radii"], grad_scale)
+        ctx.node, ctx.log_scales, ctx.quat_sink = node, bool(log_scales), quat_sink
+        return accum
+
+    @staticmethod
+    def backward(ctx, v_accum):
+        if v_accum is None:
+            return (None,) * 10
+        records, means, quats, scales, viewmats, radii, grad_scale = ctx.saved_tensors
+        node = ctx.node
+        # the colour pass's own lists and geometry (they depend on nothing the normals change)
+        _splats, flatten_ids, offsets, alpha, last_ids, _bg, _render, _pbg, t_final = node.saved_tensors
+        C, N, W, H, tw, th = node.meta[:6]
+        dev = records.device
+        v_accum = _f32(v_accum, "v_accum")
+        if v_accum.shape != (C, H, W, 3):
+            raise ValueError(f"the gradient of the accumulated normal must be [{C},{H},{W},3]")
+        rows = torch.zeros(C * N, L.VSPLAT_FLOATS, dtype=torch.float32, device=dev)
+        v_alpha = torch.zeros(C, H, W, 1, dtype=torch.float32, device=dev)
+        tile_cost = getattr(node, "tile_cost", None)
+        order_ws = torch.empty(C * tw * th + 1, dtype=torch.int32, device=dev) if tile_cost is not None else None
+        L.check(L.load().qed_composite_bwd(C, N, L.ptr(records), L.ptr(flatten_ids), L.ptr(offsets), W, H, tw, th, 3, None,
+                                           L.ptr(alpha), L.ptr(t_final), L.ptr(last_ids), L.ptr(v_accum), L.ptr(v_alpha),
+                                           L.ptr(rows), L.ptr(tile_cost), L.ptr(order_ws), None,
+                                           L.composite_launch_flags(), _stream()), "qed_composite_bwd")
+        node.__dict__.setdefault("normal_pending", []).append(NormalRows(rows, grad_scale))
+        job = (means, quats, scales, viewmats, radii, rows, grad_scale, ctx.log_scales)
+        v_quats = None
+        if ctx.quat_sink is not None:
+            ctx.quat_sink.jobs.append(job)
+        elif ctx.needs_input_grad[1]:
+            v_quats = _quat_grad(*job, add=False)
+        return (None, v_quats) + (None,) * 8
+
+
+def accumulated_normals(means: Tensor, quats: Tensor, scales: Tensor, viewmats: Tensor, info: Dict, render: Tensor,
+                        log_scales: bool = True, quat_sink: Optional[QuatGradSink] = None,
+                        grad_scale: Optional[Tensor] = None) -> Tensor:
+    """A [C,H,W,3] = Sum_i alpha_i T_i n_i of the colour pass that returned ``render`` and ``info`` (rasterization(...,
+    _keep_records=True)), DIFFERENTIABLE for any upstream gradient on A: through every alpha_i T_i to means, scales, quats
+    and opacities (the colour pass's compositing backward merges this pass's rows into its own, so ``info["means2d"].grad``
+    carries the sum and ``.absgrad`` the colour pass's only), and through every n_i to the raw quaternions -- returned to
+    autograd as ``quats``' gradient, or with ``quat_sink`` (handed to the same rasterization call as ``_post_bwd``) added to
+    the projection backward's in place.  ``grad_scale``: a device float [1] read at backward time that multiplies the
+    whole gradient of this node.  Under ``no_grad`` (or when ``render`` has no graph) it is ``accumulate_normals``."""
+    C, N = viewmats.shape[0], means.shape[0]
+    if "_splats" not in info:
+        raise ValueError("accumulated_normals needs the records of the colour pass: rasterization(..., _keep_records=True)")
+    node = render.grad_fn if (torch.is_grad_enabled() and render.requires_grad) else None
+    if node is None:
+        with torch.no_grad():
+            _, records = gaussian_normals(means, quats, scales, viewmats, "camera", log_scales, splats=info["_splats"])
+            return accumulate_normals(records, info, C, N)
+    if not hasattr(node, "meta") or not hasattr(node, "tile_cost"):
+        raise ValueError("accumulated_normals: `render` must be the image rasterization() returned (its first result)")
+    if viewmats.requires_grad:
+        raise NotImplementedError("the normal render is not differentiated with respect to the view matrices (a normal's "
+                                  "dependence on the view rotation): detach them, or switch the camera optimiser off")
+    if grad_scale is not None:
+        grad_scale = _f32(grad_scale, "grad_scale").reshape(1)
+    return _AccumulatedNormals.apply(render, quats, means, scales, viewmats, info, node, log_scales, quat_sink, grad_scale)
+
+
+def depth_normal_target(depth: Tensor, fx: float, fy: float, cx: float, cy: float) -> Tuple[Tensor, Tensor]:
+    """The default target of the normal loss: ``(normals [H,W,3], valid uint8 [H,W])`` of a sensor depth map [H,W(,1)] by
+    qed_depth_normals; the plane's bit is ``_lib.NV_DEPTH_NORMAL``."""
+    if depth.dim() == 3 and depth.shape[2] == 1:
+        depth = depth[..., 0]
+    H, W = int(depth.shape[0]), int(depth.shape[1])
+    depth, stride = _strided_plane(depth, H, W)
+    normals = torch.empty(H, W, 3, dtype=torch.float32, device=depth.device)
+    valid = torch.empty(H, W, dtype=torch.uint8, device=depth.device)
+    L.check(L.load().qed_depth_normals(H, W, L.ptr(depth), stride, fx, fy, cx, cy, L.ptr(normals), L.ptr(valid), None,
+                                       _stream()), "qed_depth_normals")
+    return normals, valid
+
+
+def batch_normal_target(normal: Tensor, H: int, W: int, device) -> Tuple[Tensor, Tensor]:
+    """``batch["normal"]`` [H,W,3] float32 (unit normals in the camera frame, zero rows = undefined) as a target: refused
+    unless it has the render's size -- there is no resizing."""
+    if not torch.is_tensor(normal) or normal.dtype != torch.float32 or tuple(normal.shape) != (H, W, 3):
+        raise L.QedSplatError(f"batch['normal']: expected float32 [{H},{W},3] (the render's size; it is not resized), got "
+                              f"{getattr(normal, 'dtype', type(normal))} {tuple(getattr(normal, 'shape', ()))}")
+    normal = normal.to(device).contiguous()
+    return normal, (normal != 0).any(dim=-1).to(torch.uint8)
+
+
+def normal_loss(accum: Tensor, alpha: Tensor, target: Tensor, target_valid: Tensor, mask: Optional[Tensor] = None,
+                normal_lambda: float = 0.1, use_cosine: bool = False, min_alpha: float = 0.5, valid_bits: int = 0xff,
+                return_parts: bool = False, scale_out: Optional[Tensor] = None):
+    """``normal_lambda * [mean over V and the channels of |n^ - g| + (use_cosine ? mean over V of (1 - n^ . g) : 0)]`` as a
+    0-dim float32 tensor, differentiable in ``accum`` [H,W,3] (the accumulated normal; n^ = A / |A| where ``alpha`` >=
+    ``min_alpha`` and |A| > 1e-8).  ``target`` [H,W,3] with ``target_valid`` (bool, or uint8 tested against ``valid_bits``),
+    ``mask`` (bool / float, optional): V = defined, valid and unmasked pixels; an empty V gives 0 with zero gradients.
+    ``return_parts``: also the float64 device tensor {loss, L1 mean, cosine mean, |V|}.  Nothing is read back.
+    ``scale_out`` (float32 [2] on the device; for a caller that owns ``accum``): receives {loss, normal_lambda / max(|V|, 1)},
+    and the gradient handed to ``accum`` is then NOT multiplied by the second -- pass ``scale_out[1:]`` as ``grad_scale`` to
+    the ``accumulated_normals`` call that made ``accum``, and let nothing else consume that tensor."""
+    from .losses import _NormalLoss
+    if accum.shape[-1] != 3 or target.shape != accum.shape:
+        raise ValueError("accum, target: two [...,3] images of one shape")
+    n_pix = accum.numel() // 3
+    dev = accum.device
+    tv = _valid_plane(target_valid, n_pix, "target_valid")
+    if mask is not None:
+        mask = mask.to(device=dev, dtype=torch.float32).contiguous()
+        if mask.numel() != n_pix:
+            raise ValueError(f"mask: {n_pix} values")
+    if alpha.numel() != n_pix:
+        raise ValueError("alpha [H,W]")
+    loss, parts = _NormalLoss.apply(accum, _f32(alpha, "alpha"), _f32(target, "target"), tv, mask, float(normal_lambda),
+                                    bool(use_cosine), float(min_alpha), int(valid_bits), scale_out)
+    return (loss, parts) if return_parts else loss
 
 
 def normal_maps(accum: Tensor, alpha: Tensor, depth: Tensor, fx: float, fy: float, cx: float, cy: float,

@@ -100,6 +100,9 @@ def _refuse_camera_optimizer(model, who: str) -> None:
     if ctx is not None and ctx.grid_optimizer is not None:
         raise NotImplementedError(f"{who}: the last fused_loss ran with a bilateral-grid optimiser; every rank would step "
                                   "the grids from its own frame, and neither they nor their Adam state are exchanged")
+    if ctx is not None and getattr(ctx, "normal_loss", False):
+        raise NotImplementedError(f"{who}: the last step carried the normal loss (config.use_normal_loss); the exchanges "
+                                  "know the colour pass's gradient records only, not the normal pass's")
 
 
 def _checked_grad(model, who: str, compact: bool):

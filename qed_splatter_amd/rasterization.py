@@ -273,7 +273,12 @@ class _ProjectSH(torch.autograd.Function):
             _stream()), "qed_project_bwd")
         post = getattr(ctx, "post_bwd", None)
         if post is not None:
-            post(v_scales, v_opacities)         # terms of the loss that read the parameters directly (model: MCMC)
+            # terms of the loss that read the parameters directly (model: MCMC); a hook that says ``wants_quats`` also takes
+            # the quaternions' gradient (normals.QuatGradSink: the normal loss's n_i part)
+            if getattr(post, "wants_quats", False):
+                post(v_scales, v_opacities, v_quats)
+            else:
+                post(v_scales, v_opacities)
         v_opacities = v_opacities.view(ctx.opac_shape)
         return (v_means, v_quats, v_scales, v_opacities, v_sh0, v_shN, v_viewmats, None) + (None,) * 15
 
@@ -378,6 +383,11 @@ class _Composite(torch.autograd.Function):
         splats, flatten_ids, offsets, alpha, last_ids, bg, render, pbg, t_final = ctx.saved_tensors
         C, N, width, height, tile_w, tile_h, channels, absgrad = ctx.meta
         dev = splats.device
+        # normals.accumulated_normals: the rows of a normal pass over this node's lists, left here by its backward (which runs
+        # first: it holds an edge to `render`), to be added to this pass's rows below.  With no gradient of its own this pass
+        # launches nothing but the merge
+        pending = ctx.__dict__.pop("normal_pending", None)
+        only_normals = bool(pending) and v_render is None and v_alpha is None and v_rgb is None and v_depth is None
         post = None
         if v_rgb is not None or v_depth is not None:
             v_rgb = _f32c(v_rgb, "v_rgb") if v_rgb is not None else None
@@ -396,7 +406,7 @@ class _Composite(torch.autograd.Function):
                         "qed_post_process_bwd")
                 v_render = vr2 if v_render is None else v_render + vr2
                 v_alpha = va2 if v_alpha is None else v_alpha + va2
-        if post is None:
+        if post is None and not only_normals:
             v_render = _f32c(v_render, "v_render") if v_render is not None else torch.zeros(
                 C, height, width, channels, dtype=torch.float32, device=dev)
             v_alpha = _f32c(v_alpha, "v_alpha") if v_alpha is not None else torch.zeros(
@@ -423,11 +433,15 @@ class _Composite(torch.autograd.Function):
                 order_ws = torch.empty(n_tiles + 1, dtype=torch.int32, device=dev)
         else:
             order_ws = None
-        L.check(lib.qed_composite_bwd(C, N, L.ptr(splats), L.ptr(flatten_ids), L.ptr(offsets), width, height, tile_w,
-                                      tile_h, channels, L.ptr(bg), L.ptr(alpha), L.ptr(t_final), L.ptr(last_ids),
-                                      L.ptr(v_render) if post is None else None, L.ptr(v_alpha) if post is None else None,
-                                      L.ptr(vsplat), L.ptr(tile_cost), L.ptr(order_ws), C_byref(post), flags, _stream()),
-                "qed_composite_bwd")
+        if not only_normals:
+            L.check(lib.qed_composite_bwd(C, N, L.ptr(splats), L.ptr(flatten_ids), L.ptr(offsets), width, height, tile_w,
+                                          tile_h, channels, L.ptr(bg), L.ptr(alpha), L.ptr(t_final), L.ptr(last_ids),
+                                          L.ptr(v_render) if post is None else None, L.ptr(v_alpha) if post is None else None,
+                                          L.ptr(vsplat), L.ptr(tile_cost), L.ptr(order_ws), C_byref(post), flags, _stream()),
+                    "qed_composite_bwd")
+        for job in pending or ():
+            L.check(lib.qed_normal_rows_merge(C * N, L.ptr(job.rows), L.ptr(job.scale), L.ptr(vsplat), _stream()),
+                    "qed_normal_rows_merge")
         ctx.order_ws = order_ws                  # (tests read the launch order: render.grad_fn.order_ws)
         v3 = vsplat.view(C, N, R)
         v_means2d = v3[..., 0:2]
@@ -477,7 +491,9 @@ def rasterization(
     (RGB+D) are their results, differentiable like ``render`` / ``alpha``.  ``_means2d_leaf``: ``info["means2d"]`` is a
     leaf that receives ``.grad`` / ``.absgrad`` as views (see below) instead of gsplat's non-leaf.  ``_post_bwd(v_scales,
     v_opacities)``: called by the projection backward right after it has written the parameter gradients, to add terms of
-    its own to them in place (the views alias the flat gradient).  ``_pose_grad`` [C,4,4]: a persistent, zeroed buffer the
+    its own to them in place (the views alias the flat gradient); a hook with the attribute ``wants_quats`` is called with
+    ``(v_scales, v_opacities, v_quats)`` (normals.QuatGradSink: the normal loss's part of the quaternions' gradient).
+    ``_pose_grad`` [C,4,4]: a persistent, zeroed buffer the
     projection backward adds the view matrices' gradient to (qed_project_bwd's v_viewmats) although ``viewmats`` does not
     require grad: the camera optimiser of the fused route (camera_optimizer.py), whose qed_pose_step reads and zeroes it.
     ``_keep_records``: ``info["_splats"]`` (the projection's packed records [C*N,12]) and ``info["_isect_offsets_full"]`` (the

@@ -343,6 +343,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--output-normals", action="store_true", default=argparse.SUPPRESS,
                     help="after training: render normal maps (normals.py) in the final \"eval_images\" evaluation, which then "
                          "reports their angular errors, and write a normal/ plane with --render-eval; training is unaffected")
+    ap.add_argument("--normal-loss", action="store_true", default=argparse.SUPPRESS,
+                    help="supervise the rendered normals with the normals of the sensor depth (config.use_normal_loss; "
+                         "normals.py); not with --camera-optimizer")
+    ap.add_argument("--normal-lambda", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="the normal loss's weight (default 0.1)")
+    ap.add_argument("--normal-cosine-loss", action="store_true", default=argparse.SUPPRESS,
+                    help="add the mean of 1 - n . g to the normal loss's L1 term")
     return ap
 
 
@@ -365,7 +372,10 @@ def main(argv=None) -> Dict:
     config = QEDSplatterModelConfig(num_downscales=a.num_downscales, resolution_schedule=a.resolution_schedule,
                                     background_color=a.background_color, sh_degree=a.sh_degree,
                                     use_bilateral_grid=a.use_bilateral_grid, grid_shape=tuple(a.grid_shape),
-                                    color_corrected_metrics=color_corrected)
+                                    color_corrected_metrics=color_corrected,
+                                    use_normal_loss=bool(getattr(a, "normal_loss", False)),
+                                    normal_lambda=float(getattr(a, "normal_lambda", QEDSplatterModelConfig.normal_lambda)),
+                                    use_normal_cosine_loss=bool(getattr(a, "normal_cosine_loss", False)))
     model = build_model(config, dm, a.init_from_ply, a.seed)
     print(f"seeded {model.num_points} Gaussians")
     trainer = Trainer(model, dm, seed=a.seed,
@@ -400,6 +410,8 @@ def main(argv=None) -> Dict:
         result["camera_opt"] = trainer.camera_opt_metrics()
     if trainer.grid_optimizer is not None:
         result["tv_loss"] = float(losses["tv_loss"]) if losses is not None else None
+    if config.use_normal_loss:
+        result["normal_loss"] = float(losses["normal_loss"]) if losses is not None else None
     if output_normals:
         trainer.model.config.output_normals = True      # (from here on: the final evaluation and --render-eval only)
     if color_corrected or output_normals:
