@@ -573,6 +573,22 @@ int qed_colorize_finalize(int32_t N, const double* color_sum, const int32_t* col
 int64_t qed_voxel_workspace_bytes(int64_t n);
 int qed_voxel_down_sample(int32_t n, const float* points, float voxel_size, float* out_points, int32_t* n_out,
                           void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
+/* The same down-sampling carrying n_attrs (1 to QED_VOXEL_MAX_ATTRS) float attribute columns and a weight per point:
+ * points[n,3], attrs[n,n_attrs], weights[n] or NULL (every weight 1).  Per occupied voxel, with the sums over its members i:
+ *   out_points = Sum w_i p_i / Sum w_i,  out_attrs = Sum w_i a_i / Sum w_i,  out_weights = Sum w_i,
+ * products and sums in float64, each result rounded to fp32 once.  Voxel membership, the ascending key order, the fixed
+ * combination order and the status words are qed_voxel_down_sample's; with weights == NULL out_points equals its
+ * out_points bit for bit and out_weights holds the member counts.  A point with a non-finite coordinate, attribute or
+ * weight, or with a weight <= 0, is dropped and counted in status[1].  No floating-point atomics: the same input gives
+ * the same bits.  The mean of a voxel's members lies in that voxel, so with ONE voxel size the weighted merge of clouds
+ * that were down-sampled already equals down-sampling their concatenation once, up to rounding.
+ * Refused on the host: as qed_voxel_down_sample, and n_attrs outside 1 .. QED_VOXEL_MAX_ATTRS; workspace:
+ * qed_voxel_attr_workspace_bytes(n, n_attrs) (8-byte aligned). */
+#define QED_VOXEL_MAX_ATTRS 8
+int64_t qed_voxel_attr_workspace_bytes(int64_t n, int32_t n_attrs);
+int qed_voxel_down_sample_attr(int32_t n, const float* points, int32_t n_attrs, const float* attrs, const float* weights,
+                               float voxel_size, float* out_points, float* out_attrs, float* out_weights, int32_t* n_out,
+                               void* workspace, int64_t workspace_bytes, int32_t* status, void* stream);
 
 /* ---- exact nearest neighbours between two point clouds, and PDMetrics' reductions (metrics.py:9-63) -------------
  * For every query point: the distance to, and the row of, the nearest point of the target cloud (what cKDTree.query
@@ -1047,6 +1063,44 @@ int qed_gaussian_normals_bwd(int32_t N, int32_t C, const float* means, const flo
                              const float* viewmats, const int32_t* radii, const float* normal_rows, const float* scale,
                              uint32_t flags, int32_t add, float* v_quats, void* stream);
 int qed_normal_rows_merge(int64_t total, const float* normal_rows, const float* scale, float* rows, void* stream);
+
+/* ---- oriented surface samples of one rendered view (csrc/surface.hip) -------------------------------------------------------
+ * The planes get_outputs returns in evaluation mode with output_normals, back-projected into a compact list of world points
+ * with normals and colours; no intermediate image.  The filters are THIS PROJECT'S definitions, in the spirit of
+ * DN-Splatter's back-projection, not checked against it and not in the reference.
+ * rgb[H,W,3]; depth = the ACCUMULATED depth D, read at depth[p * depth_stride] (as qed_normal_maps); alpha[H,W];
+ * normal[H,W,3] and depth_normal[H,W,3] in the OpenCV camera frame; valid[H,W] u8 with the QED_NV_* bits; mask[H,W] u8 (may
+ * be NULL); viewmat[4,4]: the OpenCV world-to-camera matrix [R | t], row-major, on the DEVICE.
+ * For every stride-th pixel (x, y) in x and y, IN THIS ORDER (the order is the contract):
+ *   1. alpha >= min_alpha and (mask == NULL or mask != 0), else the pixel is dropped;
+ *   2. z = D / alpha must be finite with depth_min <= z <= depth_max;
+ *   3. the chosen normal n -- `normal` (QED_SURFACE_NORMAL_RENDERED) or `depth_normal` (QED_SURFACE_NORMAL_DEPTH) -- must
+ *      carry its bit in `valid`;
+ *   4. agreement filter, on where cos_max_normal_angle > -1: where BOTH bits are set, dot(normal, depth_normal) >=
+ *      cos_max_normal_angle; a pixel with only one valid normal passes;
+ *   5. P = ((x + .5 - cx) z / fx, (y + .5 - cy) z / fy, z): the renderer's pixel centres (qed_normal_maps' convention, NOT
+ *      Open3D's integer pixels of qed_backproject_depth);
+ *   6. grazing filter, on where min_view_cos > 0: -(n_x P_x / |P| + n_y P_y / |P| + n_z P_z / |P|) >= min_view_cos;
+ *   7. world point = R^T (P - t), world normal = R^T n (not renormalised).
+ * All of it in double from the float32 inputs (the thresholds are float32 values, compared in double), rounded to float32
+ * once.  points / normals / colors[capacity,3] receive the kept pixels in row-major pixel order (colors: rgb's values),
+ * n_out[1] (device) their number.  More than `capacity`: status[0] = the number needed, n_out = 0, nothing is written.
+ * Deterministic (count / scan / write, no atomic counter): two calls give the same bits.  status[QED_STATUS_WORDS] is
+ * zeroed by the call.  workspace: qed_surface_workspace_ints(height, width, stride) int32.  No allocation, no sync;
+ * height * width == 0 launches nothing (n_out and status are then left as they are).
+ * Refused on the host: null required buffers, stride < 1, depth_stride < 1, non-finite intrinsics, fx or fy == 0,
+ * depth_min > depth_max (or either NaN), an unknown normal_source, a negative capacity; a short workspace returns
+ * QED_E_WORKSPACE. */
+#define QED_SURFACE_NORMAL_RENDERED 0
+#define QED_SURFACE_NORMAL_DEPTH 1
+int64_t qed_surface_workspace_ints(int32_t height, int32_t width, int32_t stride);
+int qed_surface_samples(int32_t height, int32_t width, const float* rgb, const float* depth, int32_t depth_stride,
+                        const float* alpha, const float* normal, const float* depth_normal, const uint8_t* valid,
+                        const uint8_t* mask, float fx, float fy, float cx, float cy, const float* viewmat, int32_t stride,
+                        float min_alpha, float depth_min, float depth_max, int32_t normal_source,
+                        float cos_max_normal_angle, float min_view_cos, int64_t capacity, float* points, float* normals,
+                        float* colors, int32_t* n_out, int32_t* workspace, int64_t workspace_ints, int32_t* status,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -417,16 +417,26 @@ def read_ply_positions(path) -> np.ndarray:
     return _stack_positions(*_read_ply_vertex(path))
 
 
-def read_ply(path):
+def read_ply(path, with_normals: bool = False):
     """``(positions, colors | None)`` of a PLY's vertex element: positions as ``read_ply_positions`` returns them,
     colours [N,3] from the properties ``red green blue`` -- uint8 as stored (uchar), or float32 / float64 as Open3D's
     tensor API writes them (the caller decides how to quantise) -- or None when the file has none.  Same supported
-    formats and the same refusals as ``read_ply_positions``."""
+    formats and the same refusals as ``read_ply_positions``.  ``with_normals``: a third result, the properties
+    ``nx ny nz`` as [N,3] float32 (float64 if stored so), or None when the file has none."""
     rgb = ("red", "green", "blue")
     n, cols = _read_ply_vertex(path, rgb)
     positions = _stack_positions(n, cols)
+    normals = None
+    if with_normals:
+        nxyz = ("nx", "ny", "nz")
+        _, ncols = _read_ply_vertex(path, nxyz)
+        if nxyz[0] in ncols:
+            if any(ncols[k].dtype.kind != "f" for k in nxyz):
+                raise RuntimeError(f"unsupported PLY (nx ny nz must be float): {path}")
+            nrm_t = np.float64 if any(ncols[k].dtype == np.float64 for k in nxyz) else np.float32
+            normals = np.stack([ncols[k].astype(nrm_t) for k in nxyz], axis=1) if n else np.zeros((0, 3), dtype=nrm_t)
     if rgb[0] not in cols:
-        return positions, None
+        return (positions, None, normals) if with_normals else (positions, None)
     kinds = {cols[k].dtype.kind for k in rgb}
     if kinds == {"f"}:
         col_t = np.float64 if any(cols[k].dtype == np.float64 for k in rgb) else np.float32
@@ -435,16 +445,22 @@ def read_ply(path):
     else:
         raise RuntimeError(f"unsupported PLY (red green blue must be uchar or float): {path}")
     colors = np.stack([cols[k].astype(col_t) for k in rgb], axis=1) if n else np.zeros((0, 3), dtype=col_t)
-    return positions, colors
+    return (positions, colors, normals) if with_normals else (positions, colors)
 
 
-def write_ply(path, positions: np.ndarray, colors: np.ndarray = None) -> None:
+def write_ply(path, positions: np.ndarray, colors: np.ndarray = None, normals: np.ndarray = None) -> None:
     """Binary little-endian PLY: ``x y z`` float and, with ``colors`` (uint8 [N,3]), ``red green blue`` uchar -- the
-    layout the reference stores on purpose (:388) and its dataparser reads back."""
+    layout the reference stores on purpose (:388) and its dataparser reads back.  ``normals`` ([N,3], stored as float):
+    ``nx ny nz`` right after ``x y z``, where Poisson tools look for them; without them the file is what it always was."""
     positions = np.asarray(positions)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {positions.shape[0]}",
               "property float x", "property float y", "property float z"]
+    if normals is not None:
+        normals = np.asarray(normals)
+        assert normals.shape == (positions.shape[0], 3)
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         colors = np.asarray(colors)
         assert colors.dtype == np.uint8 and colors.shape == (positions.shape[0], 3)
@@ -453,6 +469,9 @@ def write_ply(path, positions: np.ndarray, colors: np.ndarray = None) -> None:
     rec = np.empty(positions.shape[0], dtype=np.dtype(fields))
     for j, k in enumerate("xyz"):
         rec[k] = positions[:, j]
+    if normals is not None:
+        for j, k in enumerate(("nx", "ny", "nz")):
+            rec[k] = normals[:, j]
     if colors is not None:
         for j, k in enumerate(("red", "green", "blue")):
             rec[k] = colors[:, j]

@@ -172,6 +172,17 @@ class Trainer:
         return export_gaussian_ply(self.model, path, frame=frame, dataparser_transform=out.dataparser_transform,
                                    dataparser_scale=out.dataparser_scale, color_mode=color_mode)
 
+    def export_pointcloud(self, path, frame: str = "model", split: str = "all", **options):
+        """An oriented surface point cloud of the model over the dataset's views (surface_cloud.export_pointcloud; its
+        keyword ``options``, ``voxel_size`` 0.01 model units unless given), in the model's frame or the dataset's."""
+        from .render import dataset_path
+        from .surface_cloud import export_pointcloud
+        out = self.datamanager.outputs
+        options.setdefault("voxel_size", 0.01)
+        return export_pointcloud(self.model, dataset_path(self.datamanager, split), path, frame=frame,
+                                 dataparser_transform=out.dataparser_transform, dataparser_scale=out.dataparser_scale,
+                                 **options)
+
     def resume(self, path) -> None:
         """The six tensors, the step and the optimiser state of ``save`` (its other keys are for the exporter and are not
         read): the model is rebuilt around the loaded Gaussians (their number may differ from the seeded model's) with
@@ -321,6 +332,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="after the last evaluation, write the Gaussians as a 3DGS PLY file (gaussian_ply.py)")
     ap.add_argument("--export-frame", choices=("model", "dataset"), default="model",
                     help="'dataset': undo the dataparser's orientation, centring and scale in the exported file")
+    ap.add_argument("--export-pointcloud", metavar="PATH", default=argparse.SUPPRESS,
+                    help="after the last evaluation, write an oriented, coloured surface point cloud of the model over the "
+                         "dataset's views as a PLY file (surface_cloud.py), in the frame of --export-frame")
     ap.add_argument("--cache-device", default=None, help="'cpu' keeps the image cache in pinned host memory")
     ap.add_argument("--render-eval", metavar="DIR", default=None,
                     help="after the last evaluation, write the evaluation views as PNG files (render.py: colour, 16-bit depth "
@@ -403,6 +417,9 @@ def main(argv=None) -> Dict:
         res = trainer.export_ply(a.export_ply, a.export_frame)
         print(f"exported {res['written']} Gaussians to {a.export_ply} ({a.export_frame} frame; dropped "
               f"{res['dropped_nonfinite']} non-finite, {res['dropped_low_opacity']} below opacity 1/255)")
+    if getattr(a, "export_pointcloud", None):
+        cloud = trainer.export_pointcloud(a.export_pointcloud, a.export_frame)
+        print(f"exported a surface cloud of {len(cloud)} points to {a.export_pointcloud} ({a.export_frame} frame)")
     done = trainer.step - first
     result = {"steps": trainer.step, "steps_per_s": done / elapsed if elapsed > 0 and done else 0.0,
               "eval": metrics, "gaussian_count": trainer.model.num_points}
