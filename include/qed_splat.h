@@ -70,7 +70,8 @@ extern "C" {
  *   4  qed_adam_tick_t carries beta1 / beta2 as doubles (they were floats): the device-resident bias corrections are
  *      formed at double precision, as the host-state path forms them.
  * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_gaussian_normals,
- * qed_normal_maps, qed_depth_normals, qed_angular_error; qed_normal_loss, qed_gaussian_normals_bwd, qed_normal_rows_merge). */
+ * qed_normal_maps, qed_depth_normals, qed_angular_error; qed_normal_loss, qed_gaussian_normals_bwd, qed_normal_rows_merge;
+ * qed_normal_consistency, qed_normal_rows_merge_depth). */
 #define QED_ABI_VERSION 4
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
@@ -1063,6 +1064,56 @@ int qed_gaussian_normals_bwd(int32_t N, int32_t C, const float* means, const flo
                              const float* viewmats, const int32_t* radii, const float* normal_rows, const float* scale,
                              uint32_t flags, int32_t add, float* v_quats, void* stream);
 int qed_normal_rows_merge(int64_t total, const float* normal_rows, const float* scale, float* rows, void* stream);
+
+/* ---- normal consistency and normal smoothness in training (csrc/normal_consistency.hip) ------------------------------------
+ * Two regularisers on the rendered normal that need no sensor normals.  The consistency term is the rendered-normal to
+ * rendered-depth-normal term of 2DGS / PGSR / dn-splatter, the smoothness term dn-splatter's total variation on the predicted
+ * normal restricted to defined pairs -- both RESTATED FROM MEMORY of those projects, not checked against them.  Per pixel p of
+ * one camera's step, with A the accumulated normal, alpha the accumulation and D the ACCUMULATED depth:
+ *   n^(p) = A / |A| where alpha >= min_alpha and |A| > 1e-8 (qed_normal_maps' rule);
+ *   N(p)  = qed_normal_maps' depth normal, exactly: z = D / alpha where alpha >= min_alpha, invalid where not finite or <= 0;
+ *           P = ((x + .5 - cx) z / fx, (y + .5 - cy) z / fy, z); dx = P(x+1,y) - P(x-1,y), dy = P(x,y+1) - P(x,y-1),
+ *           N = normalize(dy x dx); undefined on the border, where the pixel or a 4-neighbour is invalid and where
+ *           |dy x dx| <= 1e-20; evaluated in double from the float32 inputs;
+ *   V_c   = the pixels where n^ and N are both defined and mask (float32, may be NULL) is non-zero;
+ *   normal_consistency_loss = lambda_c * mean over V_c of (1 - n^ . N),   0 with zero gradients when V_c is empty;
+ *   E_x   = the horizontal neighbour pairs (p, p + x) with n^ defined and the mask non-zero at both ends, E_y the vertical ones;
+ *   normal_tv_loss = lambda_tv * [ mean over E_x and the 3 channels of |n^(p + x) - n^(p)|
+ *                                  + mean over E_y and the 3 channels of |n^(p + y) - n^(p)| ],  each mean 0 on an empty set;
+ *           the derivative of |t| at exactly t == 0 is 0.
+ * Gradients flow to A from both terms; from the consistency term also through N to z at the FOUR NEIGHBOURS (the centre's own
+ * z does not enter N: a pixel gets a depth gradient only as a neighbour of other pixels), and from z to D and alpha:
+ * d z / d D = 1 / alpha, d z / d alpha = -D / alpha^2.  Every validity decision, the 1e-20 test and the intrinsics are constants.
+ *
+ * qed_normal_consistency: one image.  A(p) = accum[p * accum_stride + 0..2] (accum_stride >= 3: an [H,W,4] = [A, D] image has
+ *   stride 4), alpha[H,W], D(p) = depth[p * depth_stride] (as qed_normal_maps; NULL allowed without QED_NC_CONSISTENCY).
+ *   flags: the terms QED_NC_CONSISTENCY, QED_NC_TV (a term that is off has value 0 and no gradient) and the passes
+ *   QED_NC_REDUCE (one streaming launch and a one-workgroup fold: out[8] (device doubles) = {consistency loss, mean of
+ *   1 - n^ . N, |V_c|, tv loss, x mean, y mean, |E_x|, |E_y|}, out_f[2] (device floats, may be NULL) = {consistency loss,
+ *   tv loss}) and QED_NC_GRAD (one launch, after a reduce pass on the same inputs -- in the same call or an earlier one --
+ *   whose `out` it READS: the two terms have different denominators, which therefore never reach the host).  The gradient
+ *   pass writes the FULLY SCALED d (g_c loss_c + g_tv loss_tv) / d . : v_accum(p) at v_accum[p * v_accum_stride + 0..2],
+ *   v_depth(p) at v_depth[p * v_depth_stride] and v_alpha[H,W] (either may be NULL), zero where nothing arrives.  g_c, g_tv:
+ *   the upstream gradients, device floats, NULL = 1.  nl_v_accum (may be NULL; [H,W,3]): qed_normal_loss' UNSCALED image,
+ *   added to v_accum times nl_scale[0] (its out_f[1]) times g_nl[0] (NULL = 1), so that with all three normal terms one
+ *   image carries the sum.  No floating-point atomics: the depth gradient of a pixel is GATHERED, in a fixed order, from the
+ *   stencils centred on its four neighbours; sums are carried in double and folded in a fixed order -- the same input gives
+ *   the same bits.  workspace: QED_NORMAL_CONSISTENCY_WS_DOUBLES doubles (no zeroing needed; the reduce pass only).
+ *   height * width == 0 writes zeros to out; an image under 3 x 3 has no depth normal (its TV pairs exist).
+ * qed_normal_rows_merge_depth: qed_normal_rows_merge for the rows of a 4-channel normal pass: slots 0, 1, 4..7 AND 11 (depth)
+ *   are added, times the device scale (NULL = 1); slots 2, 3 (absgrad), 8..10 (colour) and 12..15 of `rows` keep their bits. */
+#define QED_NORMAL_CONSISTENCY_WS_DOUBLES (6 * 1024)
+#define QED_NC_CONSISTENCY 1u
+#define QED_NC_TV 2u
+#define QED_NC_REDUCE 4u
+#define QED_NC_GRAD 8u
+int qed_normal_consistency(int32_t height, int32_t width, const float* accum, int32_t accum_stride, const float* alpha,
+                           const float* depth, int32_t depth_stride, float fx, float fy, float cx, float cy, float min_alpha,
+                           const float* mask, float lambda_c, float lambda_tv, uint32_t flags, const float* g_c,
+                           const float* g_tv, const float* nl_v_accum, const float* nl_scale, const float* g_nl,
+                           double* workspace, float* v_accum, int32_t v_accum_stride, float* v_depth, int32_t v_depth_stride,
+                           float* v_alpha, double* out, float* out_f, void* stream);
+int qed_normal_rows_merge_depth(int64_t total, const float* normal_rows, const float* scale, float* rows, void* stream);
 
 /* ---- oriented surface samples of one rendered view (csrc/surface.hip) -------------------------------------------------------
  * The planes get_outputs returns in evaluation mode with output_normals, back-projected into a compact list of world points

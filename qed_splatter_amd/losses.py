@@ -1,7 +1,7 @@
 """The image losses of a training step as autograd nodes over the loss kernels: the stand-alone SSIM (``ssim``), the
 statements around the operator (``_PostProcess``), get_loss_dict's two terms (``_ImageLosses``), the fused step's K8 node
-(``_FusedImageLoss``), splatfacto's MCMC regularisers (``_McmcReg``) and the normal loss (``_NormalLoss``), with the helpers that prepare their inputs and
-scratch buffers.  Nothing in here touches the model: ``model.py`` and ``metrics.py`` call in, this module imports the
+(``_FusedImageLoss``), splatfacto's MCMC regularisers (``_McmcReg``), the normal loss (``_NormalLoss``) and the normal
+consistency and smoothness terms (``_NormalConsistency``), with the helpers that prepare their inputs and scratch buffers.  Nothing in here touches the model: ``model.py`` and ``metrics.py`` call in, this module imports the
 library binding only."""
 from __future__ import annotations
 
@@ -384,3 +384,102 @@ class _NormalLoss(torch.autograd.Function):
             unit = g.data_ptr() == _unit_grad(g.device).data_ptr()
             return (v_accum if unit else v_accum * g.to(torch.float32),) + (None,) * 9
         return (v_accum * (g.to(torch.float32) * out_f[1]),) + (None,) * 9
+
+
+def normal_loss_image(accum: Tensor, alpha: Tensor, target: Tensor, target_valid: Tensor, valid_bits: int, mask, normal_lambda,
+                      use_cosine, min_alpha):
+    """qed_normal_loss without a node of its own: ``(the unscaled per-pixel d l / d A [H,W,3], out_f = {loss, normal_lambda /
+    max(|V|, 1)})`` for ``_NormalConsistency(nl=...)``, whose gradient launch adds the image, scaled, to its own."""
+    accum = accum.contiguous()
+    n_pix = accum.numel() // 3
+    dev = accum.device
+    if mask is not None:
+        mask = mask.to(device=dev, dtype=torch.float32).contiguous()
+    ws = torch.empty(L.NORMAL_LOSS_WS_DOUBLES, dtype=torch.float64, device=dev)
+    v_accum = torch.empty_like(accum)
+    parts = torch.empty(4, dtype=torch.float64, device=dev)
+    out_f = torch.empty(2, dtype=torch.float32, device=dev)
+    L.check(L.load().qed_normal_loss(n_pix, L.ptr(accum), L.ptr(alpha.contiguous()), L.ptr(target), L.ptr(target_valid),
+                                     int(valid_bits), L.ptr(mask), float(min_alpha), 1 if use_cosine else 0,
+                                     float(normal_lambda), L.ptr(ws), L.ptr(v_accum), L.ptr(parts), L.ptr(out_f), _stream()),
+            "qed_normal_loss")
+    return v_accum, out_f
+
+
+class _NormalConsistency(torch.autograd.Function):
+    """The normal consistency and normal smoothness terms on one image (normals.normal_consistency_loss; include/qed_splat.h
+    states them): the forward runs qed_normal_consistency's reduce pass (the two values and their three denominators, all on
+    the device), the backward its gradient pass, which reads the denominators and the upstream gradients from device memory
+    and writes the FULLY SCALED gradient images -- each term stays separately differentiable, and nothing is read back.
+    ``image`` is [H,W,3] (A; ``depth`` then the accumulated depth, any evenly strided view) or [H,W,4] = [A, D] with ``depth``
+    None (normals.accumulated_normals(with_depth=True)): the gradient then is ONE [H,W,4] image, written in place by the
+    kernel with an element stride.  ``nl`` = (qed_normal_loss' unscaled image, its out_f) or None: with it the node returns
+    that loss as a fourth value and its gradient rides in the same image (model.fused_loss: all three normal terms, no torch
+    statement on an image)."""
+
+    @staticmethod
+    def forward(ctx, image, alpha, depth, intr, mask, lambda_c, lambda_tv, use_c, use_tv, min_alpha, nl=None):
+        ctx.set_materialize_grads(False)
+        if not image.is_cuda or image.dtype != torch.float32:
+            raise L.QedSplatError("the normal consistency terms need float32 GPU tensors: there is no CPU path in the product")
+        image, alpha = image.detach().contiguous(), alpha.detach().contiguous()
+        H, W, ch = image.shape
+        dev = image.device
+        packed = ch == 4 and depth is None
+        if packed:
+            d_view, d_stride = image[..., 3], 4
+        elif use_c:
+            from .normals import _strided_plane
+            if ch != 3 or depth is None:
+                raise ValueError("the consistency term needs the accumulated depth: image [H,W,3] with depth, or [H,W,4]")
+            d_view, d_stride = _strided_plane(depth, H, W)
+        else:
+            d_view, d_stride = None, 1
+        flags = (L.NC_CONSISTENCY if use_c else 0) | (L.NC_TV if use_tv else 0)
+        ws = torch.empty(L.NORMAL_CONSISTENCY_WS_DOUBLES, dtype=torch.float64, device=dev)
+        parts = torch.empty(8, dtype=torch.float64, device=dev)
+        out_f = torch.empty(2, dtype=torch.float32, device=dev)
+        fx, fy, cx, cy = intr
+        ctx.args = (H, W, L.ptr(image), ch, L.ptr(alpha), L.ptr(d_view), d_stride, fx, fy, cx, cy, min_alpha, L.ptr(mask),
+                    lambda_c, lambda_tv)
+        L.check(L.load().qed_normal_consistency(*ctx.args, flags | L.NC_REDUCE, None, None, None, None, None, L.ptr(ws), None,
+                                                3, None, 1, None, L.ptr(parts), L.ptr(out_f), _stream()),
+                "qed_normal_consistency")
+        ctx.save_for_backward(image, alpha, d_view, mask, parts, *(nl if nl is not None else ()))
+        ctx.packed, ctx.use = packed, (bool(use_c), bool(use_tv))
+        ctx.depth_shape = None if (packed or depth is None) else depth.shape
+        ctx.mark_non_differentiable(parts)
+        nl_loss = nl[1][0:1].view(()) if nl is not None else None
+        return out_f[0:1].view(()), out_f[1:2].view(()), parts, nl_loss
+
+    @staticmethod
+    def backward(ctx, g_c, g_tv, _g_parts, g_nl=None):
+        image, alpha, d_view, mask, parts = ctx.saved_tensors[:5]
+        nl = ctx.saved_tensors[5:]
+        use_c, use_tv = ctx.use[0] and g_c is not None, ctx.use[1] and g_tv is not None
+        use_nl = len(nl) == 2 and g_nl is not None
+        if not (use_c or use_tv or use_nl):
+            return (None,) * 11
+        H, W, ch = image.shape
+        dev = image.device
+        unit = _unit_grad(dev).data_ptr()
+
+        def up(g):                                            # (backward_fused()'s cached unit gradient: NULL = 1)
+            return None if (g is None or g.data_ptr() == unit) else g.to(torch.float32).reshape(1).contiguous()
+        g_c, g_tv, g_nl = up(g_c), up(g_tv), up(g_nl)
+        flags = (L.NC_CONSISTENCY if use_c else 0) | (L.NC_TV if use_tv else 0) | L.NC_GRAD
+        v_image = torch.empty_like(image)
+        v_alpha = torch.empty_like(alpha) if ctx.use[0] else None
+        v_depth = None
+        if ctx.packed:
+            vd_ptr, vd_stride = v_image.data_ptr() + 12, 4
+        else:
+            v_depth = torch.empty(H, W, dtype=torch.float32, device=dev) if ctx.use[0] else None
+            vd_ptr, vd_stride = L.ptr(v_depth), 1
+        L.check(L.load().qed_normal_consistency(*ctx.args, flags, L.ptr(g_c), L.ptr(g_tv), L.ptr(nl[0]) if use_nl else None,
+                                                L.ptr(nl[1][1:]) if use_nl else None, L.ptr(g_nl), None, L.ptr(v_image), ch,
+                                                vd_ptr, vd_stride, L.ptr(v_alpha), L.ptr(parts), None, _stream()),
+                "qed_normal_consistency")
+        if v_depth is not None:
+            v_depth = v_depth.reshape(ctx.depth_shape)
+        return (v_image, v_alpha, v_depth) + (None,) * 8

@@ -145,6 +145,19 @@ class QEDSplatterModelConfig:
     use_normal_loss: bool = False
     normal_lambda: float = 0.1
     use_normal_cosine_loss: bool = False
+    # Two regularisers on the rendered normal that need no sensor normals (normals.normal_consistency_loss,
+    # include/qed_splat.h; both off by default).  use_normal_consistency: normal_consistency_lambda * mean (1 - n^ . N) against
+    # the normal N of the RENDERED depth, the 2DGS / PGSR / dn-splatter regulariser, from step normal_consistency_from_step on
+    # (before it the term launches nothing and its key is absent); its gradient reaches the depth through the stencil.  It
+    # needs output_depth_during_training.  use_normal_tv: normal_tv_lambda * the total variation of n^ over defined neighbour
+    # pairs (dn-splatter's).  The two weights are those projects' values AS REMEMBERED, not checked against them.  Each works
+    # alone, together and beside use_normal_loss (one normal pass serves all); get_loss_dict / fused_loss add
+    # "normal_consistency_loss" / "normal_tv_loss".  Refused where use_normal_loss is
+    use_normal_consistency: bool = False
+    normal_consistency_lambda: float = 0.05
+    normal_consistency_from_step: int = 0
+    use_normal_tv: bool = False
+    normal_tv_lambda: float = 0.1
 
     @classmethod
     def synthetic(cls, **kw) -> "QEDSplatterModelConfig":
@@ -235,13 +248,15 @@ class StepContext:
 
     And two facts about the forward call itself, which the data-parallel exchanges refuse (parallel.py):
     ``pose_optimizer`` / ``grid_optimizer``, the camera and bilateral-grid optimisers ``fused_loss`` ran with, and
-    ``normal_loss``, whether the step carries the normal loss."""
+    ``normal_loss``, whether the step carries the normal loss, ``normal_reg``, whether it carries the normal consistency or
+    smoothness term."""
 
-    __slots__ = ("rgb", "handover", "_gt", "ssim", "pose_optimizer", "grid_optimizer", "normal_loss")
+    __slots__ = ("rgb", "handover", "_gt", "ssim", "pose_optimizer", "grid_optimizer", "normal_loss", "normal_reg")
 
-    def __init__(self, pose_optimizer=None, grid_optimizer=None, normal_loss=False):
+    def __init__(self, pose_optimizer=None, grid_optimizer=None, normal_loss=False, normal_reg=False):
         self.rgb = None
         self.normal_loss = bool(normal_loss)          # the step renders normals for config.use_normal_loss
+        self.normal_reg = bool(normal_reg)            # ... for config.use_normal_consistency / use_normal_tv
         self.handover = None
         self._gt = None
         self.ssim = None
@@ -813,7 +828,12 @@ class QEDSplatterModel(nn.Module):
         if want_nloss and self.camera_optimizer is not None and getattr(self.camera_optimizer, "active", True):
             raise NotImplementedError("use_normal_loss beside an active camera optimiser: a Gaussian's normal depends on the "
                                       "view rotation, which the normal render does not differentiate")
-        ctx = attrs["_step"] = StepContext(normal_loss=want_nloss)
+        # config.use_normal_consistency / use_normal_tv: the same pass serves them (with the depth channel for the first)
+        want_c, want_tv = self._normal_reg_wanted() if torch.is_grad_enabled() else (False, False)
+        if want_c or want_tv:
+            self._refuse_normal_reg(want_c, self.camera_optimizer, False)
+        ctx = attrs["_step"] = StepContext(normal_loss=want_nloss, normal_reg=want_c or want_tv)
+        want_npass = want_nloss or want_c or want_tv
 
         if self.config.rasterize_mode not in ["antialiased", "classic"]:      # model.py:253-254
             raise ValueError("Unknown rasterize_mode: %s", self.config.rasterize_mode)
@@ -834,7 +854,7 @@ class QEDSplatterModel(nn.Module):
         # config.output_normals: evaluation and rendering only (the records of the projection stay reachable for it)
         want_normals = bool(getattr(self.config, "output_normals", False)) and not self.training
         quat_sink = None
-        if want_nloss:
+        if want_npass:
             from .normals import QuatGradSink
             quat_sink = QuatGradSink()           # (the normals' part of quats.grad, added by the projection backward)
 
@@ -860,13 +880,13 @@ class QEDSplatterModel(nn.Module):
                 _flags=flags, _sh_rest=sh_rest, _sync=not (self.config.async_intersection_count and self.training),
                 _c2w=(c2w, intr) if c2w is not None else None, _post_background=bg, _handover=handover,
                 _means2d_leaf=True,     # xys is only retained and read (below; densify.py): its gradient arrives as a view
-                _capture_slot=capture_slot, _manual=manual, _keep_records=want_normals or want_nloss, _post_bwd=quat_sink,
+                _capture_slot=capture_slot, _manual=manual, _keep_records=want_normals or want_npass, _post_bwd=quat_sink,
                 # (a captured backward pass always writes the compact form; _SegmentFn.backward asks per replay)
                 _lazy_sh=self._lazy_sh_begin if (lazy and manual is None) else None)
 
         seg = None
         if (self.training and self.config.graph_segments and cam_c2w is not None and crop_ids is None
-                and torch.is_grad_enabled() and self.config.async_intersection_count and not want_nloss):
+                and torch.is_grad_enabled() and self.config.async_intersection_count and not want_npass):
             seg = self._outputs_segment(W, H, render_mode, sh_degree_to_use, flags, render_fn, cam_c2w, background)
         if seg is not None:
             rgb, alpha, depth_im = seg.run(cam_c2w[0], cam_c2w[1], background)
@@ -921,7 +941,10 @@ class QEDSplatterModel(nn.Module):
         }
         if want_normals:
             outputs.update(self._normal_outputs(means_crop, quats_crop, scales_crop, viewmat, K, info, render, alpha))
-        if want_nloss:
+        if want_c or want_tv:
+            self._normal_pass_outputs(outputs, means_crop, quats_crop, scales_crop, viewmat, K, cam_c2w, info, render,
+                                      quat_sink, want_c)
+        elif want_nloss:
             from .normals import accumulated_normals
             accum = accumulated_normals(means_crop, quats_crop, scales_crop, viewmat, info, render, log_scales=True,
                                         quat_sink=quat_sink).squeeze(0)      # (a view: its backward is no pass over the image)
@@ -930,6 +953,70 @@ class QEDSplatterModel(nn.Module):
             accum._qed_intrinsics = self._host_intrinsics(cam_c2w, K)      # (get_loss_dict: the depth target's normals)
             outputs["normal_accum"] = accum
         return outputs
+
+    def _normal_reg_wanted(self) -> Tuple[bool, bool]:
+        """(consistency term, smoothness term) of this training step: config.use_normal_consistency from
+        normal_consistency_from_step on, config.use_normal_tv."""
+        cfg = self.config
+        if not self.training:
+            return False, False
+        want_c = bool(cfg.use_normal_consistency) and int(self.step) >= int(cfg.normal_consistency_from_step)
+        return want_c, bool(cfg.use_normal_tv)
+
+    def _refuse_normal_reg(self, want_c: bool, camera_optimizer, fused: bool) -> None:
+        """The refusals of use_normal_consistency / use_normal_tv, before any launch of the step."""
+        if camera_optimizer is not None and getattr(camera_optimizer, "active", True):
+            raise NotImplementedError("use_normal_consistency / use_normal_tv beside an active camera optimiser: a Gaussian's "
+                                      "normal depends on the view rotation, which the normal render does not differentiate")
+        if fused and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("use_normal_consistency / use_normal_tv inside a captured step (graph.py, segments.py): "
+                                      "the normal pass hands its rows from one autograd node to another on the host, per step")
+        if want_c and not self.config.output_depth_during_training:
+            raise NotImplementedError("use_normal_consistency with output_depth_during_training=False: the term compares the "
+                                      "rendered normal with the normal of the rendered depth")
+
+    def _normal_pass_outputs(self, outputs, means, quats, scales, viewmat, K, cam_c2w, info, render, quat_sink, want_c) -> None:
+        """get_outputs with the consistency or smoothness term on: the one normal pass of the step, with the depth channel for
+        the consistency term.  outputs["normal_accum"] [H,W,3] as for use_normal_loss (a view of the 4-channel image then);
+        outputs["normal_accum_depth"] [H,W,4] = [A, D] and outputs["normal_alpha"], the pass's own alpha, with want_c."""
+        from .normals import accumulated_normals
+        res = accumulated_normals(means, quats, scales, viewmat, info, render, log_scales=True, quat_sink=quat_sink,
+                                  with_depth=want_c)
+        info.pop("_splats", None)
+        info.pop("_isect_offsets_full", None)
+        intr = self._host_intrinsics(cam_c2w, K)
+        if want_c:
+            packed = res[0].squeeze(0)
+            packed._qed_intrinsics = intr
+            outputs["normal_accum_depth"], outputs["normal_alpha"] = packed, res[1].squeeze(0)
+            accum = packed[..., 0:3]
+        else:
+            accum = res.squeeze(0)
+        accum._qed_intrinsics = intr
+        outputs["normal_accum"] = accum
+
+    def _add_normal_reg_losses(self, out: Dict[str, Tensor], outputs, mask) -> None:
+        """get_loss_dict: "normal_consistency_loss" / "normal_tv_loss" on the normal pass get_outputs made for them (the
+        consistency term's key is absent where that call, before normal_consistency_from_step, made no depth channel)."""
+        from .normals import normal_consistency_loss
+        cfg = self.config
+        packed, accum = outputs.get("normal_accum_depth"), outputs.get("normal_accum")
+        want_c = bool(cfg.use_normal_consistency) and packed is not None
+        want_tv = bool(cfg.use_normal_tv) and accum is not None
+        if not (want_c or want_tv):
+            return
+        lam_c = float(cfg.normal_consistency_lambda) if want_c else None
+        lam_tv = float(cfg.normal_tv_lambda) if want_tv else None
+        if packed is not None:
+            terms = normal_consistency_loss(packed, outputs["normal_alpha"], None, packed._qed_intrinsics, mask, lam_c, lam_tv,
+                                            float(cfg.normals_min_alpha))
+        else:
+            terms = normal_consistency_loss(accum, outputs["accumulation"], None, accum._qed_intrinsics, mask, None, lam_tv,
+                                            float(cfg.normals_min_alpha))
+        if want_c:
+            out["normal_consistency_loss"] = terms[0]
+        if want_tv:
+            out["normal_tv_loss"] = terms[1]
 
     def _host_intrinsics(self, cam_c2w, K) -> Tuple[float, float, float, float]:
         """(fx, fy, cx, cy) of the step's (rescaled) camera as host floats, which qed_depth_normals takes as arguments.  One
@@ -1064,6 +1151,8 @@ class QEDSplatterModel(nn.Module):
         if accum is not None:
             target = self._normal_target(batch, depth_batch, H, W, accum._qed_intrinsics)
             out["normal_loss"] = self._normal_loss_term(accum, outputs["accumulation"], target, mask)
+        if self.training and (cfg.use_normal_consistency or cfg.use_normal_tv):
+            self._add_normal_reg_losses(out, outputs, mask)
         return out
 
     # ---- get_metrics_dict (model.py:120-197) ----
@@ -1276,7 +1365,10 @@ class QEDSplatterModel(nn.Module):
         if want_nloss and torch.cuda.is_current_stream_capturing():
             raise NotImplementedError("use_normal_loss inside a captured step (graph.py, segments.py): the normal pass hands "
                                       "its rows from one autograd node to another on the host, per step")
-        attrs["_step"] = StepContext(pose_opt, grid_opt, want_nloss)
+        want_c, want_tv = self._normal_reg_wanted()
+        if want_c or want_tv:
+            self._refuse_normal_reg(want_c, pose_opt, True)
+        attrs["_step"] = StepContext(pose_opt, grid_opt, want_nloss, want_c or want_tv)
         grid_idx = None
         if grid_opt is not None:
             grid_idx = cam_idx
@@ -1325,12 +1417,15 @@ class QEDSplatterModel(nn.Module):
         # config.use_normal_loss: the target first (a batch["normal"] of another size is refused before any launch of the
         # step), then the hook through which the projection backward adds the normals' part of the quaternion gradient
         normal = None
-        if want_nloss:
+        if want_nloss or want_c or want_tv:
             from .normals import QuatGradSink
-            target = self._normal_target(batch, gt_depth, H, W, self._host_intrinsics(cam_c2w, K))
+            intr = self._host_intrinsics(cam_c2w, K)
+            target = self._normal_target(batch, gt_depth, H, W, intr) if want_nloss else None
             if torch.is_grad_enabled():
                 post_bwd = QuatGradSink(post_bwd)
             normal = (target, post_bwd if torch.is_grad_enabled() else None, viewmat)
+            if want_c or want_tv:                # (config.use_normal_consistency / use_normal_tv: _add_fused_normal_terms)
+                normal += ((intr, want_c, want_tv),)
         frame_order = self._frame_order_slot(frame_key, H, W) if frame_key is not None else None
         # (the fused loss launch offers the compositing backward its zeroed accumulator and launch order through this)
         handover = Handover(self.num_points, frame_order)
@@ -1385,6 +1480,8 @@ class QEDSplatterModel(nn.Module):
         """config.use_normal_loss on the fused route: the accumulated normal behind this step's colour pass and the loss on
         it, added to ``loss`` and returned (detached) as ``normal_loss``."""
         from .normals import accumulated_normals
+        if len(normal) == 4:
+            return self._add_fused_normal_terms(out, normal, info, render, alpha, mask)
         target, sink, viewmat = normal
         # the accumulated normal is this call's own, so the loss's factor normal_lambda / max(|V|, 1) goes to the
         # per-Gaussian rows as a device scalar (qed_normal_rows_merge, qed_gaussian_normals_bwd) instead of the image
@@ -1396,6 +1493,39 @@ class QEDSplatterModel(nn.Module):
         term = self._normal_loss_term(accum.squeeze(0), alpha[0], target, mask, scale_out=scale)
         out["loss"] = out["loss"] + term
         out["normal_loss"] = term.detach()
+
+    def _add_fused_normal_terms(self, out: Dict[str, Tensor], normal, info, render: Tensor, alpha: Tensor, mask) -> None:
+        """config.use_normal_consistency / use_normal_tv on the fused route, alone or beside use_normal_loss: ONE normal pass
+        (with the depth channel for the consistency term) and one loss node over it.  The node's gradient launch writes the
+        fully scaled sum of every term on -- the normal loss's unscaled image joins inside it -- into one image, which the
+        pass's compositing backward takes as it is."""
+        from .losses import normal_loss_image
+        from .normals import accumulated_normals, normal_consistency_loss
+        cfg = self.config
+        target, sink, viewmat, (intr, want_c, want_tv) = normal
+        res = accumulated_normals(self.means, self.quats, self.scales, viewmat, info, render, log_scales=True, quat_sink=sink,
+                                  with_depth=want_c)
+        info.pop("_splats", None)
+        info.pop("_isect_offsets_full", None)
+        image, own_alpha = (res[0][0], res[1][0]) if want_c else (res[0], alpha[0])
+        nl = None
+        if target is not None:
+            # (qed_normal_loss reads a dense [H,W,3]: beside the consistency term one copy of A out of the [A, D] image)
+            nl = normal_loss_image(image.detach()[..., 0:3], own_alpha.detach(), target[0], target[1], target[2], mask,
+                                   float(cfg.normal_lambda), bool(cfg.use_normal_cosine_loss), float(cfg.normals_min_alpha))
+        terms = normal_consistency_loss(image, own_alpha, None, intr, mask,
+                                        float(cfg.normal_consistency_lambda) if want_c else None,
+                                        float(cfg.normal_tv_lambda) if want_tv else None, float(cfg.normals_min_alpha),
+                                        _normal_loss=nl)
+        if nl is not None:
+            out["loss"] = out["loss"] + terms[2]
+            out["normal_loss"] = terms[2].detach()
+        if want_c:
+            out["loss"] = out["loss"] + terms[0]
+            out["normal_consistency_loss"] = terms[0].detach()
+        if want_tv:
+            out["loss"] = out["loss"] + terms[1]
+            out["normal_tv_loss"] = terms[1].detach()
 
     def _fused_loss_with_grid(self, grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags, sync,
                               handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask, lo, ls, mcmc_vals,

@@ -26,9 +26,14 @@ slots are merged into the colour pass's rows (so the projection backward runs on
 d L / d n_i, which ``qed_gaussian_normals_bwd`` takes to the raw quaternions.  Stated deviations: the axis choice and the
 facing sign carry no gradient; a normal's dependence on the VIEW rotation is not differentiated (a camera optimiser beside
 the loss is refused); the normal pass does not add to ``absgrad`` (gsplat's statistic is that of the total loss per pixel,
-which two passes cannot form), so the densifier sees the colour and depth loss only.  Out of scope: a total-variation term on
-the normals, a rendered-normal to rendered-depth-normal consistency term (it needs a backward pass through the depth stencil),
-ground-truth normal files in the dataparser, and meshing.
+which two passes cannot form), so the densifier sees the colour and depth loss only.  Out of scope: ground-truth normal files
+in the dataparser, and meshing.
+
+Two regularisers that need no sensor normals (config.use_normal_consistency / use_normal_tv; csrc/normal_consistency.hip):
+``normal_consistency_loss`` is the rendered-normal to rendered-depth-normal consistency term and the total variation of the
+rendered normal, both restated from memory.  The consistency term's gradient passes the depth stencil backwards to the
+accumulated depth and alpha; ``accumulated_normals(with_depth=True)`` composites the normal records with 4 channels, so that
+[A, D] and alpha come from -- and differentiate through -- the one normal pass.
 """
 from __future__ import annotations
 
@@ -90,31 +95,35 @@ def gaussian_normals(means: Tensor, quats: Tensor, scales: Tensor, viewmats: Ten
     return out if splats is None else (out, records)
 
 
-def accumulate_normals(records: Tensor, info: Dict, C: int, N: int) -> Tensor:
+def accumulate_normals(records: Tensor, info: Dict, C: int, N: int, with_depth: bool = False):
     """A[C,H,W,3] = Sum_i alpha_i T_i n_i: one call of the forward compositing kernel on ``records``
-    (``gaussian_normals(..., splats=...)``) with the tile lists of the colour pass that produced ``info``."""
+    (``gaussian_normals(..., splats=...)``) with the tile lists of the colour pass that produced ``info``.
+    ``with_depth``: the pass composites 4 channels and returns ``([C,H,W,4] = [A, D], alpha [C,H,W,1])`` -- the records carry
+    the projection's depth slot bit for bit, so D and alpha are the colour pass's accumulated depth and alpha exactly."""
     W, H, tw, th = int(info["width"]), int(info["height"]), int(info["tile_width"]), int(info["tile_height"])
     dev = records.device
     offsets = info["_isect_offsets_full"]
     flatten_ids = info["flatten_ids"]
-    accum = torch.empty(C, H, W, 3, dtype=torch.float32, device=dev)
+    channels = 4 if with_depth else 3
+    accum = torch.empty(C, H, W, channels, dtype=torch.float32, device=dev)
     alpha = torch.empty(C, H, W, 1, dtype=torch.float32, device=dev)
     last_ids = torch.empty(C, H, W, dtype=torch.int32, device=dev)
-    L.check(L.load().qed_composite_fwd(C, N, L.ptr(records), L.ptr(flatten_ids), L.ptr(offsets), W, H, tw, th, 3, None,
+    L.check(L.load().qed_composite_fwd(C, N, L.ptr(records), L.ptr(flatten_ids), L.ptr(offsets), W, H, tw, th, channels, None,
                                        L.ptr(accum), L.ptr(alpha), None, L.ptr(last_ids), None, None, None,
                                        L.composite_launch_flags(), _stream()), "qed_composite_fwd")
-    return accum
+    return (accum, alpha) if with_depth else accum
 
 
 # ---- training: the accumulation as an autograd node, the loss ------------------------------------------------------------
 class NormalRows:
     """What one normal pass's backward leaves for the colour pass's compositing backward (rasterization._Composite): its
-    accumulator ``rows`` [C N, 16] and the device scalar (or None = 1) they are multiplied by when merged."""
+    accumulator ``rows`` [C N, 16] and the device scalar (or None = 1) they are multiplied by when merged.  ``with_depth``:
+    the rows of a 4-channel pass, whose depth slot is merged too (qed_normal_rows_merge_depth)."""
 
-    __slots__ = ("rows", "scale")
+    __slots__ = ("rows", "scale", "with_depth")
 
-    def __init__(self, rows: Tensor, scale: Optional[Tensor]):
-        self.rows, self.scale = rows, scale
+    def __init__(self, rows: Tensor, scale: Optional[Tensor], with_depth: bool = False):
+        self.rows, self.scale, self.with_depth = rows, scale, with_depth
 
 
 class QuatGradSink:
@@ -154,20 +163,22 @@ class _AccumulatedNormals(torch.autograd.Function):
     compositing backward then runs after this node's backward, finds the rows left on it and merges them into its own."""
 
     @staticmethod
-    def forward(ctx, render, quats, means, scales, viewmats, info, node, log_scales, quat_sink, grad_scale):
+    def forward(ctx, render, quats, means, scales, viewmats, info, node, log_scales, quat_sink, grad_scale, with_depth=False):
         ctx.set_materialize_grads(False)
         C, N = viewmats.shape[0], means.shape[0]
         _, records = gaussian_normals(means, quats, scales, viewmats, "camera", log_scales, splats=info["_splats"])
-        accum = accumulate_normals(records, info, C, N)
+        accum = accumulate_normals(records, info, C, N, with_depth)
         ctx.save_for_backward(records, _f32(means, "means"), _f32(quats, "quats"), _f32(scales, "scales"),
                               _f32(viewmats, "viewmats"), info["radii"], grad_scale)
-        ctx.node, ctx.log_scales, ctx.quat_sink = node, bool(log_scales), quat_sink
+        ctx.node, ctx.log_scales, ctx.quat_sink, ctx.with_depth = node, bool(log_scales), quat_sink, bool(with_depth)
         return accum
 
     @staticmethod
-    def backward(ctx, v_accum):
+    def backward(ctx, v_accum, v_own_alpha=None):
+        if ctx.with_depth:
+            return _AccumulatedNormals._backward_with_depth(ctx, v_accum, v_own_alpha)
         if v_accum is None:
-            return (None,) * 10
+            return (None,) * 11
         records, means, quats, scales, viewmats, radii, grad_scale = ctx.saved_tensors
         node = ctx.node
         # the colour pass's own lists and geometry (they depend on nothing the normals change)
@@ -192,19 +203,58 @@ class _AccumulatedNormals(torch.autograd.Function):
             ctx.quat_sink.jobs.append(job)
         elif ctx.needs_input_grad[1]:
             v_quats = _quat_grad(*job, add=False)
-        return (None, v_quats) + (None,) * 8
+        return (None, v_quats) + (None,) * 9
+
+    @staticmethod
+    def _backward_with_depth(ctx, v_accum, v_own_alpha):
+        """The 4-channel pass: the incoming gradients of [A, D] and of this pass's own alpha go to the unchanged compositing
+        backward with 4 channels; the rows then carry the depth slot too, and NormalRows says so to the merge."""
+        if v_accum is None and v_own_alpha is None:
+            return (None,) * 11
+        records, means, quats, scales, viewmats, radii, grad_scale = ctx.saved_tensors
+        node = ctx.node
+        _splats, flatten_ids, offsets, alpha, last_ids, _bg, _render, _pbg, t_final = node.saved_tensors
+        C, N, W, H, tw, th = node.meta[:6]
+        dev = records.device
+        if v_accum is None:
+            v_accum = torch.zeros(C, H, W, 4, dtype=torch.float32, device=dev)
+        v_accum = _f32(v_accum, "v_accum")
+        if v_accum.shape != (C, H, W, 4):
+            raise ValueError(f"the gradient of the accumulated normal and depth must be [{C},{H},{W},4]")
+        v_alpha = _f32(v_own_alpha, "v_alpha") if v_own_alpha is not None else \
+            torch.zeros(C, H, W, 1, dtype=torch.float32, device=dev)
+        rows = torch.zeros(C * N, L.VSPLAT_FLOATS, dtype=torch.float32, device=dev)
+        tile_cost = getattr(node, "tile_cost", None)
+        order_ws = torch.empty(C * tw * th + 1, dtype=torch.int32, device=dev) if tile_cost is not None else None
+        L.check(L.load().qed_composite_bwd(C, N, L.ptr(records), L.ptr(flatten_ids), L.ptr(offsets), W, H, tw, th, 4, None,
+                                           L.ptr(alpha), L.ptr(t_final), L.ptr(last_ids), L.ptr(v_accum), L.ptr(v_alpha),
+                                           L.ptr(rows), L.ptr(tile_cost), L.ptr(order_ws), None,
+                                           L.composite_launch_flags(), _stream()), "qed_composite_bwd")
+        node.__dict__.setdefault("normal_pending", []).append(NormalRows(rows, grad_scale, with_depth=True))
+        job = (means, quats, scales, viewmats, radii, rows, grad_scale, ctx.log_scales)
+        v_quats = None
+        if ctx.quat_sink is not None:
+            ctx.quat_sink.jobs.append(job)
+        elif ctx.needs_input_grad[1]:
+            v_quats = _quat_grad(*job, add=False)
+        return (None, v_quats) + (None,) * 9
 
 
 def accumulated_normals(means: Tensor, quats: Tensor, scales: Tensor, viewmats: Tensor, info: Dict, render: Tensor,
                         log_scales: bool = True, quat_sink: Optional[QuatGradSink] = None,
-                        grad_scale: Optional[Tensor] = None) -> Tensor:
+                        grad_scale: Optional[Tensor] = None, with_depth: bool = False):
     """A [C,H,W,3] = Sum_i alpha_i T_i n_i of the colour pass that returned ``render`` and ``info`` (rasterization(...,
     _keep_records=True)), DIFFERENTIABLE for any upstream gradient on A: through every alpha_i T_i to means, scales, quats
     and opacities (the colour pass's compositing backward merges this pass's rows into its own, so ``info["means2d"].grad``
     carries the sum and ``.absgrad`` the colour pass's only), and through every n_i to the raw quaternions -- returned to
     autograd as ``quats``' gradient, or with ``quat_sink`` (handed to the same rasterization call as ``_post_bwd``) added to
     the projection backward's in place.  ``grad_scale``: a device float [1] read at backward time that multiplies the
-    whole gradient of this node.  Under ``no_grad`` (or when ``render`` has no graph) it is ``accumulate_normals``."""
+    whole gradient of this node.  Under ``no_grad`` (or when ``render`` has no graph) it is ``accumulate_normals``.
+    ``with_depth`` (behind an RGB+D colour pass): returns ``([C,H,W,4] = [A, D], alpha [C,H,W,1])`` -- D and alpha bit for bit
+    the colour pass's -- and differentiates all of it through this one node: the compositing backward runs with 4 channels on
+    the incoming gradients of [A, D] and of the returned alpha, and its rows reach the projection backward with their depth
+    slot (qed_normal_rows_merge_depth).  This is how normal_consistency_loss sends its depth gradient to the Gaussians without
+    touching the colour pass's gradient images."""
     C, N = viewmats.shape[0], means.shape[0]
     if "_splats" not in info:
         raise ValueError("accumulated_normals needs the records of the colour pass: rasterization(..., _keep_records=True)")
@@ -212,7 +262,7 @@ def accumulated_normals(means: Tensor, quats: Tensor, scales: Tensor, viewmats: 
     if node is None:
         with torch.no_grad():
             _, records = gaussian_normals(means, quats, scales, viewmats, "camera", log_scales, splats=info["_splats"])
-            return accumulate_normals(records, info, C, N)
+            return accumulate_normals(records, info, C, N, with_depth)
     if not hasattr(node, "meta") or not hasattr(node, "tile_cost"):
         raise ValueError("accumulated_normals: `render` must be the image rasterization() returned (its first result)")
     if viewmats.requires_grad:
@@ -220,7 +270,13 @@ def accumulated_normals(means: Tensor, quats: Tensor, scales: Tensor, viewmats: 
                                   "dependence on the view rotation): detach them, or switch the camera optimiser off")
     if grad_scale is not None:
         grad_scale = _f32(grad_scale, "grad_scale").reshape(1)
-    return _AccumulatedNormals.apply(render, quats, means, scales, viewmats, info, node, log_scales, quat_sink, grad_scale)
+    if with_depth and node.meta[6] != 4:
+        raise ValueError("accumulated_normals(with_depth=True) needs an RGB+D colour pass (the projection backward takes the "
+                         "depth gradient only then)")
+    if not with_depth:
+        return _AccumulatedNormals.apply(render, quats, means, scales, viewmats, info, node, log_scales, quat_sink, grad_scale)
+    return _AccumulatedNormals.apply(render, quats, means, scales, viewmats, info, node, log_scales, quat_sink, grad_scale,
+                                     True)
 
 
 def depth_normal_target(depth: Tensor, fx: float, fy: float, cx: float, cy: float) -> Tuple[Tensor, Tensor]:
@@ -273,6 +329,42 @@ def normal_loss(accum: Tensor, alpha: Tensor, target: Tensor, target_valid: Tens
     loss, parts = _NormalLoss.apply(accum, _f32(alpha, "alpha"), _f32(target, "target"), tv, mask, float(normal_lambda),
                                     bool(use_cosine), float(min_alpha), int(valid_bits), scale_out)
     return (loss, parts) if return_parts else loss
+
+
+def normal_consistency_loss(accum: Tensor, alpha: Tensor, depth: Optional[Tensor], intrinsics: Sequence[float],
+                            mask: Optional[Tensor] = None, lambda_c: Optional[float] = 0.05, lambda_tv: Optional[float] = 0.1,
+                            min_alpha: float = 0.5, return_parts: bool = False, _normal_loss=None):
+    """``(normal_consistency_loss, normal_tv_loss)``, two 0-dim float32 tensors, each separately differentiable:
+    ``lambda_c * mean over V_c of (1 - n^ . N)`` -- the rendered normal n^ = A / |A| against the normal N of the RENDERED
+    depth z = D / alpha (normal_maps' stencil) -- and ``lambda_tv * [mean over E_x of |n^(p + x) - n^(p)| + the same over
+    E_y]``; include/qed_splat.h states the sets.  A weight of None switches its term off (value 0, no launch work for it).
+    ``accum`` [H,W,3] with ``alpha`` [H,W(,1)] and ``depth`` [H,W(,1)] the ACCUMULATED depth (any evenly strided view, e.g.
+    ``render[0, ..., 3]``; None without the consistency term), ``intrinsics`` = (fx, fy, cx, cy) as host floats, ``mask``
+    (bool / float, optional).  Gradients reach ``accum`` from both terms and ``depth`` / ``alpha`` from the first, so behind
+    ``rasterization(..., _keep_records=True)`` the terms train the Gaussians through ``accumulated_normals`` on one side and
+    the colour pass on the other.  Or ``accum`` [H,W,4] = [A, D] with ``depth=None``: one image of
+    ``accumulated_normals(..., with_depth=True)`` with that node's alpha, and the whole term differentiates through that one
+    node.  ``return_parts``: also the float64 device tensor {consistency loss, mean of 1 - n^ . N, |V_c|, tv loss, x mean,
+    y mean, |E_x|, |E_y|}.  Nothing is read back."""
+    from .losses import _NormalConsistency
+    use_c, use_tv = lambda_c is not None, lambda_tv is not None
+    if accum.dim() != 3 or accum.shape[-1] not in (3, 4):
+        raise ValueError("accum: [H,W,3], or [H,W,4] = [A, D]")
+    H, W = int(accum.shape[0]), int(accum.shape[1])
+    if alpha.numel() != H * W:
+        raise ValueError("alpha [H,W]")
+    if mask is not None:
+        mask = mask.to(device=accum.device, dtype=torch.float32).contiguous()
+        if mask.numel() != H * W:
+            raise ValueError(f"mask: {H * W} values")
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    if use_c and (fx == 0.0 or fy == 0.0):
+        raise ValueError("zero focal length")
+    loss_c, loss_tv, parts, nl_loss = _NormalConsistency.apply(
+        accum, alpha, depth, (fx, fy, cx, cy), mask, float(lambda_c) if use_c else 0.0, float(lambda_tv) if use_tv else 0.0,
+        use_c, use_tv, float(min_alpha), _normal_loss)
+    out = (loss_c, loss_tv) + ((parts,) if return_parts else ()) + ((nl_loss,) if _normal_loss is not None else ())
+    return out
 
 
 def normal_maps(accum: Tensor, alpha: Tensor, depth: Tensor, fx: float, fy: float, cx: float, cy: float,

@@ -103,6 +103,10 @@ def _refuse_camera_optimizer(model, who: str) -> None:
     if ctx is not None and getattr(ctx, "normal_loss", False):
         raise NotImplementedError(f"{who}: the last step carried the normal loss (config.use_normal_loss); the exchanges "
                                   "know the colour pass's gradient records only, not the normal pass's")
+    if ctx is not None and getattr(ctx, "normal_reg", False):
+        raise NotImplementedError(f"{who}: the last step carried the normal consistency or smoothness term "
+                                  "(config.use_normal_consistency / use_normal_tv); the exchanges know the colour pass's "
+                                  "gradient records only, not the normal pass's")
 
 
 def _checked_grad(model, who: str, compact: bool):

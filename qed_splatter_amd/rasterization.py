@@ -440,8 +440,8 @@ class _Composite(torch.autograd.Function):
                                           L.ptr(vsplat), L.ptr(tile_cost), L.ptr(order_ws), C_byref(post), flags, _stream()),
                     "qed_composite_bwd")
         for job in pending or ():
-            L.check(lib.qed_normal_rows_merge(C * N, L.ptr(job.rows), L.ptr(job.scale), L.ptr(vsplat), _stream()),
-                    "qed_normal_rows_merge")
+            merge = lib.qed_normal_rows_merge_depth if job.with_depth else lib.qed_normal_rows_merge
+            L.check(merge(C * N, L.ptr(job.rows), L.ptr(job.scale), L.ptr(vsplat), _stream()), "qed_normal_rows_merge")
         ctx.order_ws = order_ws                  # (tests read the launch order: render.grad_fn.order_ws)
         v3 = vsplat.view(C, N, R)
         v_means2d = v3[..., 0:2]

@@ -364,6 +364,17 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the normal loss's weight (default 0.1)")
     ap.add_argument("--normal-cosine-loss", action="store_true", default=argparse.SUPPRESS,
                     help="add the mean of 1 - n . g to the normal loss's L1 term")
+    ap.add_argument("--normal-consistency", action="store_true", default=argparse.SUPPRESS,
+                    help="tie the rendered normals to the normals of the rendered depth (config.use_normal_consistency; "
+                         "normals.py); needs no sensor normals; not with --camera-optimizer")
+    ap.add_argument("--normal-consistency-lambda", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="the consistency term's weight (default 0.05)")
+    ap.add_argument("--normal-consistency-from", type=int, default=argparse.SUPPRESS, metavar="STEP",
+                    help="the first step that carries the consistency term (default 0)")
+    ap.add_argument("--normal-tv", action="store_true", default=argparse.SUPPRESS,
+                    help="total variation of the rendered normals (config.use_normal_tv); not with --camera-optimizer")
+    ap.add_argument("--normal-tv-lambda", type=float, default=argparse.SUPPRESS, metavar="Y",
+                    help="the smoothness term's weight (default 0.1)")
     return ap
 
 
@@ -389,7 +400,14 @@ def main(argv=None) -> Dict:
                                     color_corrected_metrics=color_corrected,
                                     use_normal_loss=bool(getattr(a, "normal_loss", False)),
                                     normal_lambda=float(getattr(a, "normal_lambda", QEDSplatterModelConfig.normal_lambda)),
-                                    use_normal_cosine_loss=bool(getattr(a, "normal_cosine_loss", False)))
+                                    use_normal_cosine_loss=bool(getattr(a, "normal_cosine_loss", False)),
+                                    use_normal_consistency=bool(getattr(a, "normal_consistency", False)),
+                                    normal_consistency_lambda=float(getattr(
+                                        a, "normal_consistency_lambda", QEDSplatterModelConfig.normal_consistency_lambda)),
+                                    normal_consistency_from_step=int(getattr(a, "normal_consistency_from", 0)),
+                                    use_normal_tv=bool(getattr(a, "normal_tv", False)),
+                                    normal_tv_lambda=float(getattr(a, "normal_tv_lambda",
+                                                                   QEDSplatterModelConfig.normal_tv_lambda)))
     model = build_model(config, dm, a.init_from_ply, a.seed)
     print(f"seeded {model.num_points} Gaussians")
     trainer = Trainer(model, dm, seed=a.seed,
@@ -429,6 +447,9 @@ def main(argv=None) -> Dict:
         result["tv_loss"] = float(losses["tv_loss"]) if losses is not None else None
     if config.use_normal_loss:
         result["normal_loss"] = float(losses["normal_loss"]) if losses is not None else None
+    for flag, key in ((config.use_normal_consistency, "normal_consistency_loss"), (config.use_normal_tv, "normal_tv_loss")):
+        if flag:                                 # (None: no step carried the term, e.g. all before --normal-consistency-from)
+            result[key] = float(losses[key]) if (losses is not None and key in losses) else None
     if output_normals:
         trainer.model.config.output_normals = True      # (from here on: the final evaluation and --render-eval only)
     if color_corrected or output_normals:
