@@ -300,6 +300,32 @@ int qed_composite_bwd(int32_t C, int32_t N, const float* splats, const int32_t* 
                       const float* v_render, const float* v_alpha, float* vsplat, const int32_t* tile_cost, int32_t* order_ws,
                       const qed_post_grad_t* post, int32_t launch_flags, void* stream);
 
+/* ---- blending contribution of every Gaussian over a view (pruning; importance.hip) ---------------
+ * The walk of qed_composite_fwd over the same records, ids and offsets (same argument checks; flatten_ids may be NULL
+ * when the list is empty) without colours and without per-pixel outputs.  At a pixel that is inside the image and
+ * whose pixel_mask[C,H,W] byte (may be NULL = all set) is not 0, Gaussian i CONTRIBUTES where the forward pass applies
+ * it: it passes the alpha test (sigma >= 0, alpha = min(.999, o e^-sigma) >= 1/255), the pixel has not terminated and
+ * T (1 - alpha) > 1e-4; its weight is w = alpha T_before.  The Gaussian that terminates a pixel is not applied by the
+ * renderer and has w = 0 there.  Records c * N + n of every camera c land on row n of three [N] buffers that
+ * ACCUMULATE across calls (the caller zeroes them once):
+ *   max_weight  the bit pattern of a non-negative float: max w (an unsigned integer max is the float max)
+ *   sum_weight  unsigned 64-bit fixed point with 32 fractional bits: sum w.  Capacity 2^32 units of weight per
+ *               Gaussian (every pixel of 2 000 views at 1920x1080 at alpha 0.999); not guarded
+ *   hits        #{(view, pixel) : w > 0}
+ * All three are integers updated with order-independent atomics (the sum of one (tile, Gaussian) is formed in a fixed
+ * lane order in float and converted once, round to nearest): the same bits on every run, for any order of views.
+ * N == 0 or an empty list leaves the buffers untouched.  launch_flags: QED_CL_NO_CULL is honoured (identical results);
+ * the launch-shape bits are ignored (always one wave per tile). */
+int qed_contribution(int32_t C, int32_t N, const float* splats, const int32_t* flatten_ids, const int32_t* offsets,
+                     int32_t width, int32_t height, int32_t tile_w, int32_t tile_h, const uint8_t* pixel_mask /* [C,H,W] or NULL */,
+                     uint32_t* max_weight, uint64_t* sum_weight, uint32_t* hits, int32_t launch_flags, void* stream);
+
+/* Keep flags and slots of a prune, in the form qed_densify_emit reads: row i is kept when score[i] > min_score, or
+ * score[i] == min_score and i < tie_below (ties by row index; a NaN score is never kept).  flags[N] receives 4 (keep the
+ * old row) or 0, pos (qed_densify_pos_ints(N) ints) the slot of every kept row in column 1, totals[4] = {0, K, 0, 0}. */
+int qed_prune_classify(int32_t N, const double* score, double min_score, int32_t tie_below, uint8_t* flags,
+                       int32_t* pos, int32_t* totals, void* stream);
+
 /* ---- K8: fused image-space loss + gradient ------------------------------------------------------
  * Collapses model.py:295-297 (background composite + clamp), :304-306 (depth fix-up), :87-116
  * (masked depth-L1, depth_lambda) and the L1 part of the parent's RGB loss into one pass.

@@ -880,7 +880,9 @@ class QEDSplatterModel(nn.Module):
                 _flags=flags, _sh_rest=sh_rest, _sync=not (self.config.async_intersection_count and self.training),
                 _c2w=(c2w, intr) if c2w is not None else None, _post_background=bg, _handover=handover,
                 _means2d_leaf=True,     # xys is only retained and read (below; densify.py): its gradient arrives as a view
-                _capture_slot=capture_slot, _manual=manual, _keep_records=want_normals or want_npass, _post_bwd=quat_sink,
+                # (_score_records: prune.score_views walks this call's lists once more)
+                _capture_slot=capture_slot, _manual=manual,
+                _keep_records=want_normals or want_npass or bool(attrs.get("_score_records")), _post_bwd=quat_sink,
                 # (a captured backward pass always writes the compact form; _SegmentFn.backward asks per replay)
                 _lazy_sh=self._lazy_sh_begin if (lazy and manual is None) else None)
 

@@ -4,6 +4,8 @@
                                      [--export-ply splat.ply [--export-frame dataset]] [--render-eval DIR]
                                      [--camera-optimizer SO3xR3 [--camera-opt-lr 1e-4] [--save-poses poses.json]]
                                      [--use-bilateral-grid [--grid-shape 16 16 8]] [--color-corrected-metrics]
+                                     [--prune-at STEP [STEP ...] [--prune-min-score X | --prune-keep-fraction F]
+                                      [--prune-score max|sum] [--prune-view-stride S]]
 
 The dataset is read by ``dataparser.parse_dataset``, cached by ``datamanager.FullImageDatamanager`` (uint8 images on
 the GPU), and every step takes the next training camera and its frame through the eager fused route: ``fused_loss``
@@ -20,6 +22,10 @@ and one launch, qed_bilagrid_step, for their TV gradient and Adam step).  Evalua
 ``--color-corrected-metrics`` (splatfacto's color_corrected_metrics) adds, under ``"eval_images"``, the evaluation split's
 psnr / ssim / lpips and the same three of every render colour-corrected towards its ground truth (``Trainer.evaluate_images``,
 color_correct.py) -- the figures that do not measure the cameras' exposure differences.
+
+``--prune-at`` scores every Gaussian by its blending contribution over the training cameras after the named steps'
+refinement and drops the low scorers from the model and the optimiser (prune.py, csrc/importance.hip); the last JSON line
+then carries ``"prune": [{"step", "n_before", "n_after", "seconds"}]``.
 
 The Gaussians are seeded from the dataset's ``ply_file_path`` (``--init-from-ply`` overrides it) in the frame of the
 cameras, or from random points when there is none.  Every ``--eval-every`` steps and at the end the evaluation split
@@ -95,6 +101,22 @@ class Trainer:
             self.densifier.refinement_after(step)
         self.step = step + 1
         return losses
+
+    def prune(self, config, view_stride: int = 1) -> Dict:
+        """Score the training cameras (every ``view_stride``-th, in evaluation mode, the dataset's masks as pixel masks) and
+        drop the low scorers from the model and the optimiser (prune.py); the densifier's running statistics are cleared.
+        Returns prune.prune's dict with ``seconds``."""
+        from .prune import prune, score_views
+        items = list(self.datamanager.train_items())
+        masks = [b["mask"] if "mask" in b else None for _, b in items]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        scores = score_views(self.model, [cam for cam, _ in items], masks if any(m is not None for m in masks) else None,
+                             view_stride)
+        info = prune(self.model, self.optimizer, scores, config, densifier=self.densifier)
+        torch.cuda.synchronize()
+        info["seconds"] = time.perf_counter() - t0
+        return info
 
     @torch.no_grad()
     def evaluate(self) -> Dict[str, float]:
@@ -375,7 +397,30 @@ def build_parser() -> argparse.ArgumentParser:
                     help="total variation of the rendered normals (config.use_normal_tv); not with --camera-optimizer")
     ap.add_argument("--normal-tv-lambda", type=float, default=argparse.SUPPRESS, metavar="Y",
                     help="the smoothness term's weight (default 0.1)")
+    ap.add_argument("--prune-at", type=int, nargs="+", default=argparse.SUPPRESS, metavar="STEP",
+                    help="after these steps' refinement: score the training cameras and prune by blending contribution "
+                         "(prune.py)")
+    ap.add_argument("--prune-min-score", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="rows whose score is below X go (default 0.01 with --prune-score max)")
+    ap.add_argument("--prune-keep-fraction", type=float, default=argparse.SUPPRESS, metavar="F",
+                    help="keep the best ceil(F N) rows instead")
+    ap.add_argument("--prune-score", choices=("max", "sum"), default=argparse.SUPPRESS)
+    ap.add_argument("--prune-view-stride", type=int, default=argparse.SUPPRESS, metavar="S", help="score every S-th camera")
     return ap
+
+
+def prune_config_of(a):
+    """The PruneConfig of the --prune-* options (None without --prune-at)."""
+    if not getattr(a, "prune_at", None):
+        return None
+    from .prune import PruneConfig
+    score = getattr(a, "prune_score", "max")
+    min_score, keep = getattr(a, "prune_min_score", None), getattr(a, "prune_keep_fraction", None)
+    if min_score is not None and keep is not None:
+        raise SystemExit("--prune-min-score and --prune-keep-fraction: give one")
+    if min_score is None and keep is None and score != "max":
+        raise SystemExit("--prune-score sum needs --prune-min-score or --prune-keep-fraction")
+    return PruneConfig(score=score, min_score=0.01 if min_score is None else float(min_score), keep_fraction=keep)
 
 
 def main(argv=None) -> Dict:
@@ -416,12 +461,18 @@ def main(argv=None) -> Dict:
         trainer.resume(a.resume)
         print(f"resumed {a.resume} at step {trainer.step} with {trainer.model.num_points} Gaussians")
     metrics: Dict[str, float] = {}
+    prune_config, prune_log = prune_config_of(a), []
     first = trainer.step
     torch.cuda.synchronize()
     t0 = time.time()
     losses = None
     while trainer.step < a.steps:
         losses = trainer.train_step()
+        if prune_config is not None and trainer.step - 1 in a.prune_at:
+            info = trainer.prune(prune_config, int(getattr(a, "prune_view_stride", 1)))
+            prune_log.append({"step": trainer.step - 1, "n_before": info["n_before"], "n_after": info["n_after"],
+                              "seconds": info["seconds"]})
+            print(f"step {trainer.step - 1}: pruned {info['n_pruned']} of {info['n_before']} Gaussians", flush=True)
         if a.eval_every and trainer.step % a.eval_every == 0 and trainer.step < a.steps:
             metrics = trainer.evaluate()
             print(f"step {trainer.step}: " + ", ".join(f"{k} {v:.5g}" for k, v in metrics.items()), flush=True)
@@ -441,6 +492,8 @@ def main(argv=None) -> Dict:
     done = trainer.step - first
     result = {"steps": trainer.step, "steps_per_s": done / elapsed if elapsed > 0 and done else 0.0,
               "eval": metrics, "gaussian_count": trainer.model.num_points}
+    if prune_config is not None:
+        result["prune"] = prune_log
     if trainer.camera_optimizer is not None:
         result["camera_opt"] = trainer.camera_opt_metrics()
     if trainer.grid_optimizer is not None:
