@@ -376,86 +376,94 @@ __device__ __forceinline__ void fwd_tile(int tile, int qf, float (*s_rec)[kRecFl
         px[q].out23 = (f2){0.f, 0.f};
     }
 
-    // Two-deep software pipeline over the batches: while batch b is composited the records of b+1 and the ids of b+2
-    // are in flight (fetched back to back, the id -> record dependency cost one exposed memory latency per batch).
-    // Every load is UNCONDITIONAL from a clamped index (lanes past the end re-read the tile's last entry: one cache
-    // line) into registers of its own that are rotated in at the end of the batch: a load under a per-lane
-    // condition is merged with the old value right behind it, which makes the wave wait for it on the spot.
-    auto id_at = [&](int idx) { return flatten_ids[idx < end ? idx : end - 1]; };
-    int rid_n = id_at(start + kBatch + lane);
-    float4 r0, r1;
-    f3 r2;
-    {
-        const size_t g = (size_t)id_at(start + lane);
-        r0 = splats[3 * g]; r1 = splats[3 * g + 1]; r2 = load_rec_tail(splats, g);
-    }
-    bool present = start + lane < end;
-    auto and_done = [&]() { u64 m = ~0ull;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) m &= done[q];
-        return m; };
-    auto or_masks = [&](const u64* mq) { u64 m = 0;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) m |= mq[q];
-        return m; };
-    bool all_done = and_done() == ~0ull;
-    for (int b = 0; b < nb && !all_done; ++b) {
-        // ---- stage this lane's Gaussian: cull per quadrant, pre-scale the conic by -log2(e) ----
-        u64 mq[NQ];
-        quadrant_masks<NQ>(present, r0, r1, r2.z, ox, oy, qf, mq);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) mq[q] = done[q] == ~0ull ? 0ull : uniform_u64(mq[q]);
-        u64 km = or_masks(mq);
-        QED_STAT(0, 1); QED_STAT(1, min(kBatch, end - (start + b * kBatch))); QED_STAT(2, __builtin_popcountll(km));
-        // which per-pixel form this Gaussian takes (see fwd_quadrant); the record carries log2(opacity) for the fast one
-        const bool fast = gaussian_is_fast(r0.z, r0.w, r1.x, r1.y);
-        const u64 m_slow = uniform_u64(__ballot(!fast));
-        if (km) {                                       // park this lane's (pre-scaled) Gaussian for the broadcast reads:
-            const float bh = kConicScale * r0.w;        // {x, y, k a, k b | k b, k c, r, g | b, depth, opacity or its log2, -}
-            *reinterpret_cast<float4*>(&s_rec[lane][0]) = make_float4(r0.x, r0.y, kConicScale * r0.z, bh);
-            *reinterpret_cast<float4*>(&s_rec[lane][4]) = make_float4(bh, kConicScale * r1.x, r1.z, r1.w);
-            *reinterpret_cast<float4*>(&s_rec[lane][8]) = make_float4(r2.x, r2.y, fast ? __builtin_amdgcn_logf(r1.y) : r1.y, 0.f);
+    // An EMPTY tile (wave-uniform: end <= start) takes none of what follows up to the stores: it reads neither the list --
+    // flatten_ids may be NULL when the sorted list is empty, and for a run that ends at offset 0 the clamped index below
+    // would be -1, the word in front of the caller's buffer -- nor any record; like bwd_tile and importance.hip, which
+    // return before their first list read.  The stores below then write the tile from the pixel state as initialised above
+    // (T = 1, nothing accumulated, id 0) and from nb = n_vis = 0: background, alpha 0, T_final 1, last id 0, the
+    // post-processing outputs of an untouched pixel, cost 0.
+    if (end > start) {
+        // Two-deep software pipeline over the batches: while batch b is composited the records of b+1 and the ids of b+2
+        // are in flight (fetched back to back, the id -> record dependency cost one exposed memory latency per batch).
+        // Every load is UNCONDITIONAL from a clamped index (lanes past the end re-read the tile's last entry: one cache
+        // line) into registers of its own that are rotated in at the end of the batch: a load under a per-lane
+        // condition is merged with the old value right behind it, which makes the wave wait for it on the spot.
+        auto id_at = [&](int idx) { return flatten_ids[idx < end ? idx : end - 1]; };
+        int rid_n = id_at(start + kBatch + lane);
+        float4 r0, r1;
+        f3 r2;
+        {
+            const size_t g = (size_t)id_at(start + lane);
+            r0 = splats[3 * g]; r1 = splats[3 * g + 1]; r2 = load_rec_tail(splats, g);
         }
-        __syncthreads();                                // single wave: orders the stores before the reads below
-        // issue the gather of the next batch (its ids arrived a batch ago) and the id load of the one after
-        const size_t g_n = (size_t)rid_n;
-        const float4 n0 = splats[3 * g_n], n1 = splats[3 * g_n + 1];
-        const f3 n2 = load_rec_tail(splats, g_n);
-        const int rid_nn = id_at(start + (b + 2) * kBatch + lane);
-        const int batch_start = start + b * kBatch;
-        // the walk over the batch's survivors (fwd_walk): two copies -- a batch whose Gaussians all take the fast form
-        // (every batch of an ordinary scene) runs without any per-visit test of the form
+        bool present = start + lane < end;
+        auto and_done = [&]() { u64 m = ~0ull;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) m &= done[q];
+            return m; };
+        auto or_masks = [&](const u64* mq) { u64 m = 0;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) m |= mq[q];
+            return m; };
+        bool all_done = and_done() == ~0ull;
+        for (int b = 0; b < nb && !all_done; ++b) {
+            // ---- stage this lane's Gaussian: cull per quadrant, pre-scale the conic by -log2(e) ----
+            u64 mq[NQ];
+            quadrant_masks<NQ>(present, r0, r1, r2.z, ox, oy, qf, mq);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) mq[q] = done[q] == ~0ull ? 0ull : uniform_u64(mq[q]);
+            u64 km = or_masks(mq);
+            QED_STAT(0, 1); QED_STAT(1, min(kBatch, end - (start + b * kBatch))); QED_STAT(2, __builtin_popcountll(km));
+            // which per-pixel form this Gaussian takes (see fwd_quadrant); the record carries log2(opacity) for the fast one
+            const bool fast = gaussian_is_fast(r0.z, r0.w, r1.x, r1.y);
+            const u64 m_slow = uniform_u64(__ballot(!fast));
+            if (km) {                                   // park this lane's (pre-scaled) Gaussian for the broadcast reads:
+                const float bh = kConicScale * r0.w;    // {x, y, k a, k b | k b, k c, r, g | b, depth, opacity or its log2, -}
+                *reinterpret_cast<float4*>(&s_rec[lane][0]) = make_float4(r0.x, r0.y, kConicScale * r0.z, bh);
+                *reinterpret_cast<float4*>(&s_rec[lane][4]) = make_float4(bh, kConicScale * r1.x, r1.z, r1.w);
+                *reinterpret_cast<float4*>(&s_rec[lane][8]) = make_float4(r2.x, r2.y, fast ? __builtin_amdgcn_logf(r1.y) : r1.y, 0.f);
+            }
+            __syncthreads();                            // single wave: orders the stores before the reads below
+            // issue the gather of the next batch (its ids arrived a batch ago) and the id load of the one after
+            const size_t g_n = (size_t)rid_n;
+            const float4 n0 = splats[3 * g_n], n1 = splats[3 * g_n + 1];
+            const f3 n2 = load_rec_tail(splats, g_n);
+            const int rid_nn = id_at(start + (b + 2) * kBatch + lane);
+            const int batch_start = start + b * kBatch;
+            // the walk over the batch's survivors (fwd_walk): two copies -- a batch whose Gaussians all take the fast form
+            // (every batch of an ordinary scene) runs without any per-visit test of the form
 #if QED_K6_FORM == 2
-        if (m_slow == 0) fwd_walk<CH, NQ, false>(km, mq, pg, px, done, batch_start, m_slow, n_vis, s_rec);
-        else fwd_walk<CH, NQ, true>(km, mq, pg, px, done, batch_start, m_slow, n_vis, s_rec);
+            if (m_slow == 0) fwd_walk<CH, NQ, false>(km, mq, pg, px, done, batch_start, m_slow, n_vis, s_rec);
+            else fwd_walk<CH, NQ, true>(km, mq, pg, px, done, batch_start, m_slow, n_vis, s_rec);
 #elif QED_K6_FORM == 4
-        if (__builtin_expect(m_slow == 0, 1)) {
-            fwd_walk<CH, NQ, false>(km, mq, pg, px, done, batch_start, m_slow, n_vis, s_rec);
-        } else {
-            // a batch with a slow-form Gaussian (rare): the walk that tests the form per Gaussian is an OUT-OF-LINE function
-            // on a COPY of the state -- inlined beside the fast walk it costs the hot loop its scalar registers, and handing
-            // it the state itself would pin that state in memory for the whole kernel
-            FwdWalkState<NQ> st;
-            st.km = km; st.n_vis = n_vis;
-            st.pg = pg;
+            if (__builtin_expect(m_slow == 0, 1)) {
+                fwd_walk<CH, NQ, false>(km, mq, pg, px, done, batch_start, m_slow, n_vis, s_rec);
+            } else {
+                // a batch with a slow-form Gaussian (rare): the walk that tests the form per Gaussian is an OUT-OF-LINE
+                // function on a COPY of the state -- inlined beside the fast walk it costs the hot loop its scalar registers,
+                // and handing it the state itself would pin that state in memory for the whole kernel
+                FwdWalkState<NQ> st;
+                st.km = km; st.n_vis = n_vis;
+                st.pg = pg;
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) { st.mq[q] = mq[q]; st.done[q] = done[q]; st.px[q] = px[q]; }
-            fwd_walk_mixed<CH, NQ>(&st, batch_start, m_slow, s_rec);
-            km = uniform_u64(st.km); n_vis = __builtin_amdgcn_readfirstlane(st.n_vis);
+                for (int q = 0; q < NQ; ++q) { st.mq[q] = mq[q]; st.done[q] = done[q]; st.px[q] = px[q]; }
+                fwd_walk_mixed<CH, NQ>(&st, batch_start, m_slow, s_rec);
+                km = uniform_u64(st.km); n_vis = __builtin_amdgcn_readfirstlane(st.n_vis);
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) { mq[q] = uniform_u64(st.mq[q]); done[q] = uniform_u64(st.done[q]); px[q] = st.px[q]; }
-            // the loads of this copy-back retire HERE: left pending at the join, the fast path inherits "a register of the
-            // walk may still be the target of a load" and its first Gaussian waits for vmcnt(1) -- the counter retires in
-            // order, so that is the next batch's gather (s_waitcnt vmcnt(0), expcnt / lgkmcnt untouched)
-            __builtin_amdgcn_s_waitcnt(0x0F70);
-        }
+                for (int q = 0; q < NQ; ++q) { mq[q] = uniform_u64(st.mq[q]); done[q] = uniform_u64(st.done[q]); px[q] = st.px[q]; }
+                // the loads of this copy-back retire HERE: left pending at the join, the fast path inherits "a register of
+                // the walk may still be the target of a load" and its first Gaussian waits for vmcnt(1) -- the counter
+                // retires in order, so that is the next batch's gather (s_waitcnt vmcnt(0), expcnt / lgkmcnt untouched)
+                __builtin_amdgcn_s_waitcnt(0x0F70);
+            }
 #else
-        fwd_walk<CH, NQ, true>(km, mq, pg, px, done, batch_start, m_slow, n_vis, s_rec);
+            fwd_walk<CH, NQ, true>(km, mq, pg, px, done, batch_start, m_slow, n_vis, s_rec);
 #endif
-        all_done = and_done() == ~0ull;                 // (a finished quadrant empties its mask, so km ran out by itself)
-        r0 = n0; r1 = n1; r2 = n2;                      // rotate the pipeline (the wave waits HERE, not above)
-        rid_n = rid_nn;
-        present = start + (b + 1) * kBatch + lane < end;
+            all_done = and_done() == ~0ull;             // (a finished quadrant empties its mask, so km ran out by itself)
+            r0 = n0; r1 = n1; r2 = n2;                  // rotate the pipeline (the wave waits HERE, not above)
+            rid_n = rid_nn;
+            present = start + (b + 1) * kBatch + lane < end;
+        }
     }
     float post_dmax = -3.0e38f;
 #pragma unroll
