@@ -71,7 +71,7 @@ extern "C" {
  *      formed at double precision, as the host-state path forms them.
  * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_gaussian_normals,
  * qed_normal_maps, qed_depth_normals, qed_angular_error; qed_normal_loss, qed_gaussian_normals_bwd, qed_normal_rows_merge;
- * qed_normal_consistency, qed_normal_rows_merge_depth). */
+ * qed_normal_consistency, qed_normal_rows_merge_depth; qed_depth_loss). */
 #define QED_ABI_VERSION 4
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
@@ -1140,6 +1140,62 @@ int qed_normal_consistency(int32_t height, int32_t width, const float* accum, in
                            double* workspace, float* v_accum, int32_t v_accum_stride, float* v_depth, int32_t v_depth_stride,
                            float* v_alpha, double* out, float* out_f, void* stream);
 int qed_normal_rows_merge_depth(int64_t total, const float* normal_rows, const float* scale, float* rows, void* stream);
+
+/* ---- robust depth losses and depth smoothness in training (csrc/depth_loss.hip) ------------------------------------------------
+ * A family of data terms and an edge-aware smoothness term on the rendered depth.  THIS PROJECT'S definitions, in the spirit of
+ * DN-Splatter's depth losses, not checked against it and not in the reference (which keeps the L1 term of qed_loss_grad).
+ * Per pixel p = (i, j) of one camera's step, everything in the model's units (after the dataparser's scale):
+ *   d(p)  = the depth get_outputs returns: the accumulated depth channel and, where alpha == 0, the channel's maximum,
+ *           detached (qed_loss_grad's dmax: fmaxf over the channel, so a NaN is skipped);
+ *   g(p)  = the sensor depth, m(p) = the float mask (1 without one), I = the ground-truth colour [H,W,3];
+ *   a = d m, b = g m, V = {p : finite(a), finite(b), b > 0} (the reference's validity), r = |a - b|;
+ *   gx(p) = mean over c of |I(i, j+1, c) - I(i, j, c)|, gy(p) = mean over c of |I(i+1, j, c) - I(i, j, c)|: forward
+ *           differences, 0 in the last column / row;
+ *   depth_loss = depth_lambda * sum over V of w(p) rho(r) / max(|V|, 1), 0 when V is empty, with
+ *           QED_DL_L1 rho = r | QED_DL_MSE r^2 | QED_DL_LOGL1 log1p(r) | QED_DL_HUBER r^2 / (2 delta) for r <= delta, else
+ *           r - delta / 2 (a FIXED delta) | QED_DL_EDGE_LOGL1 log1p(r) with w = (exp(-gx) + exp(-gy)) / 2; w = 1 otherwise;
+ *   d depth_loss / d d(p) = depth_lambda w rho'(r) sign(a - b) m / |V| on V, exactly 0 elsewhere; sign(0) = 0; with
+ *           QED_DL_FIXUP also exactly 0 where alpha == 0 (the maximum is detached);
+ *   an x-pair (p, p + x) exists for j < W - 1 and is valid iff both pixels have alpha > 0, a finite d and m != 0;
+ *   E_x = sum over the valid x-pairs of omega_x(p) |d(p + x) - d(p)|, omega_x = exp(-gx(p)) with QED_DL_TV_EDGE, else 1;
+ *           N_x their number; E_y, omega_y, N_y the same along y;
+ *   depth_tv_loss = tv_lambda * (E_x / max(N_x, 1) + E_y / max(N_y, 1)): on d, not d m, and without the sensor depth.
+ * alpha, g, m and I are constants.
+ *
+ * qed_depth_loss: one image.  d is read at depth[p * depth_stride] (channel 3 of an [H,W,4] render has stride 4).  With
+ *   QED_DL_FIXUP `depth` is the raw channel and the entry forms d itself from alpha[H,W] and the maximum -- dmax[0] (device;
+ *   qed_loss_grad's sums[3]) or, with dmax NULL, one more launch of its own; without it `depth` is d as get_outputs returned
+ *   it.  alpha may be NULL without the fix-up and QED_DL_TV; gt_rgb without an edge-aware term; gt_depth without QED_DL_DATA.
+ *   flags: the terms QED_DL_DATA, QED_DL_TV (+ QED_DL_TV_EDGE) -- a term that is off has value 0 and no gradient -- and the
+ *   passes.  QED_DL_REDUCE: one streaming launch leaves per-workgroup sums in `workspace` (QED_DEPTH_LOSS_WS_DOUBLES doubles,
+ *   no zeroing needed); alone it is followed by a one-workgroup fold that writes out[8] (device doubles) = {depth_loss,
+ *   depth_tv_loss, |V|, N_x, N_y, E_x, E_y, the maximum used (0 without the fix-up)} and out_f[3] (device floats, may be NULL)
+ *   = {depth_loss, depth_tv_loss, loss_base[0] + their sum} (loss_base: a device float, NULL = 0: the fused step's total rides
+ *   along without a launch of its own).  QED_DL_GRAD: one launch, after a reduce pass on the same inputs and the SAME
+ *   workspace -- in the same call or an earlier one --; every workgroup folds the workspace itself, so the denominators never
+ *   reach the host, and with both passes in one call the gradient launch writes out / out_f too (two launches in all).
+ *   It writes the FULLY SCALED d (g_data depth_loss + g_tv depth_tv_loss) / d d(p) to v_depth[p * v_depth_stride], every
+ *   pixel, zero where nothing arrives.  g_data, g_tv: the upstream gradients, device floats, NULL = 1.
+ *   No floating-point atomics: a pixel's smoothness gradient is gathered, in a fixed order, from the up to four pairs it
+ *   belongs to; sums are carried in double and folded in a fixed order -- the same input gives the same bits.
+ *   height * width == 0 writes zeros to out. */
+#define QED_DEPTH_LOSS_WS_DOUBLES (6 * 256 + 136)
+#define QED_DL_L1 0
+#define QED_DL_MSE 1
+#define QED_DL_LOGL1 2
+#define QED_DL_HUBER 3
+#define QED_DL_EDGE_LOGL1 4
+#define QED_DL_DATA 1u
+#define QED_DL_TV 2u
+#define QED_DL_TV_EDGE 4u
+#define QED_DL_FIXUP 8u
+#define QED_DL_REDUCE 16u
+#define QED_DL_GRAD 32u
+int qed_depth_loss(int32_t height, int32_t width, const float* depth, int32_t depth_stride, const float* alpha,
+                   const float* dmax, const float* gt_depth, const float* mask, const float* gt_rgb, int32_t type,
+                   float depth_lambda, float huber_delta, float tv_lambda, uint32_t flags, const float* g_data,
+                   const float* g_tv, const float* loss_base, double* workspace, float* v_depth, int32_t v_depth_stride,
+                   double* out, float* out_f, void* stream);
 
 /* ---- oriented surface samples of one rendered view (csrc/surface.hip) -------------------------------------------------------
  * The planes get_outputs returns in evaluation mode with output_normals, back-projected into a compact list of world points

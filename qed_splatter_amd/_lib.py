@@ -126,6 +126,8 @@ SIGNATURES = {
     "qed_normal_consistency": (C.c_int, [_I, _I, _P, _I, _P, _P, _I, _F, _F, _F, _F, _F, _P, _F, _F, _U, _P, _P, _P, _P, _P,
                                          _P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "qed_normal_rows_merge_depth": (C.c_int, [_L, _P, _P, _P, _P]),
+    "qed_depth_loss": (C.c_int, [_I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _F, _F, _F, _U, _P, _P, _P, _P, _P, _I, _P, _P,
+                                 _P]),
     "qed_voxel_attr_workspace_bytes": (_L, [_L, _I]),
     "qed_voxel_down_sample_attr": (C.c_int, [_I, _P, _I, _P, _P, _F, _P, _P, _P, _P, _P, _L, _P, _P]),
     "qed_surface_workspace_ints": (_L, [_I, _I, _I]),
@@ -165,6 +167,9 @@ ANGULAR_WS_DOUBLES = 5 * 1024              # QED_ANGULAR_WS_DOUBLES
 NORMAL_LOSS_WS_DOUBLES = 3 * 1024          # QED_NORMAL_LOSS_WS_DOUBLES
 NORMAL_CONSISTENCY_WS_DOUBLES = 6 * 1024   # QED_NORMAL_CONSISTENCY_WS_DOUBLES
 NC_CONSISTENCY, NC_TV, NC_REDUCE, NC_GRAD = 1, 2, 4, 8   # QED_NC_*
+DEPTH_LOSS_WS_DOUBLES = 6 * 256 + 136      # QED_DEPTH_LOSS_WS_DOUBLES
+DEPTH_LOSS_TYPES = {"L1": 0, "MSE": 1, "LogL1": 2, "HuberL1": 3, "EdgeAwareLogL1": 4}   # QED_DL_L1 .. QED_DL_EDGE_LOGL1
+DL_DATA, DL_TV, DL_TV_EDGE, DL_FIXUP, DL_REDUCE, DL_GRAD = 1, 2, 4, 8, 16, 32   # QED_DL_*
 NORMALS_WORLD, NORMALS_CAMERA = 0, 1       # QED_NORMALS_WORLD, QED_NORMALS_CAMERA
 NV_NORMAL, NV_DEPTH_NORMAL = 1, 2          # QED_NV_NORMAL, QED_NV_DEPTH_NORMAL
 SURFACE_NORMAL_RENDERED, SURFACE_NORMAL_DEPTH = 0, 1   # QED_SURFACE_NORMAL_RENDERED, QED_SURFACE_NORMAL_DEPTH

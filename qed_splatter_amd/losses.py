@@ -1,8 +1,9 @@
 """The image losses of a training step as autograd nodes over the loss kernels: the stand-alone SSIM (``ssim``), the
 statements around the operator (``_PostProcess``), get_loss_dict's two terms (``_ImageLosses``), the fused step's K8 node
-(``_FusedImageLoss``), splatfacto's MCMC regularisers (``_McmcReg``), the normal loss (``_NormalLoss``) and the normal
-consistency and smoothness terms (``_NormalConsistency``), with the helpers that prepare their inputs and scratch buffers.  Nothing in here touches the model: ``model.py`` and ``metrics.py`` call in, this module imports the
-library binding only."""
+(``_FusedImageLoss``), splatfacto's MCMC regularisers (``_McmcReg``), the normal loss (``_NormalLoss``), the normal
+consistency and smoothness terms (``_NormalConsistency``) and the robust depth and depth smoothness terms (``_DepthLoss``,
+``depth_terms``), with the helpers that prepare their inputs and scratch buffers.  Nothing in here touches the model:
+``model.py`` and ``metrics.py`` call in, this module imports the library binding only."""
 from __future__ import annotations
 
 import os
@@ -229,8 +230,13 @@ class _FusedImageLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, render, alpha, background, gt_rgb, gt_depth, mask, ssim_lambda, depth_lambda, handover=None, tick=None,
-                tile_cost=None):
+                tile_cost=None, depth_terms=None):
         import ctypes
+        # depth_terms (a DepthTerms; None = the built-in depth-L1 term): K8 runs with depth_lambda = 0 -- it then writes zeros
+        # to channel 3 of v_render -- and qed_depth_loss' two launches follow it: they put the depth gradient there and add
+        # their two values to K8's total, on the device.  A third output, float32 [3] = {depth_loss, depth_tv_loss, total}
+        if depth_terms is not None:
+            depth_lambda = 0.0
         lib = L.load()
         ctx.set_materialize_grads(False)
         C, H, W, CH = render.shape
@@ -283,19 +289,29 @@ class _FusedImageLoss(torch.autograd.Function):
         ctx.save_for_backward(v_render, v_alpha)
         total = losses[2:3].view(())
         parts = losses[0:2]
+        if depth_terms is not None:
+            assert CH == 4, "the depth terms need the depth channel"
+            ws, dparts, out_f = _depth_loss_buffers(dev)
+            L.check(lib.qed_depth_loss(H, W, render.data_ptr() + 12, 4, L.ptr(alpha), sums.data_ptr() + 12, L.ptr(gt_depth),
+                                       L.ptr(mask), L.ptr(gt_rgb), *depth_terms.scalars(),
+                                       depth_terms.flags | L.DL_FIXUP | L.DL_REDUCE | L.DL_GRAD, None, None,
+                                       losses.data_ptr() + 8, L.ptr(ws), v_render.data_ptr() + 12, 4, L.ptr(dparts),
+                                       L.ptr(out_f), st), "qed_depth_loss")
+            ctx.mark_non_differentiable(parts, out_f)
+            return out_f[2:3].view(()), parts, out_f
         ctx.mark_non_differentiable(parts)
         return total, parts
 
     @staticmethod
-    def backward(ctx, v_total, _v_parts):
+    def backward(ctx, v_total, *_v_parts):
         if v_total is None:
-            return (None,) * 11
+            return (None,) * 12
         v_render, v_alpha = ctx.saved_tensors
         # the kernel wrote d(total)/d(render, alpha).  The usual upstream gradient is the cached unit tensor of
         # backward_fused() and needs no scaling pass; anything else (a weighted loss, a GradScaler) is applied
         if v_total.data_ptr() != _unit_grad(v_total.device).data_ptr():
             v_render, v_alpha = v_render * v_total, v_alpha * v_total
-        return (v_render, v_alpha) + (None,) * 9
+        return (v_render, v_alpha) + (None,) * 10
 
 
 def _mcmc_reg_values(opacities: Tensor, scales: Tensor, lo: float, ls: float) -> Tensor:
@@ -483,3 +499,100 @@ class _NormalConsistency(torch.autograd.Function):
         if v_depth is not None:
             v_depth = v_depth.reshape(ctx.depth_shape)
         return (v_image, v_alpha, v_depth) + (None,) * 8
+
+
+class DepthTerms:
+    """The robust depth data term and the depth smoothness term of one step, as the kernels take them (depth_terms())."""
+    __slots__ = ("type_id", "depth_lambda", "huber_delta", "tv_lambda", "tv_edge")
+
+    def __init__(self, type_id: int, depth_lambda: float, huber_delta: float, tv_lambda: float, tv_edge: bool):
+        self.type_id, self.depth_lambda, self.huber_delta = int(type_id), float(depth_lambda), float(huber_delta)
+        self.tv_lambda, self.tv_edge = float(tv_lambda), bool(tv_edge)
+
+    @property
+    def flags(self) -> int:
+        tv = (L.DL_TV | (L.DL_TV_EDGE if self.tv_edge else 0)) if self.tv_lambda > 0.0 else 0
+        return L.DL_DATA | tv
+
+    def scalars(self):
+        """(type, depth_lambda, huber_delta, tv_lambda): the constants of a qed_depth_loss call, in its order."""
+        return self.type_id, self.depth_lambda, self.huber_delta, self.tv_lambda
+
+
+def depth_terms(cfg):
+    """config.depth_loss_type / depth_huber_delta / depth_tv_lambda / depth_tv_edge_aware checked, before any launch of a
+    step: None for the default (type "L1" without the smoothness term: the built-in kernels' depth term and nothing else),
+    else the DepthTerms that replace it -- the built-in kernels are then handed depth_lambda = 0."""
+    name = getattr(cfg, "depth_loss_type", "L1")
+    if name not in L.DEPTH_LOSS_TYPES:
+        raise ValueError(f"depth_loss_type {name!r}: the offered types are {', '.join(L.DEPTH_LOSS_TYPES)}")
+    delta = float(getattr(cfg, "depth_huber_delta", 0.1))
+    if not (delta > 0.0 and delta < float("inf")):
+        raise ValueError(f"depth_huber_delta must be a positive number (in the model's units), not {delta}")
+    tv = float(getattr(cfg, "depth_tv_lambda", 0.0))
+    if not (tv >= 0.0 and tv < float("inf")):
+        raise ValueError(f"depth_tv_lambda must be >= 0 (0 = off), not {tv}")
+    if name == "L1" and tv == 0.0:
+        return None
+    if not cfg.output_depth_during_training:
+        raise NotImplementedError("depth_loss_type other than 'L1' or depth_tv_lambda > 0 with "
+                                  "output_depth_during_training=False: both terms are taken on the rendered depth")
+    return DepthTerms(L.DEPTH_LOSS_TYPES[name], cfg.depth_lambda, delta, tv, getattr(cfg, "depth_tv_edge_aware", True))
+
+
+def _depth_loss_buffers(dev):
+    ws = torch.empty(L.DEPTH_LOSS_WS_DOUBLES, dtype=torch.float64, device=dev)
+    parts = torch.empty(8, dtype=torch.float64, device=dev)
+    out_f = torch.empty(3, dtype=torch.float32, device=dev)
+    return ws, parts, out_f
+
+
+class _DepthLoss(torch.autograd.Function):
+    """The robust depth data term and the depth smoothness term on the depth get_outputs returned (include/qed_splat.h states
+    them): the forward is qed_depth_loss' reduce pass (the two values and their denominators, all on the device), the backward
+    its gradient pass, which folds the same workspace and reads the upstream gradients from device memory -- each term stays
+    separately differentiable, and nothing is read back.  ``depth`` [H,W,1] or [H,W] is the fixed-up depth, ``alpha`` the
+    step's accumulation (read, not differentiated)."""
+
+    @staticmethod
+    def forward(ctx, depth, alpha, gt_depth, mask, gt_rgb, terms):
+        ctx.set_materialize_grads(False)
+        if not depth.is_cuda or depth.dtype != torch.float32:
+            raise L.QedSplatError("the depth losses need float32 GPU tensors: there is no CPU path in the product")
+        shape = depth.shape
+        H, W = shape[0], shape[1]
+        depth, alpha = depth.detach().contiguous(), alpha.detach().contiguous()
+        ws, parts, out_f = _depth_loss_buffers(depth.device)
+        ctx.args = (H, W, L.ptr(depth), 1, L.ptr(alpha), None, L.ptr(gt_depth), L.ptr(mask), L.ptr(gt_rgb), *terms.scalars())
+        ctx.flags = terms.flags
+        L.check(L.load().qed_depth_loss(*ctx.args, ctx.flags | L.DL_REDUCE, None, None, None, L.ptr(ws), None, 1, L.ptr(parts),
+                                        L.ptr(out_f), _stream()), "qed_depth_loss")
+        ctx.save_for_backward(depth, alpha, gt_depth, mask, gt_rgb, ws)
+        ctx.mark_non_differentiable(parts)
+        return out_f[0:1].view(()), out_f[1:2].view(()), parts
+
+    @staticmethod
+    def backward(ctx, g_data, g_tv, _g_parts):
+        depth, ws = ctx.saved_tensors[0], ctx.saved_tensors[5]
+        flags = ctx.flags
+        if g_data is None:
+            flags &= ~L.DL_DATA
+        if g_tv is None:
+            flags &= ~(L.DL_TV | L.DL_TV_EDGE)
+        if not (flags & (L.DL_DATA | L.DL_TV)) or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        unit = _unit_grad(depth.device).data_ptr()
+
+        def up(g):                                            # (backward_fused()'s cached unit gradient: NULL = 1)
+            return None if (g is None or g.data_ptr() == unit) else g.to(torch.float32).reshape(1).contiguous()
+        g_data, g_tv = up(g_data), up(g_tv)
+        v_depth = torch.empty_like(depth)
+        L.check(L.load().qed_depth_loss(*ctx.args, flags | L.DL_GRAD, L.ptr(g_data), L.ptr(g_tv), None, L.ptr(ws),
+                                        L.ptr(v_depth), 1, None, None, _stream()), "qed_depth_loss")
+        return (v_depth,) + (None,) * 5
+
+
+def depth_losses(depth: Tensor, alpha: Tensor, gt_depth: Tensor, mask, gt_rgb: Tensor, terms: DepthTerms):
+    """(depth_loss, depth_tv_loss, parts) of ``terms`` on the depth image get_outputs returned: 0-dim device tensors, each
+    differentiable in ``depth``; parts = float64 [8] {the two values, |V|, N_x, N_y, E_x, E_y, 0}."""
+    return _DepthLoss.apply(depth, alpha, gt_depth, mask, gt_rgb, terms)

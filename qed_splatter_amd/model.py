@@ -40,6 +40,7 @@ from . import _lib as L
 from .handover import FrameOrder, Handover
 from .losses import _FusedImageLoss, _ImageLosses, _McmcReg, _f32_image, _mcmc_reg_grad_adder, _mcmc_reg_values
 from .losses import _ssim_key, _unit_grad
+from .losses import depth_losses, depth_terms
 from .losses import _PostProcess, _SSIM, _UNIT_GRADS, ssim  # noqa: F401  (also importable from here)
 from .optim import FlatAdam, QedAdam, QedAdamSet, exponential_decay_lr  # noqa: F401  (also importable from here)
 from .optim import _RAW_GRAD, _all_groups_stepped_by_qed_adam, _raw_grad
@@ -158,6 +159,19 @@ class QEDSplatterModelConfig:
     normal_consistency_from_step: int = 0
     use_normal_tv: bool = False
     normal_tv_lambda: float = 0.1
+    # Robust depth data terms and depth smoothness (losses.depth_terms, include/qed_splat.h; this project's definitions in the
+    # spirit of DN-Splatter's depth losses, not checked against it).  depth_loss_type: "L1" (the reference's term, the
+    # built-in kernels), "MSE", "LogL1", "HuberL1" (a FIXED depth_huber_delta) or "EdgeAwareLogL1" (LogL1 weighted down at
+    # colour edges of the ground-truth image); "depth_loss" then is depth_lambda * the mean of that term over the reference's
+    # valid pixels.  depth_tv_lambda > 0 adds "depth_tv_loss": the total variation of the rendered depth over neighbour
+    # pairs with alpha > 0, a finite depth and a non-zero mask, weighted by exp(-|colour difference|) with
+    # depth_tv_edge_aware; it needs no sensor depth and so also acts inside sensor holes.  The residuals, depth_huber_delta
+    # and the smoothness term are in the MODEL'S units (after the dataparser's scale).  Both need
+    # output_depth_during_training; the defaults launch nothing new
+    depth_loss_type: str = "L1"
+    depth_huber_delta: float = 0.1
+    depth_tv_lambda: float = 0.0
+    depth_tv_edge_aware: bool = True
 
     @classmethod
     def synthetic(cls, **kw) -> "QEDSplatterModelConfig":
@@ -791,6 +805,7 @@ class QEDSplatterModel(nn.Module):
             return {}
         if self.training:
             assert camera.shape[0] == 1, "Only one camera at a time"          # model.py:211
+            depth_terms(self.config)             # (config.depth_loss_type / depth_tv_lambda: refused before any launch)
             if self.camera_optimizer is not None:
                 optimized_camera_to_world = self.camera_optimizer.apply_to_camera(camera)
             else:
@@ -1109,6 +1124,7 @@ class QEDSplatterModel(nn.Module):
         (0.0 when no pixel is valid, model.py:111-114).  One fused node instead of ~30 eager launches with boolean
         gathers; each entry stays separately differentiable (the trainer sums and may weight them)."""
         cfg = self.config
+        dterms = depth_terms(cfg)                # (None: the built-in depth-L1 term and nothing else)
         pred_img = outputs["rgb"]
         depth_out = outputs["depth"]
         if depth_out is None:
@@ -1130,14 +1146,20 @@ class QEDSplatterModel(nn.Module):
         if shared is not None and shared.get("loss") is not None:
             dc = depth_out.contiguous()
             if shared["depth_key"] == (dc.data_ptr(), dc._version, depth_batch.data_ptr(), depth_batch._version) \
-                    and shared["lambdas"] == (float(cfg.ssim_lambda), float(cfg.depth_lambda)):
+                    and shared["lambdas"] == (float(cfg.ssim_lambda), float(cfg.depth_lambda)) and dterms is None:
                 loss_shared = shared["loss"]
         # the accumulator of the compositing backward behind THESE outputs is zeroed by this loss's backward launch (the
         # first loss taken on them: a second one leaves the fill to the backward pass)
         handover = ctx.handover if (mine and torch.is_grad_enabled()) else None
         main, depth = _ImageLosses.apply(pred_img, depth_out, gt_img, depth_batch, mask, float(cfg.ssim_lambda),
-                                         float(cfg.depth_lambda), shared["maps_sum"] if shared else None, loss_shared,
-                                         handover)
+                                         float(cfg.depth_lambda) if dterms is None else 0.0,
+                                         shared["maps_sum"] if shared else None, loss_shared, handover)
+        depth_tv = None
+        if dterms is not None:
+            # config.depth_loss_type / depth_tv_lambda: the built-in kernels ran with depth_lambda = 0; the terms are one
+            # node of their own on the same depth image (its gradient joins theirs in autograd; behind a captured segment
+            # it is copied into the segment's buffer)
+            depth, depth_tv, _ = depth_losses(depth_out, outputs["accumulation"], depth_batch, mask, gt_img, dterms)
         out = {"main_loss": main, "scale_reg": self._scale_reg()}
         lo, ls = self._mcmc_reg_weights()
         if lo > 0.0 or ls > 0.0:
@@ -1149,6 +1171,8 @@ class QEDSplatterModel(nn.Module):
         if self.training and pose_losses is not None:                        # the parent's camera_opt_regularizer
             pose_losses(out)
         out["depth_loss"] = depth
+        if depth_tv is not None and dterms.tv_lambda > 0.0:
+            out["depth_tv_loss"] = depth_tv
         accum = outputs.get("normal_accum") if (cfg.use_normal_loss and self.training) else None
         if accum is not None:
             target = self._normal_target(batch, depth_batch, H, W, accum._qed_intrinsics)
@@ -1320,6 +1344,8 @@ class QEDSplatterModel(nn.Module):
         the differentiable total (call ``.backward()`` on it as is: the kernel already wrote its gradient
         for an upstream gradient of 1); the two parts are detached views for logging.  Numerically the
         same quantities as get_outputs + get_loss_dict.
+        With config.depth_loss_type / depth_tv_lambda (losses.depth_terms) ``depth_loss`` is the chosen data term and
+        ``depth_tv_loss`` the smoothness term, both detached and both part of ``loss``.
 
         ``frame_key`` (hashable, optional): identifies the CAMERA this frame is rendered from -- the dataset's camera
         index.  Frames under one key share a launch-order buffer: the order the loss launch computes for this frame's
@@ -1357,6 +1383,7 @@ class QEDSplatterModel(nn.Module):
         if attrs.get("compact_sh") is not None:
             self._resolve_sh_grad()               # (compact gradients of an earlier step nobody consumed: see there)
         cfg = self.config
+        dterms = depth_terms(cfg)                # (config.depth_loss_type / depth_tv_lambda: refused before any launch)
         pose_opt = camera_optimizer if (camera_optimizer is not None and camera_optimizer.active and self.training) else None
         # (conversions of the batch are shared within a step, never across steps; parallel.py refuses a data-parallel step
         # behind either optimiser)
@@ -1434,7 +1461,7 @@ class QEDSplatterModel(nn.Module):
         if grid_opt is not None:
             return self._fused_loss_with_grid(grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags,
                                               sync, handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask,
-                                              lo, ls, mcmc_vals, normal)
+                                              lo, ls, mcmc_vals, normal, dterms)
         # ``optimizer`` (a FlatAdam stepped with device_state=True, fused_sh=True right after this step's backward): the
         # loss pass's fold launch advances its device step state, so that the optimiser needs no launch of its own for it
         tick = None
@@ -1450,9 +1477,10 @@ class QEDSplatterModel(nn.Module):
             attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
             # (the compositing node keeps the forward pass's per-tile costs: the loss launch sorts them for its backward)
             tile_cost = getattr(render.grad_fn, "tile_cost", None) if torch.is_grad_enabled() else None
-            total, parts = _FusedImageLoss.apply(render, alpha, bg.contiguous(), gt_rgb, gt_depth, mask,
-                                                 float(cfg.ssim_lambda), cfg.depth_lambda,
-                                                 handover if torch.is_grad_enabled() else None, tick, tile_cost)
+            total, parts, *dparts = _FusedImageLoss.apply(render, alpha, bg.contiguous(), gt_rgb, gt_depth, mask,
+                                                          float(cfg.ssim_lambda), cfg.depth_lambda,
+                                                          handover if torch.is_grad_enabled() else None, tick, tile_cost,
+                                                          dterms)
             if frame_order is not None and tile_cost is not None and float(cfg.ssim_lambda) > 0.0 \
                     and os.environ.get("QED_STEP_PASSENGERS", "1") != "0":
                 frame_order.valid = True          # (the buffer holds an order from here on, in stream order)
@@ -1465,12 +1493,16 @@ class QEDSplatterModel(nn.Module):
             if tick is not None:
                 optimizer.drop_tick()
             raise
+        # (config.depth_loss_type / depth_tv_lambda: the node's third output holds the two terms, already part of ``total``)
+        depth_part = parts[1] if dterms is None else dparts[0][0]
         if mcmc_vals is None:
-            out = {"loss": total, "main_loss": parts[0], "depth_loss": parts[1]}
+            out = {"loss": total, "main_loss": parts[0], "depth_loss": depth_part}
         else:
             out = {"loss": total + mcmc_vals[2], "main_loss": parts[0]}
             self._put_mcmc_regs(out, lo, ls, mcmc_vals)
-            out["depth_loss"] = parts[1]
+            out["depth_loss"] = depth_part
+        if dterms is not None and dterms.tv_lambda > 0.0:
+            out["depth_tv_loss"] = dparts[0][1]
         if normal is not None:
             self._add_fused_normal_loss(out, normal, info, render, alpha, mask)
         if pose_reg is not None:
@@ -1531,7 +1563,7 @@ class QEDSplatterModel(nn.Module):
 
     def _fused_loss_with_grid(self, grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags, sync,
                               handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask, lo, ls, mcmc_vals,
-                              normal=None):
+                              normal=None, dterms=None):
         """fused_loss behind ``grid_optimizer``: the loss is taken on the CORRECTED colour, so the gridless route's one
         launch from ``render`` to its gradient does not apply.  The launches are those of get_outputs -> get_loss_dict:
         the compositing forward with its post-processing epilogue (clamped colour, fixed-up depth), the slice, the SSIM
@@ -1551,14 +1583,23 @@ class QEDSplatterModel(nn.Module):
         rgb, tv = grid_opt.begin_fused(info.pop("post_rgb"), grid_idx, H, W)
         depth = info.pop("post_depth")
         main, depth_loss = _ImageLosses.apply(rgb.squeeze(0), depth.squeeze(0), gt_rgb, gt_depth, mask,
-                                              float(cfg.ssim_lambda), float(cfg.depth_lambda), None, None,
-                                              handover if grad else None)
+                                              float(cfg.ssim_lambda), float(cfg.depth_lambda) if dterms is None else 0.0,
+                                              None, None, handover if grad else None)
+        depth_tv = None
+        if dterms is not None:                   # (config.depth_loss_type / depth_tv_lambda: get_loss_dict's node, as there)
+            depth_loss, depth_tv, _ = depth_losses(depth.squeeze(0), alpha.squeeze(0), gt_depth, mask, gt_rgb, dterms)
+            if dterms.tv_lambda <= 0.0:
+                depth_tv = None
         total = main + depth_loss + tv
+        if depth_tv is not None:
+            total = total + depth_tv
         out = {"loss": total, "main_loss": main.detach()}
         if mcmc_vals is not None:
             out["loss"] = total + mcmc_vals[2]
             self._put_mcmc_regs(out, lo, ls, mcmc_vals)
         out["depth_loss"] = depth_loss.detach()
+        if depth_tv is not None:
+            out["depth_tv_loss"] = depth_tv.detach()
         if normal is not None:                   # (the term does not touch colour: it is taken on the accumulated normal)
             self._add_fused_normal_loss(out, normal, info, render, alpha, mask)
         if pose_reg is not None:

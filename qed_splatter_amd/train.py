@@ -397,6 +397,15 @@ def build_parser() -> argparse.ArgumentParser:
                     help="total variation of the rendered normals (config.use_normal_tv); not with --camera-optimizer")
     ap.add_argument("--normal-tv-lambda", type=float, default=argparse.SUPPRESS, metavar="Y",
                     help="the smoothness term's weight (default 0.1)")
+    ap.add_argument("--depth-loss-type", choices=tuple(L.DEPTH_LOSS_TYPES), default=argparse.SUPPRESS,
+                    help="the depth data term (config.depth_loss_type, default L1: the reference's); residuals are in the "
+                         "model's units, after the dataparser's scale")
+    ap.add_argument("--depth-huber-delta", type=float, default=argparse.SUPPRESS, metavar="D",
+                    help="HuberL1's fixed threshold, in the model's units (default 0.1)")
+    ap.add_argument("--depth-tv-lambda", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="weight of the total variation of the rendered depth (config.depth_tv_lambda; default 0 = off)")
+    ap.add_argument("--no-depth-tv-edge-aware", action="store_true", default=argparse.SUPPRESS,
+                    help="do not weight the depth smoothness term down at colour edges of the ground-truth image")
     ap.add_argument("--prune-at", type=int, nargs="+", default=argparse.SUPPRESS, metavar="STEP",
                     help="after these steps' refinement: score the training cameras and prune by blending contribution "
                          "(prune.py)")
@@ -407,6 +416,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prune-score", choices=("max", "sum"), default=argparse.SUPPRESS)
     ap.add_argument("--prune-view-stride", type=int, default=argparse.SUPPRESS, metavar="S", help="score every S-th camera")
     return ap
+
+
+def depth_config_of(a) -> Dict:
+    """The model-config fields of the --depth-* options (the config's defaults where an option is absent)."""
+    cfg = QEDSplatterModelConfig
+    return {"depth_loss_type": str(getattr(a, "depth_loss_type", cfg.depth_loss_type)),
+            "depth_huber_delta": float(getattr(a, "depth_huber_delta", cfg.depth_huber_delta)),
+            "depth_tv_lambda": float(getattr(a, "depth_tv_lambda", cfg.depth_tv_lambda)),
+            "depth_tv_edge_aware": not bool(getattr(a, "no_depth_tv_edge_aware", False))}
 
 
 def prune_config_of(a):
@@ -452,7 +470,10 @@ def main(argv=None) -> Dict:
                                     normal_consistency_from_step=int(getattr(a, "normal_consistency_from", 0)),
                                     use_normal_tv=bool(getattr(a, "normal_tv", False)),
                                     normal_tv_lambda=float(getattr(a, "normal_tv_lambda",
-                                                                   QEDSplatterModelConfig.normal_tv_lambda)))
+                                                                   QEDSplatterModelConfig.normal_tv_lambda)),
+                                    **depth_config_of(a))
+    from .losses import depth_terms
+    dterms = depth_terms(config)                 # (a refused combination ends the run before the model is built)
     model = build_model(config, dm, a.init_from_ply, a.seed)
     print(f"seeded {model.num_points} Gaussians")
     trainer = Trainer(model, dm, seed=a.seed,
@@ -503,6 +524,10 @@ def main(argv=None) -> Dict:
     for flag, key in ((config.use_normal_consistency, "normal_consistency_loss"), (config.use_normal_tv, "normal_tv_loss")):
         if flag:                                 # (None: no step carried the term, e.g. all before --normal-consistency-from)
             result[key] = float(losses[key]) if (losses is not None and key in losses) else None
+    if dterms is not None:
+        result["depth_loss"] = float(losses["depth_loss"]) if losses is not None else None
+        if dterms.tv_lambda > 0.0:
+            result["depth_tv_loss"] = float(losses["depth_tv_loss"]) if losses is not None else None
     if output_normals:
         trainer.model.config.output_normals = True      # (from here on: the final evaluation and --render-eval only)
     if color_corrected or output_normals:
