@@ -97,6 +97,7 @@ struct Proj {
     bool valid;
     float mx, my, z;        // mean2d, depth
     float A, B, Cc, det;    // blurred 2D covariance and its determinant
+    float tr0, hd0;         // a0 + c0 and (a0 - c0) / 2 of the covariance before the blur
     float ca, cb, cc;       // conic
     float comp;             // anti-aliasing compensation
     float radius;
@@ -163,6 +164,8 @@ __device__ __forceinline__ void project_one(const Cam& cam, const float* mean, c
     p.A = a0 + eps2d;
     p.B = b0;
     p.Cc = c0 + eps2d;
+    p.tr0 = a0 + c0;
+    p.hd0 = 0.5f * (a0 - c0);
     p.det = det_orig + eps2d * (a0 + c0) + eps2d * eps2d;
     if (!(p.det > 0.f)) return;
     p.comp = sqrtf(fmaxf(0.f, det_orig / p.det));
@@ -779,7 +782,9 @@ project_bwd_kernel(int N, int C, const float* __restrict__ means, const float* _
             // long axis (~ 1 / l+^2) is what is left of entries 1e8 times larger: `scales` gradients 6e-2 off on
             // 2 500 : 1 needles.  l+ = bh + r and l- = det / l+ with the cancellation-free det.
             const float g01 = 0.5f * v_cb;
-            const float bh = 0.5f * (p.A + p.Cc), hd = 0.5f * (p.A - p.Cc);
+            // ((A + C) / 2 and (A - C) / 2 from the entries of S0 = T T^T itself: of a splat far below a pixel A = a0 + eps no
+            // longer holds a0, and the compensation's share below needs the eigenvalues and the axes of S0)
+            const float bh = 0.5f * p.tr0 + eps2d, hd = p.hd0;
             const float rr = __builtin_amdgcn_sqrtf(hd * hd + p.B * p.B);              // (1 ulp forms: the bound is 1e-4)
             const float lp = bh + rr, ilp = __builtin_amdgcn_rcpf(lp), lm = p.det * ilp, ilm = __builtin_amdgcn_rcpf(lm);
             // unit eigenvector of l+: (B, l+ - A) or (l+ - C, B), whichever is formed without a cancelling subtraction
@@ -794,13 +799,18 @@ project_bwd_kernel(int N, int C, const float* __restrict__ means, const float* _
             float hpp = -(ux * gux + uy * guy) * ilp * ilp;     // H' in the eigenbasis
             float hpm = -(ux * gwx + uy * gwy) * ilp * ilm;
             float hmm = -(wx * gwx + wy * gwy) * ilm * ilm;
-            if (flags & QED_F_ANTIALIASED) {
-                // compensation = sqrt(max(0, det_orig / det_blur))  (gsplat add_blur_vjp): + v_sqr (om X - eps det(X) I)
-                const float det_conic = 1.f / p.det;
-                const float v_sqr = v_comp * 0.5f / (p.comp + 1e-6f);
-                const float om = 1.f - p.comp * p.comp;
-                hpp += v_sqr * (om * ilp - eps2d * det_conic);
-                hmm += v_sqr * (om * ilm - eps2d * det_conic);
+            if ((flags & QED_F_ANTIALIASED) && p.comp > 0.f) {
+                // compensation = sqrt(det0 / det), det0 = det(S0), det = det(S0 + eps I): in the common eigenbasis, with the
+                // eigenvalues l0+, l0- of S0 (l+ = l0+ + eps),
+                //   d comp / d S0 = diag((1 - comp^2) / l+ - eps / det, ...) / (2 comp) = eps diag(l0- / l+, l0+ / l-) / (2 comp det)
+                // The left form (gsplat's add_blur_vjp) is a difference of terms ~ 1 / eps of which nothing is left for a
+                // splat far below a pixel (l0 << eps), and its guard comp + 1e-6 in the denominator scales the result by
+                // comp / (comp + 1e-6); the right one has products only.  l0+ = tr(S0) / 2 + r, l0- = det0 / l0+ with
+                // det0 = comp^2 det (Cauchy-Binet in the forward pass).  comp == 0 (det0 == 0): no gradient.
+                const float l0p = 0.5f * p.tr0 + rr, l0m = p.comp * p.comp * p.det / l0p;
+                const float v_sqr = v_comp * 0.5f * eps2d / (p.comp * p.det);
+                hpp += v_sqr * l0m * ilp;
+                hmm += v_sqr * l0p * ilm;
             }
             // ---- cov2d = T T^T + eps I  ->  v_T = 2 H T = 2 U H' (U^T T) ----
             float vT[6];
