@@ -71,7 +71,7 @@ extern "C" {
  *      formed at double precision, as the host-state path forms them.
  * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_gaussian_normals,
  * qed_normal_maps, qed_depth_normals, qed_angular_error; qed_normal_loss, qed_gaussian_normals_bwd, qed_normal_rows_merge;
- * qed_normal_consistency, qed_normal_rows_merge_depth; qed_depth_loss). */
+ * qed_normal_consistency, qed_normal_rows_merge_depth; qed_depth_loss; qed_relative_depth_loss). */
 #define QED_ABI_VERSION 4
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
@@ -1196,6 +1196,71 @@ int qed_depth_loss(int32_t height, int32_t width, const float* depth, int32_t de
                    float depth_lambda, float huber_delta, float tv_lambda, uint32_t flags, const float* g_data,
                    const float* g_tv, const float* loss_base, double* workspace, float* v_depth, int32_t v_depth_stride,
                    double* out, float* out_f, void* stream);
+
+/* ---- relative-depth supervision in training (csrc/relative_depth.hip) ---------------------------------------------------------
+ * Three terms between the rendered depth and a PRIOR known only up to an unknown scale and shift -- a monocular network's depth
+ * or inverse depth -- for datasets without a depth sensor.  THIS PROJECT'S definitions, in the spirit of FSGS, SparseGS (the
+ * Pearson terms) and MiDaS (the scale-and-shift aligned L1), restated from memory, not checked against them and not in the
+ * reference.  Per pixel p = (i, j) of one camera's step:
+ *   d(p)  = the depth, read at depth[p * depth_stride]: channel 3 of an [H,W,4] render (stride 4) or the depth get_outputs
+ *           returns (stride 1) -- pixels with alpha == 0 are outside V, so the raw channel and the fixed-up depth give the same
+ *           bits and the entry needs neither the channel's maximum nor the fix-up;
+ *   alpha = the accumulation, g(p) = the prior, m(p) = an optional float mask (NULL = 1).  The mask only selects: nothing is
+ *           multiplied by it;
+ *   V = {p : alpha > 0, m != 0, finite(d), finite(g), g > 0}, with QED_RD_INVERSE also d > 0;
+ *   x = d, or x = 1 / d with QED_RD_INVERSE (dx/dd = 1, or -1 / d^2);
+ *   over a set S of valid pixels: n = |S|, the means mx, mg, the BIASED moments vx, vg, cov, rho = cov / sqrt(vx vg).
+ *   S is DEGENERATE when n < 2, or vx <= 1e-12 mean(x^2), or vg <= 1e-12 mean(g^2): its value is 0, its gradient exactly zero.
+ * QED_RD_PEARSON, S = V:
+ *   loss = lambda (1 - rho);  d loss / d x_p = -lambda / (n sqrt(vx vg)) [(g_p - mg) - rho sqrt(vg / vx) (x_p - mx)], times dx/dd.
+ * QED_RD_SCALE_SHIFT_L1, S = V:
+ *   s = cov / vg, t = mx - s mg: the least-squares fit of the prior to the render, CONSTANTS (not differentiated);
+ *   r = x - (s g + t);  loss = lambda sum over V of |r| / n;  d loss / d x_p = lambda sign(r) / n, sign(0) = 0, times dx/dd.
+ * QED_RD_PATCH_PEARSON: boxes of P x P pixels, P = `patch` a power of two from 8 to 128; the box of pixel (i, j) is
+ *   (floor((i + offset_y) / P), floor((j + offset_x) / P)) with 0 <= offset_x, offset_y < P; partial boxes at the borders
+ *   count.  A box CONTRIBUTES iff its valid count n_b >= K = max(2, ceil(min_valid * P * P)), min_valid in (0, 1], and it is
+ *   not degenerate; B = the number of contributing boxes;
+ *   loss = lambda / B * sum over the contributing boxes of (1 - rho_b), 0 when B == 0; a pixel of V in a contributing box gets
+ *   its box's Pearson gradient (lambda = 1) times lambda / B, every other pixel exactly 0.
+ * alpha, g and m are constants.  Every sum is carried in double from the float32 inputs (raw one-pass moments) and folded in a
+ * fixed order, the per-pixel arithmetic (x, r, the bracket) is double, and there are no floating-point atomics: the same input
+ * gives the same bits on every run.
+ *
+ * qed_relative_depth_loss: one image.  flags: QED_RD_INVERSE; the passes QED_RD_REDUCE and QED_RD_GRAD, as in qed_depth_loss --
+ *   the reduce pass leaves its sums in `workspace` (QED_RELATIVE_DEPTH_WS_DOUBLES(height, width, patch) doubles; patch = 0 for
+ *   the two whole-image types; no zeroing needed) and writes out / out_f; a gradient pass, in the same call or a later one on
+ *   the same inputs and the SAME workspace, folds what it needs itself, so nothing reaches the host; QED_RD_ACCUMULATE: the
+ *   gradient pass ADDS to v_depth[p * v_depth_stride] (a plane that qed_depth_loss' smoothness term or a zero fill has written)
+ *   where without it the pass writes every element, zero where nothing arrives.
+ *   Launches: Pearson one streaming reduce and one gradient launch (a one-workgroup fold follows a reduce pass that runs
+ *   alone); ScaleShiftL1 one further streaming launch for sum |r|; PatchPearson one workgroup per box (patch <= 16: one wave per box,
+ *   four boxes per workgroup), which leaves the box's
+ *   moments and gradient coefficients in its row of a table in the workspace, a one-workgroup fold over the rows, and the
+ *   gradient launch, which reads its pixel's row.
+ *   out[8] (device doubles) = {loss, |V|, rho of the whole image, s, t (both of the whole image; 0 for a degenerate V), B, the
+ *   mean of rho_b over the contributing boxes (B and the mean 0 for the whole-image types), 0}; out_f[2] (device floats, may
+ *   be NULL) = {loss, loss_base[0] + loss} (loss_base: a device float, NULL = 0).  g_up: the upstream gradient, a device float,
+ *   NULL = 1.  height * width == 0 writes zeros.  Refused (QED_E_INVALID_ARG, qed_last_error): an unknown type or flag, no
+ *   pass flag, a negative or non-finite lambda and, for QED_RD_PATCH_PEARSON, a patch outside {8, 16, 32, 64, 128}, offsets
+ *   outside [0, patch), min_valid outside (0, 1]. */
+#define QED_RD_WS_HEAD_DOUBLES (8 * 512)
+#define QED_RD_BOX_DOUBLES 12
+#define QED_RELATIVE_DEPTH_WS_DOUBLES(H, W, P)                                                                         \
+    (QED_RD_WS_HEAD_DOUBLES + ((P) > 0 ? QED_RD_BOX_DOUBLES * ((((int64_t)(H)) + 2 * (P) - 2) / (P)) *                  \
+                                             ((((int64_t)(W)) + 2 * (P) - 2) / (P))                                      \
+                                       : 0))
+#define QED_RD_PEARSON 0
+#define QED_RD_PATCH_PEARSON 1
+#define QED_RD_SCALE_SHIFT_L1 2
+#define QED_RD_INVERSE 1u
+#define QED_RD_REDUCE 2u
+#define QED_RD_GRAD 4u
+#define QED_RD_ACCUMULATE 8u
+int qed_relative_depth_loss(int32_t height, int32_t width, const float* depth, int32_t depth_stride, const float* alpha,
+                            const float* prior, const float* mask, int32_t type, float lambda, int32_t patch,
+                            int32_t offset_x, int32_t offset_y, float min_valid, uint32_t flags, const float* g_up,
+                            const float* loss_base, double* workspace, float* v_depth, int32_t v_depth_stride, double* out,
+                            float* out_f, void* stream);
 
 /* ---- oriented surface samples of one rendered view (csrc/surface.hip) -------------------------------------------------------
  * The planes get_outputs returns in evaluation mode with output_normals, back-projected into a compact list of world points

@@ -128,6 +128,8 @@ SIGNATURES = {
     "qed_normal_rows_merge_depth": (C.c_int, [_L, _P, _P, _P, _P]),
     "qed_depth_loss": (C.c_int, [_I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _F, _F, _F, _U, _P, _P, _P, _P, _P, _I, _P, _P,
                                  _P]),
+    "qed_relative_depth_loss": (C.c_int, [_I, _I, _P, _I, _P, _P, _P, _I, _F, _I, _I, _I, _F, _U, _P, _P, _P, _P, _I, _P, _P,
+                                          _P]),
     "qed_voxel_attr_workspace_bytes": (_L, [_L, _I]),
     "qed_voxel_down_sample_attr": (C.c_int, [_I, _P, _I, _P, _P, _F, _P, _P, _P, _P, _P, _L, _P, _P]),
     "qed_surface_workspace_ints": (_L, [_I, _I, _I]),
@@ -170,7 +172,21 @@ NC_CONSISTENCY, NC_TV, NC_REDUCE, NC_GRAD = 1, 2, 4, 8   # QED_NC_*
 DEPTH_LOSS_WS_DOUBLES = 6 * 256 + 136      # QED_DEPTH_LOSS_WS_DOUBLES
 DEPTH_LOSS_TYPES = {"L1": 0, "MSE": 1, "LogL1": 2, "HuberL1": 3, "EdgeAwareLogL1": 4}   # QED_DL_L1 .. QED_DL_EDGE_LOGL1
 DL_DATA, DL_TV, DL_TV_EDGE, DL_FIXUP, DL_REDUCE, DL_GRAD = 1, 2, 4, 8, 16, 32   # QED_DL_*
-NORMALS_WORLD, NORMALS_CAMERA = 0, 1       # QED_NORMALS_WORLD, QED_NORMALS_CAMERA
+RELATIVE_DEPTH_TYPES = {"Pearson": 0, "PatchPearson": 1, "ScaleShiftL1": 2}   # QED_RD_PEARSON .. QED_RD_SCALE_SHIFT_L1
+RELATIVE_DEPTH_PATCHES = (8, 16, 32, 64, 128)
+RD_INVERSE, RD_REDUCE, RD_GRAD, RD_ACCUMULATE = 1, 2, 4, 8   # QED_RD_*
+RD_WS_HEAD_DOUBLES, RD_BOX_DOUBLES = 8 * 512, 12   # QED_RD_WS_HEAD_DOUBLES, QED_RD_BOX_DOUBLES
+
+
+def relative_depth_ws_doubles(height: int, width: int, patch: int = 0) -> int:
+    """QED_RELATIVE_DEPTH_WS_DOUBLES(height, width, patch): the slots of the streaming passes and, for the patch-wise type,
+    a row per box at the offsets that make the most boxes (patch = 0: a whole-image type)."""
+    if patch <= 0:
+        return RD_WS_HEAD_DOUBLES
+    return RD_WS_HEAD_DOUBLES + RD_BOX_DOUBLES * ((height + 2 * patch - 2) // patch) * ((width + 2 * patch - 2) // patch)
+
+
+NORMALS_WORLD, NORMALS_CAMERA = 0, 1      # QED_NORMALS_WORLD, QED_NORMALS_CAMERA
 NV_NORMAL, NV_DEPTH_NORMAL = 1, 2          # QED_NV_NORMAL, QED_NV_DEPTH_NORMAL
 SURFACE_NORMAL_RENDERED, SURFACE_NORMAL_DEPTH = 0, 1   # QED_SURFACE_NORMAL_RENDERED, QED_SURFACE_NORMAL_DEPTH
 VOXEL_MAX_ATTRS = 8                        # QED_VOXEL_MAX_ATTRS

@@ -1,8 +1,8 @@
 """The image losses of a training step as autograd nodes over the loss kernels: the stand-alone SSIM (``ssim``), the
 statements around the operator (``_PostProcess``), get_loss_dict's two terms (``_ImageLosses``), the fused step's K8 node
 (``_FusedImageLoss``), splatfacto's MCMC regularisers (``_McmcReg``), the normal loss (``_NormalLoss``), the normal
-consistency and smoothness terms (``_NormalConsistency``) and the robust depth and depth smoothness terms (``_DepthLoss``,
-``depth_terms``), with the helpers that prepare their inputs and scratch buffers.  Nothing in here touches the model:
+consistency and smoothness terms (``_NormalConsistency``), the robust depth and depth smoothness terms (``_DepthLoss``,
+``depth_terms``) and the relative-depth terms (``_RelativeDepthLoss``, ``relative_depth_terms``), with the helpers that prepare their inputs and scratch buffers.  Nothing in here touches the model:
 ``model.py`` and ``metrics.py`` call in, this module imports the library binding only."""
 from __future__ import annotations
 
@@ -230,12 +230,15 @@ class _FusedImageLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, render, alpha, background, gt_rgb, gt_depth, mask, ssim_lambda, depth_lambda, handover=None, tick=None,
-                tile_cost=None, depth_terms=None):
+                tile_cost=None, depth_terms=None, relative_terms=None, relative_offsets=(0, 0)):
         import ctypes
         # depth_terms (a DepthTerms; None = the built-in depth-L1 term): K8 runs with depth_lambda = 0 -- it then writes zeros
         # to channel 3 of v_render -- and qed_depth_loss' two launches follow it: they put the depth gradient there and add
         # their two values to K8's total, on the device.  A third output, float32 [3] = {depth_loss, depth_tv_loss, total}
-        if depth_terms is not None:
+        # relative_terms (a RelativeDepthTerms; None = off): K8 runs with depth_lambda = 0 as well, and qed_relative_depth_loss'
+        # launches follow any of qed_depth_loss: with QED_RD_ACCUMULATE they ADD their gradient to channel 3 of v_render and
+        # their value to the total, on the device.  One more output, float32 [2] = {relative_depth_loss, total}
+        if depth_terms is not None or relative_terms is not None:
             depth_lambda = 0.0
         lib = L.load()
         ctx.set_materialize_grads(False)
@@ -289,29 +292,40 @@ class _FusedImageLoss(torch.autograd.Function):
         ctx.save_for_backward(v_render, v_alpha)
         total = losses[2:3].view(())
         parts = losses[0:2]
+        extra, base = [], losses.data_ptr() + 8
         if depth_terms is not None:
             assert CH == 4, "the depth terms need the depth channel"
             ws, dparts, out_f = _depth_loss_buffers(dev)
             L.check(lib.qed_depth_loss(H, W, render.data_ptr() + 12, 4, L.ptr(alpha), sums.data_ptr() + 12, L.ptr(gt_depth),
                                        L.ptr(mask), L.ptr(gt_rgb), *depth_terms.scalars(),
                                        depth_terms.flags | L.DL_FIXUP | L.DL_REDUCE | L.DL_GRAD, None, None,
-                                       losses.data_ptr() + 8, L.ptr(ws), v_render.data_ptr() + 12, 4, L.ptr(dparts),
+                                       base, L.ptr(ws), v_render.data_ptr() + 12, 4, L.ptr(dparts),
                                        L.ptr(out_f), st), "qed_depth_loss")
-            ctx.mark_non_differentiable(parts, out_f)
-            return out_f[2:3].view(()), parts, out_f
-        ctx.mark_non_differentiable(parts)
-        return total, parts
+            extra.append(out_f)
+            total, base = out_f[2:3].view(()), out_f.data_ptr() + 8
+        if relative_terms is not None:
+            assert CH == 4, "the relative-depth terms need the depth channel"
+            ws, rparts, rout_f = _relative_depth_buffers(H, W, relative_terms, dev)
+            L.check(lib.qed_relative_depth_loss(H, W, render.data_ptr() + 12, 4, L.ptr(alpha), L.ptr(gt_depth), L.ptr(mask),
+                                                *relative_terms.scalars(relative_offsets),
+                                                relative_terms.flags | L.RD_REDUCE | L.RD_GRAD | L.RD_ACCUMULATE, None, base,
+                                                L.ptr(ws), v_render.data_ptr() + 12, 4, L.ptr(rparts), L.ptr(rout_f), st),
+                    "qed_relative_depth_loss")
+            extra.append(rout_f)
+            total = rout_f[1:2].view(())
+        ctx.mark_non_differentiable(parts, *extra)
+        return (total, parts, *extra)
 
     @staticmethod
     def backward(ctx, v_total, *_v_parts):
         if v_total is None:
-            return (None,) * 12
+            return (None,) * 14
         v_render, v_alpha = ctx.saved_tensors
         # the kernel wrote d(total)/d(render, alpha).  The usual upstream gradient is the cached unit tensor of
         # backward_fused() and needs no scaling pass; anything else (a weighted loss, a GradScaler) is applied
         if v_total.data_ptr() != _unit_grad(v_total.device).data_ptr():
             v_render, v_alpha = v_render * v_total, v_alpha * v_total
-        return (v_render, v_alpha) + (None,) * 10
+        return (v_render, v_alpha) + (None,) * 12
 
 
 def _mcmc_reg_values(opacities: Tensor, scales: Tensor, lo: float, ls: float) -> Tensor:
@@ -503,16 +517,18 @@ class _NormalConsistency(torch.autograd.Function):
 
 class DepthTerms:
     """The robust depth data term and the depth smoothness term of one step, as the kernels take them (depth_terms())."""
-    __slots__ = ("type_id", "depth_lambda", "huber_delta", "tv_lambda", "tv_edge")
+    __slots__ = ("type_id", "depth_lambda", "huber_delta", "tv_lambda", "tv_edge", "data")
 
-    def __init__(self, type_id: int, depth_lambda: float, huber_delta: float, tv_lambda: float, tv_edge: bool):
+    def __init__(self, type_id: int, depth_lambda: float, huber_delta: float, tv_lambda: float, tv_edge: bool,
+                 data: bool = True):
         self.type_id, self.depth_lambda, self.huber_delta = int(type_id), float(depth_lambda), float(huber_delta)
         self.tv_lambda, self.tv_edge = float(tv_lambda), bool(tv_edge)
+        self.data = bool(data)               # (False beside a relative-depth term: the prior cannot feed a metric term)
 
     @property
     def flags(self) -> int:
         tv = (L.DL_TV | (L.DL_TV_EDGE if self.tv_edge else 0)) if self.tv_lambda > 0.0 else 0
-        return L.DL_DATA | tv
+        return (L.DL_DATA if self.data else 0) | tv
 
     def scalars(self):
         """(type, depth_lambda, huber_delta, tv_lambda): the constants of a qed_depth_loss call, in its order."""
@@ -537,7 +553,11 @@ def depth_terms(cfg):
     if not cfg.output_depth_during_training:
         raise NotImplementedError("depth_loss_type other than 'L1' or depth_tv_lambda > 0 with "
                                   "output_depth_during_training=False: both terms are taken on the rendered depth")
-    return DepthTerms(L.DEPTH_LOSS_TYPES[name], cfg.depth_lambda, delta, tv, getattr(cfg, "depth_tv_edge_aware", True))
+    # (beside a relative-depth term batch["depth_image"] is a prior up to scale and shift: the metric data term is off, its
+    # value the kernels' zero, and only the smoothness term is left of this node)
+    relative = getattr(cfg, "relative_depth_loss_type", "off") != "off"
+    return DepthTerms(L.DEPTH_LOSS_TYPES[name], cfg.depth_lambda, delta, tv, getattr(cfg, "depth_tv_edge_aware", True),
+                      data=not relative)
 
 
 def _depth_loss_buffers(dev):
@@ -596,3 +616,130 @@ def depth_losses(depth: Tensor, alpha: Tensor, gt_depth: Tensor, mask, gt_rgb: T
     """(depth_loss, depth_tv_loss, parts) of ``terms`` on the depth image get_outputs returned: 0-dim device tensors, each
     differentiable in ``depth``; parts = float64 [8] {the two values, |V|, N_x, N_y, E_x, E_y, 0}."""
     return _DepthLoss.apply(depth, alpha, gt_depth, mask, gt_rgb, terms)
+
+
+class RelativeDepthTerms:
+    """The relative-depth term of one step, as the kernels take it (relative_depth_terms())."""
+    __slots__ = ("type_id", "lam", "inverse", "patch", "min_valid", "jitter")
+
+    def __init__(self, type_id: int, lam: float, inverse: bool, patch: int, min_valid: float, jitter: bool):
+        self.type_id, self.lam, self.inverse = int(type_id), float(lam), bool(inverse)
+        self.patch, self.min_valid, self.jitter = int(patch), float(min_valid), bool(jitter)
+
+    @property
+    def flags(self) -> int:
+        return L.RD_INVERSE if self.inverse else 0
+
+    @property
+    def patchwise(self) -> bool:
+        return self.type_id == L.RELATIVE_DEPTH_TYPES["PatchPearson"]
+
+    def offsets(self, step: int):
+        """(ox, oy) of the boxes at training step ``step``: ((37 step) mod P, (91 step) mod P) with jitter, else (0, 0)."""
+        if not (self.jitter and self.patchwise):
+            return (0, 0)
+        return ((37 * int(step)) % self.patch, (91 * int(step)) % self.patch)
+
+    def scalars(self, offsets=(0, 0)):
+        """(type, lambda, patch, offset_x, offset_y, min_valid): the constants of a qed_relative_depth_loss call, in its order."""
+        return self.type_id, self.lam, self.patch, int(offsets[0]), int(offsets[1]), self.min_valid
+
+    def ws_doubles(self, H: int, W: int) -> int:
+        return L.relative_depth_ws_doubles(H, W, self.patch if self.patchwise else 0)
+
+
+def relative_depth_terms(cfg):
+    """config.relative_depth_loss_type / _lambda / _space / _patch / _patch_min_valid / _patch_jitter checked, before any launch
+    of a step: None when the feature is off (the default: nothing changes), else the RelativeDepthTerms of the step."""
+    name = getattr(cfg, "relative_depth_loss_type", "off")
+    if name == "off":
+        return None
+    if name not in L.RELATIVE_DEPTH_TYPES:
+        raise ValueError(f"relative_depth_loss_type {name!r}: the offered types are off, {', '.join(L.RELATIVE_DEPTH_TYPES)}")
+    space = getattr(cfg, "relative_depth_space", "depth")
+    if space not in ("depth", "inverse"):
+        raise ValueError(f"relative_depth_space {space!r}: the offered spaces are depth, inverse")
+    lam = float(getattr(cfg, "relative_depth_lambda", 0.1))
+    if not (lam >= 0.0 and lam < float("inf")):
+        raise ValueError(f"relative_depth_lambda must be a finite number >= 0, not {lam}")
+    patch = getattr(cfg, "relative_depth_patch", 64)
+    if patch not in L.RELATIVE_DEPTH_PATCHES:
+        raise ValueError(f"relative_depth_patch {patch!r}: the offered sizes are "
+                         f"{', '.join(map(str, L.RELATIVE_DEPTH_PATCHES))}")
+    f = float(getattr(cfg, "relative_depth_patch_min_valid", 0.25))
+    if not (f > 0.0 and f <= 1.0):
+        raise ValueError(f"relative_depth_patch_min_valid must lie in (0, 1], not {f}")
+    metric = getattr(cfg, "depth_loss_type", "L1")
+    if metric != "L1":
+        raise ValueError(f"relative_depth_loss_type {name!r} beside depth_loss_type {metric!r}: a prior known up to scale and "
+                         "shift cannot feed a metric term (leave depth_loss_type at 'L1': that term is then not computed)")
+    if not cfg.output_depth_during_training:
+        raise NotImplementedError("relative_depth_loss_type with output_depth_during_training=False: the term is taken on "
+                                  "the rendered depth")
+    return RelativeDepthTerms(L.RELATIVE_DEPTH_TYPES[name], lam, space == "inverse", patch, f,
+                              getattr(cfg, "relative_depth_patch_jitter", True))
+
+
+def _relative_depth_buffers(H: int, W: int, terms: RelativeDepthTerms, dev):
+    ws = torch.empty(terms.ws_doubles(H, W), dtype=torch.float64, device=dev)
+    parts = torch.empty(8, dtype=torch.float64, device=dev)
+    out_f = torch.empty(2, dtype=torch.float32, device=dev)
+    return ws, parts, out_f
+
+
+class _RelativeDepthLoss(torch.autograd.Function):
+    """The relative-depth term on the depth get_outputs returned (include/qed_splat.h states it): the forward is
+    qed_relative_depth_loss' reduce pass (the value and its moments, all on the device), the backward its gradient pass, which
+    folds the same workspace and reads the upstream gradient from device memory -- nothing is read back.  ``depth`` [H,W,1] or
+    [H,W], ``alpha`` the step's accumulation and ``prior`` (batch["depth_image"]) are read, only ``depth`` is differentiated."""
+
+    @staticmethod
+    def forward(ctx, depth, alpha, prior, mask, terms, offsets):
+        ctx.set_materialize_grads(False)
+        if not depth.is_cuda or depth.dtype != torch.float32:
+            raise L.QedSplatError("the relative-depth terms need float32 GPU tensors: there is no CPU path in the product")
+        H, W = depth.shape[0], depth.shape[1]
+        depth, alpha = depth.detach().contiguous(), alpha.detach().contiguous()
+        ws, parts, out_f = _relative_depth_buffers(H, W, terms, depth.device)
+        ctx.args = (H, W, L.ptr(depth), 1, L.ptr(alpha), L.ptr(prior), L.ptr(mask), *terms.scalars(offsets))
+        ctx.flags = terms.flags
+        L.check(L.load().qed_relative_depth_loss(*ctx.args, ctx.flags | L.RD_REDUCE, None, None, L.ptr(ws), None, 1,
+                                                 L.ptr(parts), L.ptr(out_f), _stream()), "qed_relative_depth_loss")
+        ctx.save_for_backward(depth, alpha, prior, mask, ws)
+        ctx.mark_non_differentiable(parts)
+        return out_f[0:1].view(()), parts
+
+    @staticmethod
+    def backward(ctx, g, _g_parts):
+        if g is None or not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        depth, ws = ctx.saved_tensors[0], ctx.saved_tensors[4]
+        if g.data_ptr() == _unit_grad(depth.device).data_ptr():   # (backward_fused()'s cached unit gradient: NULL = 1)
+            g = None
+        else:
+            g = g.to(torch.float32).reshape(1).contiguous()
+        v_depth = torch.empty_like(depth)
+        L.check(L.load().qed_relative_depth_loss(*ctx.args, ctx.flags | L.RD_GRAD, L.ptr(g), None, L.ptr(ws), L.ptr(v_depth),
+                                                 1, None, None, _stream()), "qed_relative_depth_loss")
+        return (v_depth,) + (None,) * 5
+
+
+def relative_depth_losses(depth: Tensor, alpha: Tensor, prior: Tensor, mask, terms: RelativeDepthTerms, offsets=(0, 0)):
+    """(relative_depth_loss, parts) of ``terms`` on the depth image get_outputs returned: a 0-dim device tensor,
+    differentiable in ``depth``; parts = float64 [8] {the value, |V|, rho of the whole image, s, t, B, the mean of rho_b, 0}."""
+    return _RelativeDepthLoss.apply(depth, alpha, prior, mask, terms, offsets)
+
+
+def relative_depth_pearson(depth: Tensor, alpha: Tensor, prior: Tensor, mask, terms: RelativeDepthTerms) -> Tensor:
+    """rho between ``depth`` and ``prior`` over the whole image's valid pixels, in the space of ``terms``: out[2] of a
+    reduce-only call, a 0-dim float32 device tensor (0 for a degenerate set)."""
+    H, W = depth.shape[0], depth.shape[1]
+    depth, alpha = depth.detach().contiguous(), alpha.detach().contiguous()
+    dev = depth.device
+    ws = torch.empty(L.relative_depth_ws_doubles(H, W, 0), dtype=torch.float64, device=dev)
+    parts = torch.empty(8, dtype=torch.float64, device=dev)
+    L.check(L.load().qed_relative_depth_loss(H, W, L.ptr(depth), 1, L.ptr(alpha), L.ptr(prior), L.ptr(mask),
+                                             L.RELATIVE_DEPTH_TYPES["Pearson"], 0.0, 0, 0, 0, 0.0, terms.flags | L.RD_REDUCE,
+                                             None, None, L.ptr(ws), None, 1, L.ptr(parts), None, _stream()),
+            "qed_relative_depth_loss")
+    return parts[2].to(torch.float32)

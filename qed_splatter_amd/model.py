@@ -40,7 +40,7 @@ from . import _lib as L
 from .handover import FrameOrder, Handover
 from .losses import _FusedImageLoss, _ImageLosses, _McmcReg, _f32_image, _mcmc_reg_grad_adder, _mcmc_reg_values
 from .losses import _ssim_key, _unit_grad
-from .losses import depth_losses, depth_terms
+from .losses import depth_losses, depth_terms, relative_depth_losses, relative_depth_pearson, relative_depth_terms
 from .losses import _PostProcess, _SSIM, _UNIT_GRADS, ssim  # noqa: F401  (also importable from here)
 from .optim import FlatAdam, QedAdam, QedAdamSet, exponential_decay_lr  # noqa: F401  (also importable from here)
 from .optim import _RAW_GRAD, _all_groups_stepped_by_qed_adam, _raw_grad
@@ -172,6 +172,21 @@ class QEDSplatterModelConfig:
     depth_huber_delta: float = 0.1
     depth_tv_lambda: float = 0.0
     depth_tv_edge_aware: bool = True
+    # Relative-depth supervision (losses.relative_depth_terms, include/qed_splat.h; this project's definitions in the spirit
+    # of FSGS, SparseGS and MiDaS, not checked against them): batch["depth_image"] is then a PRIOR known up to an unknown
+    # scale and shift -- a monocular network's depth, or with relative_depth_space "inverse" its inverse depth.
+    # relative_depth_loss_type: "off", "Pearson" (relative_depth_lambda (1 - rho) over the valid pixels), "PatchPearson" (the
+    # mean of 1 - rho over boxes of relative_depth_patch^2 pixels that hold at least relative_depth_patch_min_valid of valid
+    # ones; with relative_depth_patch_jitter the boxes move with the step) or "ScaleShiftL1" (mean |x - (s g + t)| with the
+    # least-squares s, t).  The metric data term is then not computed ("depth_loss" is the kernels' zero; a depth_loss_type
+    # other than "L1" is refused), depth_tv_lambda stays combinable; get_loss_dict / fused_loss add "relative_depth_loss",
+    # get_metrics_dict "depth_pearson".  It needs output_depth_during_training; "off" launches nothing new
+    relative_depth_loss_type: str = "off"
+    relative_depth_lambda: float = 0.1
+    relative_depth_space: str = "depth"
+    relative_depth_patch: int = 64
+    relative_depth_patch_min_valid: float = 0.25
+    relative_depth_patch_jitter: bool = True
 
     @classmethod
     def synthetic(cls, **kw) -> "QEDSplatterModelConfig":
@@ -806,6 +821,7 @@ class QEDSplatterModel(nn.Module):
         if self.training:
             assert camera.shape[0] == 1, "Only one camera at a time"          # model.py:211
             depth_terms(self.config)             # (config.depth_loss_type / depth_tv_lambda: refused before any launch)
+            relative_depth_terms(self.config)    # (config.relative_depth_*: as well)
             if self.camera_optimizer is not None:
                 optimized_camera_to_world = self.camera_optimizer.apply_to_camera(camera)
             else:
@@ -1125,6 +1141,7 @@ class QEDSplatterModel(nn.Module):
         gathers; each entry stays separately differentiable (the trainer sums and may weight them)."""
         cfg = self.config
         dterms = depth_terms(cfg)                # (None: the built-in depth-L1 term and nothing else)
+        rterms = relative_depth_terms(cfg)       # (None: off; else the metric data term is not computed)
         pred_img = outputs["rgb"]
         depth_out = outputs["depth"]
         if depth_out is None:
@@ -1146,13 +1163,14 @@ class QEDSplatterModel(nn.Module):
         if shared is not None and shared.get("loss") is not None:
             dc = depth_out.contiguous()
             if shared["depth_key"] == (dc.data_ptr(), dc._version, depth_batch.data_ptr(), depth_batch._version) \
-                    and shared["lambdas"] == (float(cfg.ssim_lambda), float(cfg.depth_lambda)) and dterms is None:
+                    and shared["lambdas"] == (float(cfg.ssim_lambda), float(cfg.depth_lambda)) and dterms is None \
+                    and rterms is None:
                 loss_shared = shared["loss"]
         # the accumulator of the compositing backward behind THESE outputs is zeroed by this loss's backward launch (the
         # first loss taken on them: a second one leaves the fill to the backward pass)
         handover = ctx.handover if (mine and torch.is_grad_enabled()) else None
         main, depth = _ImageLosses.apply(pred_img, depth_out, gt_img, depth_batch, mask, float(cfg.ssim_lambda),
-                                         float(cfg.depth_lambda) if dterms is None else 0.0,
+                                         float(cfg.depth_lambda) if (dterms is None and rterms is None) else 0.0,
                                          shared["maps_sum"] if shared else None, loss_shared, handover)
         depth_tv = None
         if dterms is not None:
@@ -1179,6 +1197,11 @@ class QEDSplatterModel(nn.Module):
             out["normal_loss"] = self._normal_loss_term(accum, outputs["accumulation"], target, mask)
         if self.training and (cfg.use_normal_consistency or cfg.use_normal_tv):
             self._add_normal_reg_losses(out, outputs, mask)
+        if rterms is not None:
+            # config.relative_depth_*: one more node on the same depth image, batch["depth_image"] as the prior (its gradient
+            # joins the others' in autograd)
+            out["relative_depth_loss"] = relative_depth_losses(depth_out, outputs["accumulation"], depth_batch, mask, rterms,
+                                                               rterms.offsets(self.step))[0]
         return out
 
     # ---- get_metrics_dict (model.py:120-197) ----
@@ -1213,6 +1236,17 @@ class QEDSplatterModel(nn.Module):
         # same tensors before using it)
         ctx = self.__dict__.get("_step")
         lpips_w = self._lpips_weights()
+        rterms = relative_depth_terms(self.config) if has_depth else None
+
+        def pearson(out):
+            # config.relative_depth_*: rho between the rendered depth and the prior over the valid pixels, in the configured
+            # space (the loss mask selects only where it has the render's size)
+            depth = outputs["depth"].detach()
+            depth = depth[0] if depth.dim() == 4 else depth
+            H, W = depth.shape[:2]
+            mask = self._loss_mask(batch, (H, W)) if d <= 1 else None
+            prior = _f32_image(gt_depth, H * W, "batch['depth_image']", self.device)
+            out["depth_pearson"] = relative_depth_pearson(depth, outputs["accumulation"].detach(), prior, mask, rterms)
         keep = (self.training and torch.is_grad_enabled() and self.config.ssim_lambda > 0.0 and d <= 1
                 and pred_rgb.is_cuda and pred_rgb.dtype == torch.float32 and ctx is not None and ctx.owns(outputs))
         with torch.no_grad():
@@ -1224,6 +1258,8 @@ class QEDSplatterModel(nn.Module):
                                            lpips_weights=lpips_w)
                 ctx.ssim = shared
                 out["gaussian_count"] = self.num_points
+                if rterms is not None:
+                    pearson(out)
                 return _reference_key_order(out)
             out = dict(_image_metrics(pred_rgb.detach(), gt_rgb, outputs["depth"].detach() if has_depth else None, gt_depth,
                                       keep_ssim_maps=keep, lpips_weights=lpips_w))
@@ -1232,6 +1268,8 @@ class QEDSplatterModel(nn.Module):
                 ctx.ssim = kept
             out["gaussian_count"] = self.num_points
             out["avg_min_scale"] = nanmean_exp(self.scales[..., -1])                  # model.py:192-194
+            if rterms is not None:
+                pearson(out)
         return _reference_key_order(out)
 
     # ---- get_image_metrics_and_images (splatfacto's, inherited by the reference: the evaluation dictionary) ----
@@ -1345,7 +1383,9 @@ class QEDSplatterModel(nn.Module):
         for an upstream gradient of 1); the two parts are detached views for logging.  Numerically the
         same quantities as get_outputs + get_loss_dict.
         With config.depth_loss_type / depth_tv_lambda (losses.depth_terms) ``depth_loss`` is the chosen data term and
-        ``depth_tv_loss`` the smoothness term, both detached and both part of ``loss``.
+        ``depth_tv_loss`` the smoothness term, both detached and both part of ``loss``.  With config.relative_depth_loss_type
+        (losses.relative_depth_terms) ``relative_depth_loss`` follows every other key, detached and part of ``loss``;
+        ``depth_loss`` then is the kernels' zero (batch["depth_image"] is a prior, not a metric depth).
 
         ``frame_key`` (hashable, optional): identifies the CAMERA this frame is rendered from -- the dataset's camera
         index.  Frames under one key share a launch-order buffer: the order the loss launch computes for this frame's
@@ -1384,6 +1424,12 @@ class QEDSplatterModel(nn.Module):
             self._resolve_sh_grad()               # (compact gradients of an earlier step nobody consumed: see there)
         cfg = self.config
         dterms = depth_terms(cfg)                # (config.depth_loss_type / depth_tv_lambda: refused before any launch)
+        rterms = relative_depth_terms(cfg)       # (config.relative_depth_*: as well)
+        if rterms is not None and rterms.patchwise and rterms.jitter and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("relative_depth_loss_type 'PatchPearson' with relative_depth_patch_jitter inside a captured "
+                                      "step (graph.py, segments.py): the boxes' offsets are launch constants, a replay would "
+                                      "freeze them; set relative_depth_patch_jitter=False")
+        roffsets = rterms.offsets(self.step) if rterms is not None else (0, 0)
         pose_opt = camera_optimizer if (camera_optimizer is not None and camera_optimizer.active and self.training) else None
         # (conversions of the batch are shared within a step, never across steps; parallel.py refuses a data-parallel step
         # behind either optimiser)
@@ -1461,7 +1507,7 @@ class QEDSplatterModel(nn.Module):
         if grid_opt is not None:
             return self._fused_loss_with_grid(grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags,
                                               sync, handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask,
-                                              lo, ls, mcmc_vals, normal, dterms)
+                                              lo, ls, mcmc_vals, normal, dterms, rterms, roffsets)
         # ``optimizer`` (a FlatAdam stepped with device_state=True, fused_sh=True right after this step's backward): the
         # loss pass's fold launch advances its device step state, so that the optimiser needs no launch of its own for it
         tick = None
@@ -1480,7 +1526,7 @@ class QEDSplatterModel(nn.Module):
             total, parts, *dparts = _FusedImageLoss.apply(render, alpha, bg.contiguous(), gt_rgb, gt_depth, mask,
                                                           float(cfg.ssim_lambda), cfg.depth_lambda,
                                                           handover if torch.is_grad_enabled() else None, tick, tile_cost,
-                                                          dterms)
+                                                          dterms, rterms, roffsets)
             if frame_order is not None and tile_cost is not None and float(cfg.ssim_lambda) > 0.0 \
                     and os.environ.get("QED_STEP_PASSENGERS", "1") != "0":
                 frame_order.valid = True          # (the buffer holds an order from here on, in stream order)
@@ -1494,6 +1540,8 @@ class QEDSplatterModel(nn.Module):
                 optimizer.drop_tick()
             raise
         # (config.depth_loss_type / depth_tv_lambda: the node's third output holds the two terms, already part of ``total``)
+        # (config.relative_depth_*: one more output, {relative_depth_loss, total})
+        rparts = dparts.pop() if rterms is not None else None
         depth_part = parts[1] if dterms is None else dparts[0][0]
         if mcmc_vals is None:
             out = {"loss": total, "main_loss": parts[0], "depth_loss": depth_part}
@@ -1508,6 +1556,8 @@ class QEDSplatterModel(nn.Module):
         if pose_reg is not None:
             out["loss"] = out["loss"] + pose_reg
             out["camera_opt_regularizer"] = pose_reg
+        if rparts is not None:                   # (after every other key, as in get_loss_dict)
+            out["relative_depth_loss"] = rparts[0]
         return out
 
     def _add_fused_normal_loss(self, out: Dict[str, Tensor], normal, info, render: Tensor, alpha: Tensor, mask) -> None:
@@ -1563,7 +1613,7 @@ class QEDSplatterModel(nn.Module):
 
     def _fused_loss_with_grid(self, grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags, sync,
                               handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask, lo, ls, mcmc_vals,
-                              normal=None, dterms=None):
+                              normal=None, dterms=None, rterms=None, roffsets=(0, 0)):
         """fused_loss behind ``grid_optimizer``: the loss is taken on the CORRECTED colour, so the gridless route's one
         launch from ``render`` to its gradient does not apply.  The launches are those of get_outputs -> get_loss_dict:
         the compositing forward with its post-processing epilogue (clamped colour, fixed-up depth), the slice, the SSIM
@@ -1583,7 +1633,8 @@ class QEDSplatterModel(nn.Module):
         rgb, tv = grid_opt.begin_fused(info.pop("post_rgb"), grid_idx, H, W)
         depth = info.pop("post_depth")
         main, depth_loss = _ImageLosses.apply(rgb.squeeze(0), depth.squeeze(0), gt_rgb, gt_depth, mask,
-                                              float(cfg.ssim_lambda), float(cfg.depth_lambda) if dterms is None else 0.0,
+                                              float(cfg.ssim_lambda),
+                                              float(cfg.depth_lambda) if (dterms is None and rterms is None) else 0.0,
                                               None, None, handover if grad else None)
         depth_tv = None
         if dterms is not None:                   # (config.depth_loss_type / depth_tv_lambda: get_loss_dict's node, as there)
@@ -1593,6 +1644,10 @@ class QEDSplatterModel(nn.Module):
         total = main + depth_loss + tv
         if depth_tv is not None:
             total = total + depth_tv
+        relative = None
+        if rterms is not None:                   # (config.relative_depth_*: get_loss_dict's node, as there)
+            relative = relative_depth_losses(depth.squeeze(0), alpha.squeeze(0), gt_depth, mask, rterms, roffsets)[0]
+            total = total + relative
         out = {"loss": total, "main_loss": main.detach()}
         if mcmc_vals is not None:
             out["loss"] = total + mcmc_vals[2]
@@ -1606,4 +1661,6 @@ class QEDSplatterModel(nn.Module):
             out["loss"] = out["loss"] + pose_reg
             out["camera_opt_regularizer"] = pose_reg
         out["tv_loss"] = tv
+        if relative is not None:
+            out["relative_depth_loss"] = relative.detach()
         return out

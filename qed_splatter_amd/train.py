@@ -142,6 +142,23 @@ class Trainer:
         out["gaussian_count"] = model.num_points
         return out
 
+    @torch.no_grad()
+    def depth_pearson(self):
+        """The mean of get_metrics_dict's ``depth_pearson`` over the TRAINING cameras, in eval() (None when the relative-depth
+        term is off): what the run reports where the evaluation split is empty."""
+        model = self.model
+        was_training = model.training
+        model.eval()
+        vals = []
+        try:
+            for camera, batch in self.datamanager.train_items():
+                md = model.get_metrics_dict(model.get_outputs(camera), batch)
+                if "depth_pearson" in md:
+                    vals.append(md["depth_pearson"].detach().reshape(()).float())
+        finally:
+            model.train(was_training)
+        return float(torch.stack(vals).mean()) if vals else None
+
     def evaluate_images(self, get_std: bool = True) -> Dict[str, float]:
         """The evaluation split through ``evaluate_image_items``: Nerfstudio's get_average_eval_image_metrics."""
         return evaluate_image_items(self.model, self.datamanager.eval_items(), get_std)
@@ -406,6 +423,20 @@ def build_parser() -> argparse.ArgumentParser:
                     help="weight of the total variation of the rendered depth (config.depth_tv_lambda; default 0 = off)")
     ap.add_argument("--no-depth-tv-edge-aware", action="store_true", default=argparse.SUPPRESS,
                     help="do not weight the depth smoothness term down at colour edges of the ground-truth image")
+    ap.add_argument("--relative-depth-loss", choices=("off", *L.RELATIVE_DEPTH_TYPES), default=argparse.SUPPRESS, metavar="TYPE",
+                    help="treat the depth files as a PRIOR known up to scale and shift (a monocular network's) and supervise "
+                         "with Pearson, PatchPearson or ScaleShiftL1 (config.relative_depth_loss_type, default off); the "
+                         "metric depth term is then not computed")
+    ap.add_argument("--relative-depth-lambda", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="the relative-depth term's weight (default 0.1)")
+    ap.add_argument("--relative-depth-space", choices=("depth", "inverse"), default=argparse.SUPPRESS,
+                    help="compare the prior with the rendered depth or with its reciprocal (default depth)")
+    ap.add_argument("--relative-depth-patch", type=int, default=argparse.SUPPRESS, metavar="P",
+                    help="PatchPearson's box size: 8, 16, 32, 64 or 128 pixels (default 64)")
+    ap.add_argument("--relative-depth-min-valid", type=float, default=argparse.SUPPRESS, metavar="F",
+                    help="a box contributes from this share of valid pixels on, in (0, 1] (default 0.25)")
+    ap.add_argument("--no-relative-depth-jitter", action="store_true", default=argparse.SUPPRESS,
+                    help="keep PatchPearson's boxes where they are instead of moving them with the step")
     ap.add_argument("--prune-at", type=int, nargs="+", default=argparse.SUPPRESS, metavar="STEP",
                     help="after these steps' refinement: score the training cameras and prune by blending contribution "
                          "(prune.py)")
@@ -425,6 +456,18 @@ def depth_config_of(a) -> Dict:
             "depth_huber_delta": float(getattr(a, "depth_huber_delta", cfg.depth_huber_delta)),
             "depth_tv_lambda": float(getattr(a, "depth_tv_lambda", cfg.depth_tv_lambda)),
             "depth_tv_edge_aware": not bool(getattr(a, "no_depth_tv_edge_aware", False))}
+
+
+def relative_depth_config_of(a) -> Dict:
+    """The model-config fields of the --relative-depth-* options (the config's defaults where an option is absent)."""
+    cfg = QEDSplatterModelConfig
+    return {"relative_depth_loss_type": str(getattr(a, "relative_depth_loss", cfg.relative_depth_loss_type)),
+            "relative_depth_lambda": float(getattr(a, "relative_depth_lambda", cfg.relative_depth_lambda)),
+            "relative_depth_space": str(getattr(a, "relative_depth_space", cfg.relative_depth_space)),
+            "relative_depth_patch": int(getattr(a, "relative_depth_patch", cfg.relative_depth_patch)),
+            "relative_depth_patch_min_valid": float(getattr(a, "relative_depth_min_valid",
+                                                            cfg.relative_depth_patch_min_valid)),
+            "relative_depth_patch_jitter": not bool(getattr(a, "no_relative_depth_jitter", False))}
 
 
 def prune_config_of(a):
@@ -471,9 +514,10 @@ def main(argv=None) -> Dict:
                                     use_normal_tv=bool(getattr(a, "normal_tv", False)),
                                     normal_tv_lambda=float(getattr(a, "normal_tv_lambda",
                                                                    QEDSplatterModelConfig.normal_tv_lambda)),
-                                    **depth_config_of(a))
-    from .losses import depth_terms
+                                    **depth_config_of(a), **relative_depth_config_of(a))
+    from .losses import depth_terms, relative_depth_terms
     dterms = depth_terms(config)                 # (a refused combination ends the run before the model is built)
+    rterms = relative_depth_terms(config)
     model = build_model(config, dm, a.init_from_ply, a.seed)
     print(f"seeded {model.num_points} Gaussians")
     trainer = Trainer(model, dm, seed=a.seed,
@@ -528,6 +572,10 @@ def main(argv=None) -> Dict:
         result["depth_loss"] = float(losses["depth_loss"]) if losses is not None else None
         if dterms.tv_lambda > 0.0:
             result["depth_tv_loss"] = float(losses["depth_tv_loss"]) if losses is not None else None
+    if rterms is not None:
+        # (depth_pearson, in the configured space: the evaluation split's mean; the training cameras' where that split is empty)
+        result["relative_depth_loss"] = float(losses["relative_depth_loss"]) if losses is not None else None
+        result["depth_pearson"] = metrics["depth_pearson"] if "depth_pearson" in metrics else trainer.depth_pearson()
     if output_normals:
         trainer.model.config.output_normals = True      # (from here on: the final evaluation and --render-eval only)
     if color_corrected or output_normals:
