@@ -1300,6 +1300,60 @@ int qed_surface_samples(int32_t height, int32_t width, const float* rgb, const f
                         float* colors, int32_t* n_out, int32_t* workspace, int64_t workspace_ints, int32_t* status,
                         void* stream);
 
+/* ---- growing Gaussians from sensor depth (csrc/depth_grow.hip) -------------------------------------------------------------
+ * Where one view's render misses the surface its depth image measures, new Gaussians are proposed at the measured points and
+ * appended to the flat buffers.  The rules are THIS PROJECT'S definitions, in the spirit of SplaTAM's densification (seed where
+ * the accumulated alpha is low or the rendered depth lies behind the measured one), restated from memory; they are not checked
+ * against it and are not in the reference.
+ *
+ * qed_depth_grow_candidates, one view.  gt_rgb[H,W,3] and gt_depth[H,W] (model units): the frame's ground truth as float
+ * planes at the render's size; mask[H,W] u8 (may be NULL); depth = the ACCUMULATED depth D, read at depth[p * depth_stride] (as
+ * qed_surface_samples); alpha[H,W]; viewmat[4,4]: the OpenCV world-to-camera matrix [R | t], row-major, on the DEVICE.
+ * For every stride-th pixel (x, y) in x and y, in row-major order (the order is the contract), with d = gt_depth, the pixel
+ * is a CANDIDATE when
+ *   1. it has a measurement: d finite, d > 0, depth_min <= d <= depth_max, and (mask == NULL or mask != 0); and
+ *   2. it is a HOLE, alpha < hole_alpha, or -- only where alpha >= hole_alpha and z = D / alpha is finite -- the render lies
+ *      BEHIND the measurement, z > d + max(depth_tol, depth_tol_rel * d).  The hole test comes first: alpha == 0 never
+ *      divides.  (depth_tol = depth_tol_rel = +inf: holes only.)
+ * All comparisons in double on the float32 inputs (the thresholds are float32 values).  K = the number of candidates (it stays
+ * on the device); cap = capacity, the most rows this view may add.  K <= cap: candidate j (0-based, pixel order) goes to row
+ * j.  K > cap: candidate j is kept iff floor((j + 1) cap / K) > floor(j cap / K) and goes to row floor(j cap / K), in 64-bit
+ * integers: exactly cap candidates, spread evenly in pixel order.  Per kept candidate, in double, rounded to float32 once:
+ *   P = ((x + .5 - cx) d / fx, (y + .5 - cy) d / fy, d)   the renderer's pixel centres, as qed_surface_samples;
+ *   points[row] = R^T (P - t);
+ *   log_scale[row] = log(scale_factor * stride * d / (0.5 (fx + fy)))   one sampled pixel's footprint at that depth;
+ *   colors[row] = gt_rgb at the pixel.
+ * points / colors[capacity,3], log_scale[capacity]; rows from min(K, cap) on are not written.  n_out[1] (device) = min(K, cap);
+ * status[QED_STATUS_WORDS] is written by the call: [0] = K, [1] = the hole candidates, [2] = the behind candidates, the rest 0.
+ * Deterministic (count / scan / write, no atomic counter, no host read-back): two calls give the same bits.  workspace:
+ * qed_depth_grow_workspace_ints(height, width, stride) int32.  No allocation, no sync; height * width == 0 launches nothing
+ * (n_out and status are then left as they are).
+ * Refused on the host: null required buffers, stride < 1, depth_stride < 1, non-finite intrinsics, fx or fy == 0, depth_min >
+ * depth_max (or either NaN), a negative (or NaN) tolerance, a NaN hole_alpha, a scale_factor that is not positive and finite,
+ * a negative capacity; a short workspace returns QED_E_WORKSPACE.
+ *
+ * qed_grow_append: old flat parameters and both Adam moments of n Gaussians (begins h_old_begin[7], host, as
+ * qed_densify_emit) and k candidate rows -> the buffers of n + k Gaussians (begins h_new_begin[7]), one launch.  Rows [0, n)
+ * of every group are copied bit for bit, in params, exp_avg and exp_avg_sq.  Rows [n, n + k): means = points; scales =
+ * log_scale in all three columns; quats = (1, 0, 0, 0); opacities = logit(init_opacity); features_dc = (c - 0.5) /
+ * 0.28209479177387814 for sh_coeffs > 1 and logit(c, eps = 1e-10) for sh_coeffs == 1 (sh_coeffs from the width of
+ * features_rest), in double, rounded once, as qed_seed_gaussians; features_rest = 0; both moments 0.  k is a HOST value (the
+ * caller has read n_out: the one sync of a growth); k == 0 is a plain copy, n == 0 is legal, n + k == 0 launches nothing.
+ * Refused on the host: n or k negative or n + k >= 2^30, a layout whose groups are not width x rows in the order means,
+ * scales, quats, opacities, features_dc, features_rest, init_opacity outside (0, 1), null buffers that would be read or
+ * written. */
+int64_t qed_depth_grow_workspace_ints(int32_t height, int32_t width, int32_t stride);
+int qed_depth_grow_candidates(int32_t height, int32_t width, const float* gt_rgb, const float* gt_depth, const uint8_t* mask,
+                              const float* depth, int32_t depth_stride, const float* alpha, float fx, float fy, float cx,
+                              float cy, const float* viewmat, int32_t stride, float hole_alpha, float depth_tol,
+                              float depth_tol_rel, float depth_min, float depth_max, float scale_factor, int64_t capacity,
+                              float* points, float* log_scale, float* colors, int32_t* n_out, int32_t* workspace,
+                              int64_t workspace_ints, int32_t* status, void* stream);
+int qed_grow_append(int32_t n, int32_t k, const float* old_params, const float* old_exp_avg, const float* old_exp_avg_sq,
+                    const int64_t* h_old_begin, const float* points, const float* log_scale, const float* colors,
+                    float init_opacity, float* new_params, float* new_exp_avg, float* new_exp_avg_sq,
+                    const int64_t* h_new_begin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

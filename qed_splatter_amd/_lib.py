@@ -135,6 +135,10 @@ SIGNATURES = {
     "qed_surface_workspace_ints": (_L, [_I, _I, _I]),
     "qed_surface_samples": (C.c_int, [_I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _I, _F, _F, _F, _I, _F, _F,
                                       _L, _P, _P, _P, _P, _P, _L, _P, _P]),
+    "qed_depth_grow_workspace_ints": (_L, [_I, _I, _I]),
+    "qed_depth_grow_candidates": (C.c_int, [_I, _I, _P, _P, _P, _P, _I, _P, _F, _F, _F, _F, _P, _I, _F, _F, _F, _F, _F, _F, _L,
+                                            _P, _P, _P, _P, _P, _L, _P, _P]),
+    "qed_grow_append": (C.c_int, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P]),
 }
 
 class Post(C.Structure):

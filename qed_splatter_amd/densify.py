@@ -63,7 +63,9 @@ class Densifier:
 
     # ---- SplatfactoModel.after_train ----
     @torch.no_grad()
-    def after_train(self, step: int) -> None:
+    def after_train(self, step: int, n_rendered: Optional[int] = None) -> None:
+        """``n_rendered``: the rows the step rendered, when depth_grow.grow appended Gaussians between the step's render and
+        this call (None: all of them).  The step's statistics go to those rows; the appended ones keep their initial values."""
         m = self.model
         if step >= self.config.stop_split_at:
             return
@@ -74,6 +76,9 @@ class Densifier:
         if self.max_2Dsize is None:
             self.max_2Dsize = torch.zeros(n, dtype=torch.float32, device=m.device)
         absgrad = m.xys.absgrad                                   # [1,N,2], a strided view of the vsplat rows
+        if n_rendered is not None:
+            assert 0 <= n_rendered <= n, "n_rendered: the rows of the step's render, at most the model's"
+            n = int(n_rendered)                                   # (the kernel walks the first n entries of the statistics)
         assert absgrad.shape == (1, n, 2) and absgrad.stride(2) == 1, "absgrad must be [1,N,2] with unit inner stride"
         radii = m.radii.to(torch.int32).contiguous()
         L.check(L.load().qed_densify_accumulate(n, L.ptr(absgrad), absgrad.stride(1), L.ptr(radii),

@@ -6,6 +6,9 @@
                                      [--use-bilateral-grid [--grid-shape 16 16 8]] [--color-corrected-metrics]
                                      [--prune-at STEP [STEP ...] [--prune-min-score X | --prune-keep-fraction F]
                                       [--prune-score max|sum] [--prune-view-stride S]]
+                                     [--grow-from-depth-every K [--grow-start STEP] [--grow-until STEP] [--grow-stride S]
+                                      [--grow-hole-alpha A] [--grow-depth-tol T] [--grow-depth-tol-rel R]
+                                      [--grow-init-opacity O] [--grow-max-new M] [--grow-max-gaussians G]]
 
 The dataset is read by ``dataparser.parse_dataset``, cached by ``datamanager.FullImageDatamanager`` (uint8 images on
 the GPU), and every step takes the next training camera and its frame through the eager fused route: ``fused_loss``
@@ -26,6 +29,10 @@ color_correct.py) -- the figures that do not measure the cameras' exposure diffe
 ``--prune-at`` scores every Gaussian by its blending contribution over the training cameras after the named steps'
 refinement and drops the low scorers from the model and the optimiser (prune.py, csrc/importance.hip); the last JSON line
 then carries ``"prune": [{"step", "n_before", "n_after", "seconds"}]``.
+
+``--grow-from-depth-every K`` seeds new Gaussians from the step's own depth image every K-th step between ``--grow-start``
+and ``--grow-until``, where that camera's render has a hole or lies behind the measurement (depth_grow.py,
+csrc/depth_grow.hip); the last JSON line then carries ``"grown": {"calls", "n_added", "n_holes", "n_behind"}``.
 
 The Gaussians are seeded from the dataset's ``ply_file_path`` (``--init-from-ply`` overrides it) in the frame of the
 cameras, or from random points when there is none.  Every ``--eval-every`` steps and at the end the evaluation split
@@ -58,14 +65,25 @@ class Trainer:
 
     def __init__(self, model: QEDSplatterModel, datamanager: FullImageDatamanager, seed: int = 0,
                  densify_config: Optional[DensifyConfig] = None, camera_opt_config: Optional[CameraOptimizerConfig] = None,
-                 grid_opt_config: Optional[BilateralGridOptimizerConfig] = None):
+                 grid_opt_config: Optional[BilateralGridOptimizerConfig] = None, grow_config=None, grow_every: int = 0,
+                 grow_start: Optional[int] = None, grow_until: Optional[int] = None):
+        """``grow_config`` (a depth_grow.GrowConfig) with ``grow_every`` = K > 0: every K-th step from ``grow_start`` (default:
+        the densifier's warmup_length) up to, not including, ``grow_until`` (default: its stop_split_at) grows Gaussians from
+        that step's depth image."""
         self.model, self.datamanager, self.seed = model, datamanager, int(seed)
+        self.grow_config, self.grow_every = grow_config, int(grow_every)
+        self.grow_start, self.grow_until = grow_start, grow_until
+        self.grown = {"calls": 0, "n_added": 0, "n_holes": 0, "n_behind": 0}
         self.densify_config = densify_config
         self.grid_opt_config = grid_opt_config
         self.step = 0
         self.camera_optimizer: Optional[CameraOptimizer] = None
         if camera_opt_config is not None and camera_opt_config.mode != "off":
             self.camera_optimizer = CameraOptimizer(camera_opt_config, datamanager.num_train, model.device)
+        if self.grow_every > 0:
+            from .depth_grow import GrowConfig, _refuse
+            self.grow_config = (self.grow_config or GrowConfig()).validate()
+            _refuse(model, "Trainer(grow_every=...)", self.camera_optimizer)       # (before any step is taken)
         self._bind_optimizer()
 
     def _bind_optimizer(self) -> None:
@@ -96,11 +114,37 @@ class Trainer:
         self.optimizer.step(fused_sh=True)
         if grid_opt is not None:
             grid_opt.step_fused(step)           # every grid's TV gradient, this camera's slab gradient, Adam: one launch
-        self.densifier.after_train(step)
+        # growth from this step's depth image: after the optimiser step and before the densifier's statistics, which then
+        # go to the rows this step rendered while the appended rows start from their initial values
+        n_rendered = None
+        if self._grow_due(step):
+            n_rendered = model.num_points
+            self.grow(camera, batch)
+        self.densifier.after_train(step, n_rendered)
         if step % self.densifier.config.refine_every == 0:
             self.densifier.refinement_after(step)
         self.step = step + 1
         return losses
+
+    def _grow_due(self, step: int) -> bool:
+        if self.grow_every <= 0 or step % self.grow_every != 0:
+            return False
+        cfg = self.densifier.config
+        start = cfg.warmup_length if self.grow_start is None else int(self.grow_start)
+        until = cfg.stop_split_at if self.grow_until is None else int(self.grow_until)
+        return start <= step < until
+
+    def grow(self, camera, batch) -> Dict:
+        """Seed Gaussians from ``batch``'s depth image where ``camera``'s render misses the surface (depth_grow.py): the
+        model, the optimiser's moments and the densifier's running statistics grow together.  Returns depth_grow.grow's dict
+        and adds it to ``self.grown``."""
+        from .depth_grow import GrowConfig, grow_from_view
+        info = grow_from_view(self.model, self.optimizer, camera, batch, self.grow_config or GrowConfig(),
+                              densifier=self.densifier, camera_optimizer=self.camera_optimizer)
+        self.grown["calls"] += 1
+        for key in ("n_added", "n_holes", "n_behind"):
+            self.grown[key] += int(info[key])
+        return info
 
     def prune(self, config, view_stride: int = 1) -> Dict:
         """Score the training cameras (every ``view_stride``-th, in evaluation mode, the dataset's masks as pixel masks) and
@@ -446,6 +490,26 @@ def build_parser() -> argparse.ArgumentParser:
                     help="keep the best ceil(F N) rows instead")
     ap.add_argument("--prune-score", choices=("max", "sum"), default=argparse.SUPPRESS)
     ap.add_argument("--prune-view-stride", type=int, default=argparse.SUPPRESS, metavar="S", help="score every S-th camera")
+    ap.add_argument("--grow-from-depth-every", type=int, default=argparse.SUPPRESS, metavar="K",
+                    help="every K-th step: seed new Gaussians from the step's depth image where its camera's render has a "
+                         "hole or lies behind the measurement (depth_grow.py); not with --camera-optimizer or "
+                         "--relative-depth-loss")
+    ap.add_argument("--grow-start", type=int, default=argparse.SUPPRESS, metavar="STEP",
+                    help="the first step that may grow (default: the densifier's warmup_length, 500)")
+    ap.add_argument("--grow-until", type=int, default=argparse.SUPPRESS, metavar="STEP",
+                    help="growth stops at this step (default: the densifier's stop_split_at, 15000)")
+    ap.add_argument("--grow-stride", type=int, default=argparse.SUPPRESS, metavar="S", help="look at every S-th pixel (default 2)")
+    ap.add_argument("--grow-hole-alpha", type=float, default=argparse.SUPPRESS, metavar="A",
+                    help="a pixel whose accumulated alpha is below A is a hole (default 0.5)")
+    ap.add_argument("--grow-depth-tol", type=float, default=argparse.SUPPRESS, metavar="T",
+                    help="the render is behind the measurement d beyond max(T, R d), T in model units (default 0)")
+    ap.add_argument("--grow-depth-tol-rel", type=float, default=argparse.SUPPRESS, metavar="R", help="(default 0.05)")
+    ap.add_argument("--grow-init-opacity", type=float, default=argparse.SUPPRESS, metavar="O",
+                    help="the new Gaussians' opacity (default 0.5)")
+    ap.add_argument("--grow-max-new", type=int, default=argparse.SUPPRESS, metavar="M",
+                    help="at most M new Gaussians per growth, spread evenly over the candidates (default 50000)")
+    ap.add_argument("--grow-max-gaussians", type=int, default=argparse.SUPPRESS, metavar="G",
+                    help="growth never takes the model past G Gaussians (default: no limit)")
     return ap
 
 
@@ -484,8 +548,33 @@ def prune_config_of(a):
     return PruneConfig(score=score, min_score=0.01 if min_score is None else float(min_score), keep_fraction=keep)
 
 
+def grow_config_of(a):
+    """``(GrowConfig, every)`` of the --grow-* options, ``(None, 0)`` without --grow-from-depth-every.  The combinations
+    depth_grow.grow refuses end the run here, when the arguments are parsed."""
+    every = int(getattr(a, "grow_from_depth_every", 0) or 0)
+    if every <= 0:
+        if getattr(a, "grow_from_depth_every", None) is not None:
+            raise SystemExit("--grow-from-depth-every: a positive number of steps")
+        return None, 0
+    if a.camera_optimizer != "off":
+        raise SystemExit("--grow-from-depth-every with --camera-optimizer: the pose growth would back-project with is not "
+                         "the one training renders with")
+    if getattr(a, "relative_depth_loss", "off") != "off":
+        raise SystemExit("--grow-from-depth-every with --relative-depth-loss: the depth files are then a prior of unknown "
+                         "scale and cannot place a point")
+    from .depth_grow import GrowConfig
+    names = {"grow_stride": "stride", "grow_hole_alpha": "hole_alpha", "grow_depth_tol": "depth_tol",
+             "grow_depth_tol_rel": "depth_tol_rel", "grow_init_opacity": "init_opacity", "grow_max_new": "max_new_per_view",
+             "grow_max_gaussians": "max_gaussians"}
+    try:
+        return GrowConfig(**{field: getattr(a, opt) for opt, field in names.items() if hasattr(a, opt)}).validate(), every
+    except ValueError as e:
+        raise SystemExit(f"--grow-*: {e}")
+
+
 def main(argv=None) -> Dict:
     a = build_parser().parse_args(argv)
+    grow_config, grow_every = grow_config_of(a)
     color_corrected = bool(getattr(a, "color_corrected_metrics", False))
     output_normals = bool(getattr(a, "output_normals", False))
     if a.use_bilateral_grid:
@@ -521,7 +610,9 @@ def main(argv=None) -> Dict:
     model = build_model(config, dm, a.init_from_ply, a.seed)
     print(f"seeded {model.num_points} Gaussians")
     trainer = Trainer(model, dm, seed=a.seed,
-                      camera_opt_config=CameraOptimizerConfig(mode=a.camera_optimizer, lr=a.camera_opt_lr))
+                      camera_opt_config=CameraOptimizerConfig(mode=a.camera_optimizer, lr=a.camera_opt_lr),
+                      grow_config=grow_config, grow_every=grow_every, grow_start=getattr(a, "grow_start", None),
+                      grow_until=getattr(a, "grow_until", None))
     if a.resume:
         trainer.resume(a.resume)
         print(f"resumed {a.resume} at step {trainer.step} with {trainer.model.num_points} Gaussians")
@@ -559,6 +650,8 @@ def main(argv=None) -> Dict:
               "eval": metrics, "gaussian_count": trainer.model.num_points}
     if prune_config is not None:
         result["prune"] = prune_log
+    if grow_every:
+        result["grown"] = dict(trainer.grown)
     if trainer.camera_optimizer is not None:
         result["camera_opt"] = trainer.camera_opt_metrics()
     if trainer.grid_optimizer is not None:
