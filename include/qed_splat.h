@@ -71,7 +71,8 @@ extern "C" {
  *      formed at double precision, as the host-state path forms them.
  * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_gaussian_normals,
  * qed_normal_maps, qed_depth_normals, qed_angular_error; qed_normal_loss, qed_gaussian_normals_bwd, qed_normal_rows_merge;
- * qed_normal_consistency, qed_normal_rows_merge_depth; qed_depth_loss; qed_relative_depth_loss). */
+ * qed_normal_consistency, qed_normal_rows_merge_depth; qed_depth_loss; qed_relative_depth_loss; qed_depth_spread_fwd,
+ * qed_depth_spread_bwd, qed_depth_distortion_loss). */
 #define QED_ABI_VERSION 4
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
@@ -1353,6 +1354,50 @@ int qed_grow_append(int32_t n, int32_t k, const float* old_params, const float* 
                     const int64_t* h_old_begin, const float* points, const float* log_scale, const float* colors,
                     float init_opacity, float* new_params, float* new_exp_avg, float* new_exp_avg_sq,
                     const int64_t* h_new_begin, void* stream);
+
+/* ---- depth spread along the ray and the depth distortion loss (csrc/depth_spread.hip) ---------------------------------------
+ * How the blending weights of a pixel are spread in depth: Mip-NeRF 360's distortion loss in the squared form 2DGS uses for
+ * splats, RESTATED FROM MEMORY of those papers, not checked against their code and not in the reference.
+ * Per pixel, over the Gaussians the colour pass applied there -- the same records, ids and offsets, the same accept / skip /
+ * terminate decisions as qed_composite_fwd (and qed_contribution) -- with the weights w_i = alpha_i T_i and the depths z_i =
+ * slot 9 of the record:
+ *   A = sum w_i,   m = sum w_i z_i / A,   S = sum w_i (z_i - m)^2
+ *   spread     L = A S = sum_{i<j} w_i w_j (z_i - z_j)^2
+ *   depth_std    = sqrt(S / A)                  the weighted standard deviation of the depth along the ray (0 where A == 0)
+ * Both are in the model's units (after the dataparser's scale) and exactly 0 where one Gaussian contributes.
+ *
+ * qed_depth_spread_fwd writes four planes [C,H,W]: spread; mean_u = m - z_ref, the mean ANCHORED at z_ref = the depth of the
+ * tile's first list entry (0 where A == 0); acc = A; depth_std (may be NULL).  The sums run in float32 by the weighted Welford
+ * update on u_i = z_i - z_ref (L from the raw moments A sum w z^2 - (sum w z)^2 cancels on a thin surface); pixels of empty
+ * tiles get zeros; N == 0 or flatten_ids == NULL (an empty list) zero the planes.  launch_flags: QED_CL_NO_CULL is honoured
+ * (bit-identical planes); the launch-shape bits are ignored (always one wave per tile).
+ *
+ * qed_depth_spread_bwd: the gradient of sum_p v_p L_p for a per-pixel factor image v[C,H,W], walked back to front from the
+ * colour pass's last_ids with its t_final (both required, [C,H,W]) and the three planes of the forward call:
+ *   d / d w_i     = v_p (S + A (z_i - m)^2) = g_i
+ *   d / d z_i     = 2 v_p A w_i (z_i - m)                                 -> slot 11 of the row
+ *   d / d alpha_i = T_i g_i - (sum_{j>i} w_j g_j) / (1 - alpha_i)         then qed_composite_bwd's own chain to the opacity
+ *                   (slot 7), the conic (4..6) and the 2-D mean (0, 1); a clamped alpha passes nothing.
+ * One add per (tile, Gaussian) and value into rows[C*N][16], qed_project_bwd's layout, which the caller zeroes; the absgrad
+ * slots 2, 3, the colour slots 8..10 and the padding are not touched.  tile_cost / order_ws / QED_CL_ORDER_READY: as
+ * qed_composite_bwd (costliest tiles first; every tile stays one whole-tile wave); QED_CL_NO_CULL is honoured; a forced
+ * launch shape only selects the plain tile order.  Same gradients up to the order of the float atomics.
+ *
+ * qed_depth_distortion_loss: loss[1] = lambda * mean of spread over the n_pix pixels whose mask (float, may be NULL = all) is
+ * not 0, or 0 when there is none, and -- with v (may be NULL) -- v[n_pix] = lambda / count at those pixels, 0 elsewhere: the
+ * factor image of qed_depth_spread_bwd for an upstream gradient of 1.  Sum and count are doubles, folded in a fixed order:
+ * no float atomics, no host read-back, the same bits on every run.  workspace: QED_DEPTH_DISTORTION_WS_DOUBLES doubles; its
+ * last two hold the sum and the count afterwards.  Refused on the host: a negative or non-finite lambda. */
+#define QED_DEPTH_DISTORTION_WS_DOUBLES (2 * 256 + 2)
+int qed_depth_spread_fwd(int32_t C, int32_t N, const float* splats, const int32_t* flatten_ids, const int32_t* offsets,
+                         int32_t width, int32_t height, int32_t tile_w, int32_t tile_h, float* spread, float* mean_u,
+                         float* acc, float* depth_std, int32_t launch_flags, void* stream);
+int qed_depth_spread_bwd(int32_t C, int32_t N, const float* splats, const int32_t* flatten_ids, const int32_t* offsets,
+                         int32_t width, int32_t height, int32_t tile_w, int32_t tile_h, const float* t_final,
+                         const int32_t* last_ids, const float* spread, const float* mean_u, const float* acc, const float* v,
+                         float* rows, const int32_t* tile_cost, int32_t* order_ws, int32_t launch_flags, void* stream);
+int qed_depth_distortion_loss(int64_t n_pix, const float* spread, const float* mask, float lambda, double* workspace,
+                              float* v, float* loss, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """Evaluate a checkpoint on a dataset -- what ``ns-eval --load-config ... --output-path OUT.json`` does in the reference:
 
     python -m qed_splatter_amd.eval --load CKPT --data DIR --output-path OUT.json [--color-corrected-metrics]
-                                    [--lpips-weights W] [--split eval|train|all] [--output-normals]
+                                    [--lpips-weights W] [--split eval|train|all] [--output-normals] [--output-depth-spread]
 
 The model and the cameras are built as ``render.py dataset`` builds them (``load_model``, the dataparser options of the
 training run, checked against the checkpoint's ``dataparser_scale``); every frame of the split goes through ``eval()`` /
@@ -41,6 +41,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--output-normals", action="store_true",
                     help="also normal_depth_mae / normal_sensor_mae / normal_sensor_under_*: angular errors, in degrees, of the "
                          "rendered normal maps against the normals of the rendered and of the sensor depth (normals.py)")
+    ap.add_argument("--output-depth-spread", action="store_true",
+                    help="also depth_std_mean: the depth standard deviation along each ray (model units), averaged over the "
+                         "pixels with accumulation >= 0.5 (depth_distortion.py)")
     ap.add_argument("--lpips-weights", metavar="W", default=None,
                     help="LPIPS weights: one merged file, or AlexNet's and the lin layers' files joined by the path separator")
     ap.add_argument("--split", choices=("eval", "train", "all"), default="eval")
@@ -77,6 +80,7 @@ def main(argv=None) -> Dict:
     model.config.color_corrected_metrics = bool(a.color_corrected_metrics)
     model.config.lpips_weights = a.lpips_weights
     model.config.output_normals = bool(a.output_normals)
+    model.config.output_depth_spread = bool(a.output_depth_spread)
     dp_cfg = DataparserConfig(orientation_method=a.orientation_method, center_method=a.center_method,
                               auto_scale_poses=a.auto_scale_poses == "True",
                               depth_unit_scale_factor=a.depth_unit_scale_factor,

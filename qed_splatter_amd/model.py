@@ -187,6 +187,19 @@ class QEDSplatterModelConfig:
     relative_depth_patch: int = 64
     relative_depth_patch_min_valid: float = 0.25
     relative_depth_patch_jitter: bool = True
+    # Depth distortion (depth_distortion.py, include/qed_splat.h; Mip-NeRF 360's distortion loss in the squared form 2DGS uses
+    # for splats, restated from memory): depth_distortion_lambda * the mean over the loss mask of the per-pixel spread
+    # L = sum_{i<j} w_i w_j (z_i - z_j)^2 of the blending weights in depth, from step depth_distortion_from_step on (before
+    # it, and with lambda 0, the term launches nothing and its key is absent).  In the model's units (after the dataparser's
+    # scale).  It combines with every depth, relative-depth and normal option, with strategy "mcmc" and with a camera
+    # optimiser; get_loss_dict / fused_loss add "depth_distortion_loss".  It needs output_depth_during_training; refused in a
+    # captured step and by the data-parallel exchange; such a step takes the eager route (no captured segment)
+    depth_distortion_lambda: float = 0.0
+    depth_distortion_from_step: int = 0
+    # get_outputs() outside training also returns "depth_std" [H,W,1]: the weighted standard deviation of the depth along
+    # each pixel's ray (depth_distortion.depth_spread; 0 where nothing was composited); get_image_metrics_and_images then
+    # reports "depth_std_mean" over the pixels with accumulation >= 0.5.  Training is unaffected by this flag
+    output_depth_spread: bool = False
 
     @classmethod
     def synthetic(cls, **kw) -> "QEDSplatterModelConfig":
@@ -278,14 +291,22 @@ class StepContext:
     And two facts about the forward call itself, which the data-parallel exchanges refuse (parallel.py):
     ``pose_optimizer`` / ``grid_optimizer``, the camera and bilateral-grid optimisers ``fused_loss`` ran with, and
     ``normal_loss``, whether the step carries the normal loss, ``normal_reg``, whether it carries the normal consistency or
-    smoothness term."""
+    smoothness term, ``depth_distortion``, whether it carries the depth distortion term.
 
-    __slots__ = ("rgb", "handover", "_gt", "ssim", "pose_optimizer", "grid_optimizer", "normal_loss", "normal_reg")
+    ``distortion_inputs`` is no optimisation: get_outputs leaves what get_loss_dict's depth distortion term needs and the
+    outputs do not carry -- (the colour pass's render, its records and lists, lambda, the accumulation tensor the outputs
+    hold) -- and get_loss_dict takes the term only on outputs whose accumulation is that tensor."""
 
-    def __init__(self, pose_optimizer=None, grid_optimizer=None, normal_loss=False, normal_reg=False):
+    __slots__ = ("rgb", "handover", "_gt", "ssim", "pose_optimizer", "grid_optimizer", "normal_loss", "normal_reg",
+                 "depth_distortion", "distortion_inputs")
+
+    def __init__(self, pose_optimizer=None, grid_optimizer=None, normal_loss=False, normal_reg=False,
+                 depth_distortion=False):
         self.rgb = None
         self.normal_loss = bool(normal_loss)          # the step renders normals for config.use_normal_loss
         self.normal_reg = bool(normal_reg)            # ... for config.use_normal_consistency / use_normal_tv
+        self.depth_distortion = bool(depth_distortion)    # ... carries config.depth_distortion_lambda's term
+        self.distortion_inputs = None
         self.handover = None
         self._gt = None
         self.ssim = None
@@ -863,7 +884,9 @@ class QEDSplatterModel(nn.Module):
         want_c, want_tv = self._normal_reg_wanted() if torch.is_grad_enabled() else (False, False)
         if want_c or want_tv:
             self._refuse_normal_reg(want_c, self.camera_optimizer, False)
-        ctx = attrs["_step"] = StepContext(normal_loss=want_nloss, normal_reg=want_c or want_tv)
+        # config.depth_distortion_lambda: the term's lambda for this step (0: off), refused before any launch
+        lam_dd = self._depth_distortion_lambda() if torch.is_grad_enabled() else 0.0
+        ctx = attrs["_step"] = StepContext(normal_loss=want_nloss, normal_reg=want_c or want_tv, depth_distortion=lam_dd > 0.0)
         want_npass = want_nloss or want_c or want_tv
 
         if self.config.rasterize_mode not in ["antialiased", "classic"]:      # model.py:253-254
@@ -884,6 +907,8 @@ class QEDSplatterModel(nn.Module):
         background = self._get_background_color()
         # config.output_normals: evaluation and rendering only (the records of the projection stay reachable for it)
         want_normals = bool(getattr(self.config, "output_normals", False)) and not self.training
+        # config.output_depth_spread: evaluation and rendering only, from the same records
+        want_spread = bool(getattr(self.config, "output_depth_spread", False)) and not self.training
         quat_sink = None
         if want_npass:
             from .normals import QuatGradSink
@@ -913,13 +938,15 @@ class QEDSplatterModel(nn.Module):
                 _means2d_leaf=True,     # xys is only retained and read (below; densify.py): its gradient arrives as a view
                 # (_score_records: prune.score_views walks this call's lists once more)
                 _capture_slot=capture_slot, _manual=manual,
-                _keep_records=want_normals or want_npass or bool(attrs.get("_score_records")), _post_bwd=quat_sink,
+                _keep_records=(want_normals or want_npass or want_spread or lam_dd > 0.0
+                               or bool(attrs.get("_score_records"))), _post_bwd=quat_sink,
                 # (a captured backward pass always writes the compact form; _SegmentFn.backward asks per replay)
                 _lazy_sh=self._lazy_sh_begin if (lazy and manual is None) else None)
 
         seg = None
         if (self.training and self.config.graph_segments and cam_c2w is not None and crop_ids is None
-                and torch.is_grad_enabled() and self.config.async_intersection_count and not want_npass):
+                and torch.is_grad_enabled() and self.config.async_intersection_count and not want_npass
+                and lam_dd == 0.0):
             seg = self._outputs_segment(W, H, render_mode, sh_degree_to_use, flags, render_fn, cam_c2w, background)
         if seg is not None:
             rgb, alpha, depth_im = seg.run(cam_c2w[0], cam_c2w[1], background)
@@ -972,6 +999,17 @@ class QEDSplatterModel(nn.Module):
             "accumulation": alpha.squeeze(0),
             "background": background,
         }
+        if want_spread or lam_dd > 0.0:
+            # (before the normal outputs below drop the records from info)
+            records = {k: info[k] for k in ("_splats", "_isect_offsets_full", "flatten_ids", "width", "height", "tile_width",
+                                            "tile_height")}
+            if want_spread:
+                from .depth_distortion import depth_spread
+                if viewmat.shape[0] != 1:
+                    raise NotImplementedError("output_depth_spread needs the render of one camera (evaluation mode)")
+                outputs["depth_std"] = depth_spread(records, 1, means_crop.shape[0])[1][0].unsqueeze(-1)
+            else:
+                ctx.distortion_inputs = (render, records, lam_dd, outputs["accumulation"])
         if want_normals:
             outputs.update(self._normal_outputs(means_crop, quats_crop, scales_crop, viewmat, K, info, render, alpha))
         if want_c or want_tv:
@@ -985,7 +1023,27 @@ class QEDSplatterModel(nn.Module):
             info.pop("_isect_offsets_full", None)
             accum._qed_intrinsics = self._host_intrinsics(cam_c2w, K)      # (get_loss_dict: the depth target's normals)
             outputs["normal_accum"] = accum
+        if (want_spread or lam_dd > 0.0) and not attrs.get("_score_records"):
+            info.pop("_splats", None)            # (as in _normal_outputs: not kept alive by self.info)
+            info.pop("_isect_offsets_full", None)
         return outputs
+
+    def _depth_distortion_lambda(self) -> float:
+        """config.depth_distortion_lambda for this step: 0 outside training, with lambda 0 and before
+        depth_distortion_from_step (the term then launches nothing); the term's refusals, before any launch of the step."""
+        cfg = self.config
+        lam = float(getattr(cfg, "depth_distortion_lambda", 0.0))
+        if not (0.0 <= lam < float("inf")):
+            raise ValueError(f"depth_distortion_lambda must be a finite number >= 0, not {lam}")
+        if lam == 0.0 or not self.training or int(self.step) < int(getattr(cfg, "depth_distortion_from_step", 0)):
+            return 0.0
+        if not cfg.output_depth_during_training:
+            raise NotImplementedError("depth_distortion_lambda with output_depth_during_training=False: the term's depth "
+                                      "gradient reaches the Gaussians through the depth channel of the colour pass")
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("depth_distortion_lambda inside a captured step (graph.py, segments.py): the term hands "
+                                      "its rows from one autograd node to another on the host, per step")
+        return lam
 
     def _normal_reg_wanted(self) -> Tuple[bool, bool]:
         """(consistency term, smoothness term) of this training step: config.use_normal_consistency from
@@ -1197,6 +1255,12 @@ class QEDSplatterModel(nn.Module):
             out["normal_loss"] = self._normal_loss_term(accum, outputs["accumulation"], target, mask)
         if self.training and (cfg.use_normal_consistency or cfg.use_normal_tv):
             self._add_normal_reg_losses(out, outputs, mask)
+        dd = ctx.distortion_inputs if (ctx is not None and self.training) else None
+        if dd is not None and outputs.get("accumulation") is dd[3]:
+            # config.depth_distortion_lambda: a node behind the colour pass of THESE outputs (get_outputs left its render and
+            # records); its rows join the colour pass's in the compositing backward
+            from .depth_distortion import depth_distortion_loss
+            out["depth_distortion_loss"] = depth_distortion_loss(dd[0], dd[1], mask, dd[2])
         if rterms is not None:
             # config.relative_depth_*: one more node on the same depth image, batch["depth_image"] as the prior (its gradient
             # joins the others' in autograd)
@@ -1296,6 +1360,11 @@ class QEDSplatterModel(nn.Module):
                             "cc_lpips": _lpips_or_nan(cc_rgb, gt_rgb, lpips_w)})
         if outputs.get("normal") is not None and outputs.get("normal_valid") is not None:
             metrics.update(self._normal_metrics(outputs, batch))
+        if outputs.get("depth_std") is not None:
+            # config.output_depth_spread: the mean depth standard deviation along the ray over the pixels with accumulation
+            # >= 0.5 (model units; 0 when there is none)
+            from .depth_distortion import masked_mean
+            metrics["depth_std_mean"] = masked_mean(outputs["depth_std"], outputs["accumulation"] >= 0.5)
         return metrics, {"img": torch.cat([gt_rgb, rgb], dim=1)}
 
     def _normal_metrics(self, outputs, batch) -> Dict[str, Tensor]:
@@ -1443,7 +1512,8 @@ class QEDSplatterModel(nn.Module):
         want_c, want_tv = self._normal_reg_wanted()
         if want_c or want_tv:
             self._refuse_normal_reg(want_c, pose_opt, True)
-        attrs["_step"] = StepContext(pose_opt, grid_opt, want_nloss, want_c or want_tv)
+        lam_dd = self._depth_distortion_lambda()     # (config.depth_distortion_lambda: 0 = off; refused before any launch)
+        attrs["_step"] = StepContext(pose_opt, grid_opt, want_nloss, want_c or want_tv, lam_dd > 0.0)
         grid_idx = None
         if grid_opt is not None:
             grid_idx = cam_idx
@@ -1507,7 +1577,7 @@ class QEDSplatterModel(nn.Module):
         if grid_opt is not None:
             return self._fused_loss_with_grid(grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags,
                                               sync, handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask,
-                                              lo, ls, mcmc_vals, normal, dterms, rterms, roffsets)
+                                              lo, ls, mcmc_vals, normal, dterms, rterms, roffsets, lam_dd)
         # ``optimizer`` (a FlatAdam stepped with device_state=True, fused_sh=True right after this step's backward): the
         # loss pass's fold launch advances its device step state, so that the optimiser needs no launch of its own for it
         tick = None
@@ -1519,7 +1589,7 @@ class QEDSplatterModel(nn.Module):
                 viewmats=viewmat, Ks=K, width=W, height=H, render_mode="RGB+D", sh_degree=deg, _flags=flags,
                 _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd,
                 _pose_grad=pose_opt.pose_grad if (pose_opt is not None and torch.is_grad_enabled()) else None,
-                _keep_records=normal is not None)
+                _keep_records=normal is not None or lam_dd > 0.0)
             attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
             # (the compositing node keeps the forward pass's per-tile costs: the loss launch sorts them for its backward)
             tile_cost = getattr(render.grad_fn, "tile_cost", None) if torch.is_grad_enabled() else None
@@ -1551,6 +1621,8 @@ class QEDSplatterModel(nn.Module):
             out["depth_loss"] = depth_part
         if dterms is not None and dterms.tv_lambda > 0.0:
             out["depth_tv_loss"] = dparts[0][1]
+        if lam_dd > 0.0:
+            self._add_fused_depth_distortion(out, info, render, mask, lam_dd, normal is None)
         if normal is not None:
             self._add_fused_normal_loss(out, normal, info, render, alpha, mask)
         if pose_reg is not None:
@@ -1559,6 +1631,19 @@ class QEDSplatterModel(nn.Module):
         if rparts is not None:                   # (after every other key, as in get_loss_dict)
             out["relative_depth_loss"] = rparts[0]
         return out
+
+    def _add_fused_depth_distortion(self, out: Dict[str, Tensor], info, render: Tensor, mask, lam: float,
+                                    drop_records: bool) -> None:
+        """config.depth_distortion_lambda on the fused route: the term behind this step's colour pass, added to ``loss`` and
+        returned (detached) as ``depth_distortion_loss``.  Its rows reach the colour pass's compositing backward with the
+        upstream factor as a device scalar (normals.NormalRows), so the projection backward runs once, on the sum."""
+        from .depth_distortion import depth_distortion_loss
+        term = depth_distortion_loss(render, info, mask, lam)
+        if drop_records:                         # (else the normal pass that follows reads them, and drops them)
+            info.pop("_splats", None)
+            info.pop("_isect_offsets_full", None)
+        out["loss"] = out["loss"] + term
+        out["depth_distortion_loss"] = term.detach()
 
     def _add_fused_normal_loss(self, out: Dict[str, Tensor], normal, info, render: Tensor, alpha: Tensor, mask) -> None:
         """config.use_normal_loss on the fused route: the accumulated normal behind this step's colour pass and the loss on
@@ -1613,7 +1698,7 @@ class QEDSplatterModel(nn.Module):
 
     def _fused_loss_with_grid(self, grid_opt, grid_idx, viewmat, K, cam_c2w, W, H, deg, colors, sh_rest, flags, sync,
                               handover, post_bwd, pose_opt, pose_reg, bg, gt_rgb, gt_depth, mask, lo, ls, mcmc_vals,
-                              normal=None, dterms=None, rterms=None, roffsets=(0, 0)):
+                              normal=None, dterms=None, rterms=None, roffsets=(0, 0), lam_dd=0.0):
         """fused_loss behind ``grid_optimizer``: the loss is taken on the CORRECTED colour, so the gridless route's one
         launch from ``render`` to its gradient does not apply.  The launches are those of get_outputs -> get_loss_dict:
         the compositing forward with its post-processing epilogue (clamped colour, fixed-up depth), the slice, the SSIM
@@ -1628,7 +1713,8 @@ class QEDSplatterModel(nn.Module):
             means=self.means, quats=self.quats, scales=self.scales, opacities=self.opacities, colors=colors,
             viewmats=viewmat, Ks=K, width=W, height=H, render_mode="RGB+D", sh_degree=deg, _flags=flags,
             _sh_rest=sh_rest, _sync=sync, _handover=handover, _c2w=cam_c2w, _post_bwd=post_bwd, _post_background=bg,
-            _pose_grad=pose_opt.pose_grad if (pose_opt is not None and grad) else None, _keep_records=normal is not None)
+            _pose_grad=pose_opt.pose_grad if (pose_opt is not None and grad) else None,
+            _keep_records=normal is not None or lam_dd > 0.0)
         attrs["info"], attrs["xys"], attrs["radii"] = info, info["means2d"], info["radii"][0]
         rgb, tv = grid_opt.begin_fused(info.pop("post_rgb"), grid_idx, H, W)
         depth = info.pop("post_depth")
@@ -1655,6 +1741,8 @@ class QEDSplatterModel(nn.Module):
         out["depth_loss"] = depth_loss.detach()
         if depth_tv is not None:
             out["depth_tv_loss"] = depth_tv.detach()
+        if lam_dd > 0.0:                         # (the term does not touch colour either)
+            self._add_fused_depth_distortion(out, info, render, mask, lam_dd, normal is None)
         if normal is not None:                   # (the term does not touch colour: it is taken on the accumulated normal)
             self._add_fused_normal_loss(out, normal, info, render, alpha, mask)
         if pose_reg is not None:

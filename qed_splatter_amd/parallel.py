@@ -107,6 +107,10 @@ def _refuse_camera_optimizer(model, who: str) -> None:
         raise NotImplementedError(f"{who}: the last step carried the normal consistency or smoothness term "
                                   "(config.use_normal_consistency / use_normal_tv); the exchanges know the colour pass's "
                                   "gradient records only, not the normal pass's")
+    if ctx is not None and getattr(ctx, "depth_distortion", False):
+        raise NotImplementedError(f"{who}: the last step carried the depth distortion term "
+                                  "(config.depth_distortion_lambda); the exchanges know the colour pass's gradient records "
+                                  "only, not the rows that term merges into them")
 
 
 def _checked_grad(model, who: str, compact: bool):

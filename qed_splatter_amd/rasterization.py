@@ -426,7 +426,9 @@ class _Composite(torch.autograd.Function):
             flags |= L.CL_ORDER_READY
         elif tile_cost is not None:
             slot = handover.frame_order if handover is not None else None
-            if slot is not None and slot.fits(n_tiles) and (flags & 3) == 0:
+            # (a pass that only merges pending rows launches no ordering: the camera's buffer must not be marked as holding
+            # an order, or the next frame's forward kernel would read its tiles from whatever the buffer holds)
+            if slot is not None and slot.fits(n_tiles) and (flags & 3) == 0 and not only_normals:
                 order_ws = slot.buffer          # the camera's persistent buffer: the next frame's forward pass reads it
                 slot.valid = True
             else:

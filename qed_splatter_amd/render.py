@@ -49,9 +49,13 @@ from .model import GROUP_ORDER, PinholeCameras, QEDSplatterModel, QEDSplatterMod
 
 PLANES = ("rgb", "depth16", "depthmap", "alpha")
 # planes that are not part of the default: "normal" (the rendered normal map as 8-bit RGB, normals.py) turns
-# config.output_normals on for the run
+# config.output_normals on for the run, "depth_std" (the depth standard deviation along the ray through the depth colour map,
+# depth_distortion.py) config.output_depth_spread
 EXTRA_PLANES = ("normal",)
-PLANE_DIRS = {"rgb": "rgb", "depth16": "depth", "depthmap": "depth_vis", "alpha": "accumulation", "normal": "normal"}
+SPREAD_PLANES = ("depth_std",)
+ALL_PLANES = PLANES + EXTRA_PLANES + SPREAD_PLANES
+PLANE_DIRS = {"rgb": "rgb", "depth16": "depth", "depthmap": "depth_vis", "alpha": "accumulation", "normal": "normal",
+              "depth_std": "depth_std"}
 MAX_WORKERS = 16
 
 _TURBO_HEX = (
@@ -124,10 +128,14 @@ def present_frame(outputs, *, depth_unit: float, near: Optional[float] = None, f
                  get_outputs made with config.output_normals -- round(255 (.5 + .5 (n_x, -n_y, -n_z))) of the camera-frame
                  normal, a facing surface blue-violet, black where there is none
 
+      "depth_std" uint8 [H,W,3] (not in the default): ``outputs["depth_std"]`` (config.output_depth_spread) through the same
+                 ``lut`` and kernel as "depthmap", over the frame's own range of its positive values, over white by the
+                 accumulation; a pixel with one contributor (0) or none is white
+
     An ``outputs["depth"]`` of None leaves both depth planes out of the result.  Launched on the current stream."""
-    unknown = [p for p in planes if p not in PLANES + EXTRA_PLANES]
+    unknown = [p for p in planes if p not in ALL_PLANES]
     if unknown:
-        raise ValueError(f"planes {unknown}: choose from {PLANES + EXTRA_PLANES}")
+        raise ValueError(f"planes {unknown}: choose from {ALL_PLANES}")
     if (near is None) != (far is None):
         raise ValueError("near and far: give both or neither")
     rgb, depth, alpha = outputs["rgb"], outputs.get("depth"), outputs["accumulation"]
@@ -144,6 +152,19 @@ def present_frame(outputs, *, depth_unit: float, near: Optional[float] = None, f
         if vis is None:
             raise ValueError("planes: 'normal' needs outputs of a model with config.output_normals (outputs['normal_vis'])")
         out["normal"] = vis
+    if "depth_std" in planes:
+        std = outputs.get("depth_std")
+        if std is None:
+            raise ValueError("planes: 'depth_std' needs outputs of a model with config.output_depth_spread "
+                             "(outputs['depth_std'])")
+        std = _plane(std, "depth_std", h, w, 1)
+        out["depth_std"] = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        lib, st = L.load(), L.current_stream()
+        std_rng = torch.empty(2, dtype=torch.float32, device=dev)
+        L.check(lib.qed_present_range(h, w, L.ptr(std), L.ptr(alpha), L.ptr(std_rng), st), "qed_present_range")
+        L.check(lib.qed_present_frame(h, w, None, L.ptr(std), L.ptr(alpha), 1.0, L.ptr(std_rng), 0.0, 0.0,
+                                      L.ptr(_device_lut(lut, dev)), None, None, L.ptr(out["depth_std"]), None, st),
+                "qed_present_frame")
     if not want:
         return out
     shapes = {"rgb": ((h, w, 3), torch.uint8), "depth16": ((h, w), torch.uint16), "depthmap": ((h, w, 3), torch.uint8),
@@ -199,9 +220,9 @@ class FrameWriter:
 
     def __init__(self, out_dir, planes: Sequence[str] = PLANES, n_slots: int = 3, n_workers: int = 8,
                  png_compress_level: int = 1):
-        unknown = [p for p in planes if p not in PLANES + EXTRA_PLANES]
+        unknown = [p for p in planes if p not in ALL_PLANES]
         if unknown:
-            raise ValueError(f"planes {unknown}: choose from {PLANES + EXTRA_PLANES}")
+            raise ValueError(f"planes {unknown}: choose from {ALL_PLANES}")
         if n_slots < 1 or n_workers < 1:
             raise ValueError("n_slots and n_workers must be at least 1")
         self.out_dir = Path(out_dir)
@@ -485,8 +506,11 @@ def render_frames(model: QEDSplatterModel, cameras: Sequence[PinholeCameras], wr
     was_training = model.training
     model.eval()
     had_normals = bool(getattr(model.config, "output_normals", False))
+    had_spread = bool(getattr(model.config, "output_depth_spread", False))
     if "normal" in writer.planes:
         model.config.output_normals = True      # (asking for the plane turns the normal pass on for this run)
+    if "depth_std" in writer.planes:
+        model.config.output_depth_spread = True
     n = 0
     try:
         with torch.no_grad():
@@ -508,6 +532,7 @@ def render_frames(model: QEDSplatterModel, cameras: Sequence[PinholeCameras], wr
     finally:
         model.train(was_training)
         model.config.output_normals = had_normals
+        model.config.output_depth_spread = had_spread
     return n
 
 
@@ -560,7 +585,7 @@ def main(argv=None) -> dict:
     ap.add_argument("--steps-per-pair", type=int, default=10)
     ap.add_argument("--order-poses", action="store_true", help="interpolate: visit the cameras nearest-first")
     ap.add_argument("--camera-path-file", metavar="JSON", default=None)
-    ap.add_argument("--planes", nargs="+", choices=PLANES + EXTRA_PLANES, default=list(PLANES),
+    ap.add_argument("--planes", nargs="+", choices=ALL_PLANES, default=list(PLANES),
                     help="'normal' (not in the default) adds normal/: the rendered normal map as 8-bit RGB")
     ap.add_argument("--colormap", choices=("turbo", "gray"), default="turbo")
     ap.add_argument("--near", type=float, default=None)

@@ -166,16 +166,30 @@ def _camera_intrinsics(outputs: Dict, camera) -> Tuple[float, float, float, floa
 def frame_surface_samples(outputs: Dict, camera, *, stride: int = 1, min_alpha: float = 0.5, depth_min: float = 0.0,
                           depth_max: float = math.inf, normals: str = "rendered",
                           max_normal_angle_deg: Optional[float] = None, min_view_cos: float = 0.0,
-                          mask: Optional[Tensor] = None) -> SurfaceCloud:
+                          mask: Optional[Tensor] = None, max_depth_std: Optional[float] = None) -> SurfaceCloud:
     """The oriented samples of ONE view, a single launch sequence on the planes as they are: ``outputs`` is what
     ``get_outputs(camera)`` returned in evaluation mode with ``config.output_normals`` (rgb, depth, accumulation, normal,
-    depth_normal, normal_valid).  Every sample weighs 1."""
+    depth_normal, normal_valid).  Every sample weighs 1.  ``max_depth_std`` (model units; None: no filter, the call is
+    what it was): pixels whose ``outputs["depth_std"]`` (config.output_depth_spread: the standard deviation of the depth along
+    the ray, depth_distortion.py) exceeds it -- or is not a number -- are dropped AHEAD of qed_surface_samples, through its
+    mask plane, so the compact list is written without them."""
     missing = [k for k in ("rgb", "depth", "accumulation", "normal", "depth_normal", "normal_valid") if outputs.get(k) is None]
     if missing:
         raise ValueError(f"frame_surface_samples: outputs lack {missing}: render in evaluation mode with config.output_normals")
     rgb = outputs["rgb"]
     if not rgb.is_cuda:
         raise L.QedSplatError("frame_surface_samples needs GPU tensors: there is no CPU path in the product")
+    if max_depth_std is not None:
+        std = outputs.get("depth_std")
+        if std is None:
+            raise ValueError("frame_surface_samples(max_depth_std=...): outputs lack 'depth_std': render with "
+                             "config.output_depth_spread")
+        if not float(max_depth_std) >= 0.0:
+            raise ValueError(f"max_depth_std must be a number >= 0, got {max_depth_std}")
+        keep = std.reshape(rgb.shape[0], rgb.shape[1]) <= float(max_depth_std)
+        if mask is not None:
+            keep = keep & (mask.to(rgb.device).reshape(keep.shape) != 0)
+        mask = keep.to(torch.uint8)
     points, nrm, colors = surface_samples(
         rgb, outputs["depth"], outputs["accumulation"], outputs["normal"], outputs["depth_normal"], outputs["normal_valid"],
         camera_viewmat(camera, rgb.device), _camera_intrinsics(outputs, camera), mask=mask, stride=stride,
@@ -271,8 +285,9 @@ def export_pointcloud(model, cameras, path=None, *, voxel_size: float, stride: i
                       depth_min: float = 0.0, depth_max: float = math.inf, normals: str = "rendered",
                       max_normal_angle_deg: Optional[float] = None, min_view_cos: float = 0.0, min_samples: float = 1,
                       max_rows_in_flight: int = 4_000_000, frame: str = "model", dataparser_transform=None,
-                      dataparser_scale: float = 1.0) -> SurfaceCloud:
-    """The whole export: every camera through ``model.get_outputs`` (evaluation mode, no gradients, ``output_normals``
+                      dataparser_scale: float = 1.0, max_depth_std: Optional[float] = None) -> SurfaceCloud:
+    """``max_depth_std`` (None: off): ``config.output_depth_spread`` is forced on for the run as well and every view drops the
+    pixels whose depth standard deviation along the ray exceeds it (``frame_surface_samples``).  The whole export: every camera through ``model.get_outputs`` (evaluation mode, no gradients, ``output_normals``
     forced on for the run and restored afterwards; ``model.crop_box`` applies) and ``frame_surface_samples``; the views
     merged on the voxel grid (``merge_clouds``); voxels of fewer than ``min_samples`` samples dropped; normals
     normalised; ``frame="dataset"``: moved back through ``dataparser_transform`` / ``dataparser_scale`` (refused without
@@ -298,8 +313,11 @@ def export_pointcloud(model, cameras, path=None, *, voxel_size: float, stride: i
         min_alpha = float(model.config.normals_min_alpha)
     was_training = model.training
     had_normals = bool(getattr(model.config, "output_normals", False))
+    had_spread = bool(getattr(model.config, "output_depth_spread", False))
     model.eval()
     model.config.output_normals = True
+    if max_depth_std is not None:
+        model.config.output_depth_spread = True
 
     def frame_clouds():
         for cam in cameras:
@@ -309,7 +327,7 @@ def export_pointcloud(model, cameras, path=None, *, voxel_size: float, stride: i
                 continue
             cloud = frame_surface_samples(outputs, cam, stride=stride, min_alpha=min_alpha, depth_min=depth_min,
                                           depth_max=depth_max, normals=normals, max_normal_angle_deg=max_normal_angle_deg,
-                                          min_view_cos=min_view_cos)
+                                          min_view_cos=min_view_cos, max_depth_std=max_depth_std)
             if len(cloud):
                 yield cloud
 
@@ -321,6 +339,7 @@ def export_pointcloud(model, cameras, path=None, *, voxel_size: float, stride: i
     finally:
         model.train(was_training)
         model.config.output_normals = had_normals
+        model.config.output_depth_spread = had_spread
     if path is not None:
         cloud.write_ply(path)
     return cloud
@@ -345,6 +364,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="drop pixels whose rendered normal and depth normal differ by more than this")
     ap.add_argument("--min-view-cos", type=float, default=0.0, metavar="C",
                     help="drop pixels seen at a grazing angle: -dot(normal, view direction) below this")
+    ap.add_argument("--max-depth-std", type=float, default=None, metavar="V",
+                    help="drop pixels whose blending weights are spread along the ray by more than this standard deviation of "
+                         "the depth, in the model's units (depth_distortion.py; default: no filter)")
     ap.add_argument("--min-samples", type=float, default=1, metavar="K", help="drop voxels that hold fewer samples")
     ap.add_argument("--frame", choices=("model", "dataset"), default="model",
                     help="'dataset': undo the dataparser's orientation, centring and scale")
@@ -388,7 +410,7 @@ def main(argv=None) -> dict:
                               depth_max=a.depth_max, normals=a.normals, max_normal_angle_deg=a.max_normal_angle,
                               min_view_cos=a.min_view_cos, min_samples=a.min_samples, frame=a.frame,
                               dataparser_transform=ckpt.get("dataparser_transform"),
-                              dataparser_scale=float(ckpt.get("dataparser_scale", 1.0)))
+                              dataparser_scale=float(ckpt.get("dataparser_scale", 1.0)), max_depth_std=a.max_depth_std)
     result = {"output": str(a.output), "points": len(cloud), "views": len(cameras), "frame": a.frame,
               "voxel_size": a.voxel_size}
     if a.gt is not None:

@@ -481,6 +481,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="a box contributes from this share of valid pixels on, in (0, 1] (default 0.25)")
     ap.add_argument("--no-relative-depth-jitter", action="store_true", default=argparse.SUPPRESS,
                     help="keep PatchPearson's boxes where they are instead of moving them with the step")
+    ap.add_argument("--depth-distortion-lambda", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="weight of the depth distortion term: the spread of each pixel's blending weights in depth "
+                         "(config.depth_distortion_lambda, depth_distortion.py; default 0 = off), in the model's units")
+    ap.add_argument("--depth-distortion-from-step", type=int, default=argparse.SUPPRESS, metavar="K",
+                    help="the first step that carries the depth distortion term (default 0)")
+    ap.add_argument("--output-depth-spread", action="store_true", default=argparse.SUPPRESS,
+                    help="after training: render the depth standard deviation along each ray in the final \"eval_images\" "
+                         "evaluation, which then reports depth_std_mean; training is unaffected")
     ap.add_argument("--prune-at", type=int, nargs="+", default=argparse.SUPPRESS, metavar="STEP",
                     help="after these steps' refinement: score the training cameras and prune by blending contribution "
                          "(prune.py)")
@@ -520,6 +528,13 @@ def depth_config_of(a) -> Dict:
             "depth_huber_delta": float(getattr(a, "depth_huber_delta", cfg.depth_huber_delta)),
             "depth_tv_lambda": float(getattr(a, "depth_tv_lambda", cfg.depth_tv_lambda)),
             "depth_tv_edge_aware": not bool(getattr(a, "no_depth_tv_edge_aware", False))}
+
+
+def depth_distortion_config_of(a) -> Dict:
+    """The model-config fields of the --depth-distortion-* options (the config's defaults where an option is absent)."""
+    cfg = QEDSplatterModelConfig
+    return {"depth_distortion_lambda": float(getattr(a, "depth_distortion_lambda", cfg.depth_distortion_lambda)),
+            "depth_distortion_from_step": int(getattr(a, "depth_distortion_from_step", cfg.depth_distortion_from_step))}
 
 
 def relative_depth_config_of(a) -> Dict:
@@ -603,7 +618,7 @@ def main(argv=None) -> Dict:
                                     use_normal_tv=bool(getattr(a, "normal_tv", False)),
                                     normal_tv_lambda=float(getattr(a, "normal_tv_lambda",
                                                                    QEDSplatterModelConfig.normal_tv_lambda)),
-                                    **depth_config_of(a), **relative_depth_config_of(a))
+                                    **depth_config_of(a), **relative_depth_config_of(a), **depth_distortion_config_of(a))
     from .losses import depth_terms, relative_depth_terms
     dterms = depth_terms(config)                 # (a refused combination ends the run before the model is built)
     rterms = relative_depth_terms(config)
@@ -669,18 +684,25 @@ def main(argv=None) -> Dict:
         # (depth_pearson, in the configured space: the evaluation split's mean; the training cameras' where that split is empty)
         result["relative_depth_loss"] = float(losses["relative_depth_loss"]) if losses is not None else None
         result["depth_pearson"] = metrics["depth_pearson"] if "depth_pearson" in metrics else trainer.depth_pearson()
+    if config.depth_distortion_lambda > 0.0:     # (None: no step carried the term, e.g. all before --depth-distortion-from-step)
+        key = "depth_distortion_loss"
+        result[key] = float(losses[key]) if (losses is not None and key in losses) else None
     if output_normals:
         trainer.model.config.output_normals = True      # (from here on: the final evaluation and --render-eval only)
-    if color_corrected or output_normals:
+    output_spread = bool(getattr(a, "output_depth_spread", False))
+    if output_spread:
+        trainer.model.config.output_depth_spread = True
+    if color_corrected or output_normals or output_spread:
         result["eval_images"] = trainer.evaluate_images()
     if a.save_poses:
         result["save_poses"] = trainer.save_poses(a.save_poses, a.data)
         print(f"wrote {result['save_poses']} training poses to {a.save_poses}")
     if a.render_eval:
-        from .render import EXTRA_PLANES, PLANES, dataset_path, render_to_directory
+        from .render import EXTRA_PLANES, PLANES, SPREAD_PLANES, dataset_path, render_to_directory
         unit = float(dm.outputs.dataparser_scale) * float(dm.outputs.depth_unit_scale_factor)
         result["render_eval"] = render_to_directory(trainer.model, dataset_path(dm, "eval"), a.render_eval, depth_unit=unit,
-                                                    planes=PLANES + (EXTRA_PLANES if output_normals else ()))
+                                                    planes=PLANES + (EXTRA_PLANES if output_normals else ())
+                                                    + (SPREAD_PLANES if output_spread else ()))
         print(f"rendered {result['render_eval']['frames']} evaluation views to {a.render_eval}")
     print(json.dumps(result))
     return result
