@@ -72,7 +72,8 @@ extern "C" {
  * New entry points change nothing a caller of version 4 relies on and keep the number (the latest: qed_gaussian_normals,
  * qed_normal_maps, qed_depth_normals, qed_angular_error; qed_normal_loss, qed_gaussian_normals_bwd, qed_normal_rows_merge;
  * qed_normal_consistency, qed_normal_rows_merge_depth; qed_depth_loss; qed_relative_depth_loss; qed_depth_spread_fwd,
- * qed_depth_spread_bwd, qed_depth_distortion_loss). */
+ * qed_depth_spread_bwd, qed_depth_distortion_loss; qed_features_fwd, qed_features_bwd, qed_label_loss, qed_label_confusion,
+ * qed_label_present). */
 #define QED_ABI_VERSION 4
 int qed_version(void);   /* == QED_ABI_VERSION of the header the library was built from */
 const char* qed_last_error(void);
@@ -1398,6 +1399,67 @@ int qed_depth_spread_bwd(int32_t C, int32_t N, const float* splats, const int32_
                          float* rows, const int32_t* tile_cost, int32_t* order_ws, int32_t launch_flags, void* stream);
 int qed_depth_distortion_loss(int64_t n_pix, const float* spread, const float* mask, float lambda, double* workspace,
                               float* v, float* loss, void* stream);
+
+/* ---- label fields on frozen Gaussians: K-channel compositing and the label kernels (csrc/semantic.hip) -----------------------
+ * A table features[N,K] (class logits, one row per Gaussian) composited with the render's own blending weights, LangSplat's /
+ * Feature-3DGS's route RESTATED FROM MEMORY of those papers, not checked against their code and not in the reference.  The
+ * geometry is frozen: nothing here produces a gradient to the records.
+ *
+ * qed_features_fwd: out[c,p,k] = sum_i w_i(p) features[n_i,k] over the Gaussians the colour pass applied at pixel p -- the
+ * same records, ids and offsets, the same accept / skip / terminate decisions as qed_composite_fwd (and qed_contribution: a
+ * Gaussian contributes where it passes the alpha test, the pixel has not terminated and T (1 - alpha) > 1e-4; the one that
+ * terminates a pixel is not applied), w_i = alpha_i T_i.  Records c * N + n of every camera c read row n of the one table.
+ * 1 <= K <= QED_FEATURES_MAX.  Every entry of features (and of v_out) must be FINITE: a lane that did not accept a Gaussian adds
+ * weight 0 times its row, so a non-finite entry reaches every pixel of an 8x8 quadrant in which some pixel accepted that
+ * Gaussian, and "the same bits with the cull off" holds for finite tables only.  out is [C,H,W,K]; every pixel inside the image is written (zeros in empty tiles and where
+ * nothing contributed) and nothing outside it; N == 0 or flatten_ids == NULL (an empty list) zero out.  The sum of one (pixel,
+ * channel) runs in list order in float32 whatever the kernel's channel chunk, and no value depends on the launch order of the
+ * tiles.  launch_flags: QED_CL_NO_CULL is honoured (bit-identical out); the launch-shape bits are ignored (always one wave per
+ * tile and channel chunk).
+ *
+ * qed_features_bwd: v_features[n,k] += sum over cameras and pixels of w_i(p) v_out[c,p,k] for n = n_i: a FORWARD walk again
+ * (no last_ids, no t_final, no suffix sums).  The caller zeroes v_features [N,K]; calls accumulate.  One float atomic add per
+ * (tile, contributing Gaussian, channel) -- the tile's sum is formed in a fixed lane order first -- and none for a Gaussian that
+ * contributed to no pixel of the tile: its row keeps its bits.  Same values up to the order of those adds.  N == 0 or an empty
+ * list: nothing is done.
+ *
+ * Both refuse on the host: bad extents, K outside 1..QED_FEATURES_MAX, a tile grid that does not match the image, NULL
+ * buffers, features / out / v_out not 16-byte aligned.
+ *
+ * qed_label_loss: loss[1] = sum_p cw[y_p] nll_p / sum_p cw[y_p] over the LABELLED pixels p -- labels[p] = y_p is not
+ * ignore_label and < K (a label >= K counts as ignored) -- with nll_p = logsumexp(logits[p,:]) - logits[p,y_p] taken about
+ * the row maximum and cw = class_weight[K] (NULL: all 1): torch.nn.functional.cross_entropy(logits, labels, weight=cw,
+ * ignore_index=ignore_label, reduction="mean").  With v_logits (may be NULL): v_logits[p,k] = cw[y_p] (softmax_k - [k == y_p])
+ * / sum cw at the labelled pixels, 0 at the others.  Loss and gradient are 0 when no pixel is labelled (or the weights of the
+ * labelled pixels sum to 0).  The two sums are doubles, folded in a fixed order: no float atomics, no host read-back, the same
+ * bits on every run.  workspace: QED_LABEL_LOSS_WS_DOUBLES doubles; its last two hold sum cw nll and sum cw afterwards.
+ *
+ * qed_label_confusion ADDS, for every labelled pixel, 1 to confusion[y_p][pred_p] of a [K][K + 1] table of unsigned 64-bit
+ * counts (row = label, column = prediction; ONE layout, with or without acc): pred_p = the first maximum of logits[p,:] (ties
+ * go to the lower index, a NaN never wins), or K -- "no prediction", the last column -- when acc (float [n_pix], may be NULL) is
+ * given and acc[p] >= min_alpha does not hold.  Integer atomics only: the same bits for any order of views.  The caller
+ * zeroes the table once.
+ *
+ * qed_label_present: the planes an image writer stores.  out_label[p] (uint8, may be NULL) = pred_p, or QED_LABEL_NONE where
+ * acc[p] >= min_alpha does not hold; out_rgb[p] (uint8 [n_pix,3], may be NULL) = palette[pred_p] of a uint8 [K + 1][3] palette
+ * whose last row colours the pixels without a prediction.
+ * The three refuse a class count outside 1..QED_FEATURES_MAX, NULL buffers and a NaN min_alpha.  No function of this section
+ * allocates, synchronises or reads anything back. */
+#define QED_FEATURES_MAX 32
+#define QED_LABEL_NONE 255
+#define QED_LABEL_LOSS_WS_DOUBLES (2 * 256 + 2)
+int qed_features_fwd(int32_t C, int32_t N, int32_t K, const float* splats, const int32_t* flatten_ids, const int32_t* offsets,
+                     int32_t width, int32_t height, int32_t tile_w, int32_t tile_h, const float* features, float* out,
+                     int32_t launch_flags, void* stream);
+int qed_features_bwd(int32_t C, int32_t N, int32_t K, const float* splats, const int32_t* flatten_ids, const int32_t* offsets,
+                     int32_t width, int32_t height, int32_t tile_w, int32_t tile_h, const float* v_out, float* v_features,
+                     int32_t launch_flags, void* stream);
+int qed_label_loss(int64_t n_pix, int32_t K, const float* logits, const uint8_t* labels, int32_t ignore_label,
+                   const float* class_weight, double* workspace, float* v_logits, float* loss, void* stream);
+int qed_label_confusion(int64_t n_pix, int32_t K, const float* logits, const uint8_t* labels, int32_t ignore_label,
+                        const float* acc, float min_alpha, uint64_t* confusion, void* stream);
+int qed_label_present(int64_t n_pix, int32_t K, const float* logits, const float* acc, float min_alpha, const uint8_t* palette,
+                      uint8_t* out_label, uint8_t* out_rgb, void* stream);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,11 @@ SIGNATURES = {
     "qed_depth_spread_fwd": (C.c_int, [_I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
     "qed_depth_spread_bwd": (C.c_int, [_I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "qed_depth_distortion_loss": (C.c_int, [_L, _P, _P, _F, _P, _P, _P, _P]),
+    "qed_features_fwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "qed_features_bwd": (C.c_int, [_I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "qed_label_loss": (C.c_int, [_L, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "qed_label_confusion": (C.c_int, [_L, _I, _P, _P, _I, _P, _F, _P, _P]),
+    "qed_label_present": (C.c_int, [_L, _I, _P, _P, _F, _P, _P, _P, _P]),
 }
 
 class Post(C.Structure):
@@ -178,6 +183,9 @@ NORMAL_CONSISTENCY_WS_DOUBLES = 6 * 1024   # QED_NORMAL_CONSISTENCY_WS_DOUBLES
 NC_CONSISTENCY, NC_TV, NC_REDUCE, NC_GRAD = 1, 2, 4, 8   # QED_NC_*
 DEPTH_LOSS_WS_DOUBLES = 6 * 256 + 136      # QED_DEPTH_LOSS_WS_DOUBLES
 DEPTH_DISTORTION_WS_DOUBLES = 2 * 256 + 2  # QED_DEPTH_DISTORTION_WS_DOUBLES
+FEATURES_MAX = 32                          # QED_FEATURES_MAX
+LABEL_NONE = 255                           # QED_LABEL_NONE
+LABEL_LOSS_WS_DOUBLES = 2 * 256 + 2        # QED_LABEL_LOSS_WS_DOUBLES
 DEPTH_LOSS_TYPES = {"L1": 0, "MSE": 1, "LogL1": 2, "HuberL1": 3, "EdgeAwareLogL1": 4}   # QED_DL_L1 .. QED_DL_EDGE_LOGL1
 DL_DATA, DL_TV, DL_TV_EDGE, DL_FIXUP, DL_REDUCE, DL_GRAD = 1, 2, 4, 8, 16, 32   # QED_DL_*
 RELATIVE_DEPTH_TYPES = {"Pearson": 0, "PatchPearson": 1, "ScaleShiftL1": 2}   # QED_RD_PEARSON .. QED_RD_SCALE_SHIFT_L1

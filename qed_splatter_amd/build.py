@@ -15,7 +15,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB_DIR = PKG / "lib"
 LIB_PATH = LIB_DIR / "libqed_splat.so"
-SOURCES = ["project.hip", "isect.hip", "radix_sort.hip", "composite.hip", "loss.hip", "adam.hip", "ssim.hip", "metrics.hip", "densify.hip", "backproject.hip", "bilagrid.hip", "mcmc.hip", "colorize.hip", "voxel.hip", "nn.hip", "seed.hip", "lpips.hip", "ingest.hip", "undistort.hip", "export.hip", "present.hip", "pose.hip", "color_correct.hip", "normals.hip", "normal_loss.hip", "normal_consistency.hip", "depth_loss.hip", "relative_depth.hip", "surface.hip", "importance.hip", "depth_grow.hip", "depth_spread.hip"]
+SOURCES = ["project.hip", "isect.hip", "radix_sort.hip", "composite.hip", "loss.hip", "adam.hip", "ssim.hip", "metrics.hip", "densify.hip", "backproject.hip", "bilagrid.hip", "mcmc.hip", "colorize.hip", "voxel.hip", "nn.hip", "seed.hip", "lpips.hip", "ingest.hip", "undistort.hip", "export.hip", "present.hip", "pose.hip", "color_correct.hip", "normals.hip", "normal_loss.hip", "normal_consistency.hip", "depth_loss.hip", "relative_depth.hip", "surface.hip", "importance.hip", "depth_grow.hip", "depth_spread.hip", "semantic.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",

@@ -1,6 +1,7 @@
 """The reference's data manager -- ``FullImageDatamanager[DepthDataset]`` with ``cache_images_type="uint8"``
 (config.py:34-38) -- over ``dataparser.parse_dataset``: every frame is loaded once and cached as the files store it
-(uint8 colour, RGBA kept; 16-bit depth as uint16 with ONE scalar; bool masks), and every training step is handed a
+(uint8 colour, RGBA kept; 16-bit depth as uint16 with ONE scalar; bool masks; uint8 class maps under ``"label"`` [H,W] for
+the frames of a dataset that has them, semantic.py), and every training step is handed a
 different camera and that camera's cached frame.  The float ground truth the loss kernels read is made per step by
 ``QEDSplatterModel._ground_truth`` (csrc/ingest.hip, one launch): it depends on the step's downscale factor and on
 the step's background colour, so it cannot be made here.
@@ -160,6 +161,17 @@ def _load_mask(path: Path) -> np.ndarray:
         return np.array(im.convert("L")) != 0
 
 
+def _load_label(path: Path) -> np.ndarray:
+    """uint8 [H,W]: the class of every pixel as the file stores it (255 = unlabelled).  Only 8-bit greyscale images (PIL mode
+    "L"): a palette image's indices name colours, not classes, and are refused like a colour image."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode != "L":
+            raise ValueError(f"{path}: a label image is an 8-bit single-channel greyscale PNG (value = class), not mode "
+                             f"{im.mode!r}")
+        return np.array(im, dtype=np.uint8)
+
+
 class FullImageDatamanager:
     """``next_train(step) -> (camera, batch)`` over the training split, ``next_eval`` / ``eval_items()`` over the
     evaluation split.
@@ -189,6 +201,10 @@ class FullImageDatamanager:
         unit = out.depth_unit_scale_factor * out.dataparser_scale
         self.frames: List[dict] = []
         n_bytes = 0
+        labels = out.label_filenames
+        if labels is not None and out.config.undistort:
+            raise NotImplementedError("label images on a dataset parsed with undistort=True: there is no nearest-neighbour "
+                                      "resampling of labels yet")
         for k in range(len(out)):
             img = _load_image(out.image_filenames[k])
             depth, depth_scale = _load_depth(out.depth_filenames[k], unit)
@@ -204,9 +220,15 @@ class FullImageDatamanager:
                     raise ValueError(f"{out.mask_filenames[k]}: mask is {mask.shape[1]}x{mask.shape[0]}, its image is "
                                      f"{img.shape[1]}x{img.shape[0]} (resizing is not offered)")
                 frame["mask"] = torch.from_numpy(np.ascontiguousarray(mask))[..., None]
+            if labels is not None and labels[k] is not None:
+                label = _load_label(labels[k])
+                if label.shape[:2] != img.shape[:2]:
+                    raise ValueError(f"{labels[k]}: label image is {label.shape[1]}x{label.shape[0]}, its image is "
+                                     f"{img.shape[1]}x{img.shape[0]} (resizing is not offered)")
+                frame["label"] = torch.from_numpy(np.ascontiguousarray(label))
             if out.distortion_params is not None and is_distorted(out.distortion_params[k], out.camera_models[k]):
                 self._undistort(frame, k)
-            for key in ("image", "depth_image", "mask"):
+            for key in ("image", "depth_image", "mask", "label"):
                 if key in frame:
                     t = frame[key].to(self.device)
                     frame[key] = t.pin_memory() if pin else t
@@ -260,7 +282,7 @@ class FullImageDatamanager:
     def _batch(self, k: int, idx: int) -> GpuBatch:
         frame = self.frames[k]
         batch = GpuBatch()
-        for key in ("image", "depth_image", "mask"):
+        for key in ("image", "depth_image", "mask", "label"):
             if key in frame:
                 batch[key] = frame[key].to(self.compute_device, non_blocking=True)
         batch["image_idx"] = idx

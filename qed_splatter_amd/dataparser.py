@@ -83,6 +83,9 @@ class DataparserOutputs:
     # dataset's own frame (train.py --save-poses) without the float32 rounding of the translations
     camera_to_worlds_f64: Optional[np.ndarray] = None
     dataparser_transform_f64: Optional[np.ndarray] = None
+    # Per frame the class map of semantic.py (``label_path``: an 8-bit single-channel PNG of the frame's size, value = class,
+    # 255 = unlabelled) or None; None for the whole dataset when no frame has one.
+    label_filenames: Optional[List[Optional[Path]]] = None
 
     def __len__(self) -> int:
         return len(self.image_filenames)
@@ -167,8 +170,8 @@ def _frame_size(contents: dict, frame: dict, image_path: Path):
 
 def parse_dataset(data_dir, config: Optional[DataparserConfig] = None, verbose: bool = True) -> DataparserOutputs:
     """Reads ``data_dir/transforms.json``.  Frames are sorted by ``file_path``; frames without ``depth_file_path`` are
-    skipped (their number is reported); ``mask_path`` is optional.  Intrinsics and sizes are the frame's, else the
-    file's.  Poses go through ``orient_and_center`` and are then scaled by ``scale_factor / max |origin coordinate|``
+    skipped (their number is reported); ``mask_path`` and ``label_path`` (a class map, semantic.py) are optional.
+    Intrinsics and sizes are the frame's, else the file's.  Poses go through ``orient_and_center`` and are then scaled by ``scale_factor / max |origin coordinate|``
     (``auto_scale_poses``) or by ``scale_factor``.  With ``config.undistort`` the intrinsics of a distorted frame are
     replaced by ``optimal_new_intrinsics`` of the frame's own (see the module docstring)."""
     cfg = config or DataparserConfig()
@@ -183,7 +186,7 @@ def parse_dataset(data_dir, config: Optional[DataparserConfig] = None, verbose: 
         print(f"dataparser: skipped {n_skipped} of {len(frames)} frames without depth_file_path")
     if not with_depth:
         raise ValueError(f"{data_dir}: no frame of transforms.json has a depth_file_path")
-    images, depths, masks, poses, intr, sizes = [], [], [], [], [], []
+    images, depths, masks, poses, intr, sizes, labels = [], [], [], [], [], [], []
     src_intr, dists, models, new_K = [], [], [], {}
     for f in with_depth:
         if not cfg.undistort:
@@ -191,6 +194,7 @@ def parse_dataset(data_dir, config: Optional[DataparserConfig] = None, verbose: 
         images.append(data_dir / f["file_path"])
         depths.append(data_dir / f["depth_file_path"])
         masks.append(data_dir / f["mask_path"] if "mask_path" in f else None)
+        labels.append(data_dir / f["label_path"] if "label_path" in f else None)
         poses.append(np.asarray(f["transform_matrix"], dtype=np.float64))
         intr.append(frame_intrinsics(contents, f))
         sizes.append(_frame_size(contents, f, images[-1]))
@@ -224,4 +228,5 @@ def parse_dataset(data_dir, config: Optional[DataparserConfig] = None, verbose: 
         src_intrinsics=np.asarray(src_intr, dtype=np.float64) if cfg.undistort else None,
         distortion_params=np.asarray(dists, dtype=np.float64) if cfg.undistort else None,
         camera_models=models if cfg.undistort else None,
-        camera_to_worlds_f64=np.array(c2w, dtype=np.float64), dataparser_transform_f64=np.array(transform, dtype=np.float64))
+        camera_to_worlds_f64=np.array(c2w, dtype=np.float64), dataparser_transform_f64=np.array(transform, dtype=np.float64),
+        label_filenames=labels if any(p is not None for p in labels) else None)

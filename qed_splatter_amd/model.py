@@ -1152,9 +1152,10 @@ class QEDSplatterModel(nn.Module):
         intr = (float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2]))
         out = render_normals(means, quats, scales, viewmat, info, alpha[0], render[0, ..., 3], intr,
                              min_alpha=float(self.config.normals_min_alpha), log_scales=True, colors=True)
-        info.pop("_splats", None)                # (24 MB at 500 k Gaussians: not kept alive by self.info)
-        info.pop("_isect_offsets_full", None)
-        out["normal"]._qed_intrinsics = intr     # (get_image_metrics_and_images: the sensor depth's normals)
+        if not self.__dict__.get("_score_records"):     # (a caller that walks the lists once more drops them itself)
+            info.pop("_splats", None)            # (24 MB at 500 k Gaussians: not kept alive by self.info)
+            info.pop("_isect_offsets_full", None)
+        out["normal"]._qed_intrinsics = intr    # (get_image_metrics_and_images: the sensor depth's normals)
         return {"normal": out["normal"], "depth_normal": out["depth_normal"], "normal_valid": out["valid"],
                 "normal_vis": out["rgb8"]}
 

@@ -222,10 +222,12 @@ def keep_mask(config: PruneConfig, max_weight: Tensor, sum_weight: Tensor, scale
 
 @torch.no_grad()
 def prune(model, optimizer, scores: ContributionScores, config: Optional[PruneConfig] = None, densifier=None,
-          captured_step=None) -> Dict:
+          captured_step=None, field=None) -> Dict:
     """Drop the low scorers from ``model`` and both Adam moments of ``optimizer`` (a FlatAdam; None: parameters only).
     Survivors keep their order and their bits.  Returns ``n_before``, ``n_after``, ``n_pruned``, ``threshold``.
-    ``densifier``: its running statistics (length N) are cleared.
+    ``densifier``: its running statistics (length N) are cleared.  ``field`` (a semantic.SemanticField of the model's N): the
+    result also holds ``"field"``, the field of the pruned model (``field.select`` of the keep mask: the survivors' rows
+    and moments, bit for bit).
 
     Refused: ``strategy="mcmc"`` (relocation owns dead Gaussians there and the count is a target), and a
     ``captured_step`` (graph.GraphedTrainStep): it replays launches on the buffers of the old N and ``rebind_flat`` cannot
@@ -240,10 +242,14 @@ def prune(model, optimizer, scores: ContributionScores, config: Optional[PruneCo
     n, dev = model.num_points, model.device
     if scores.n != n:
         raise ValueError(f"prune: the scores hold {scores.n} Gaussians, the model has {n}")
+    if field is not None:
+        field.check_model(model)
     score = selection_score(config, scores.max_weight(), scores.sum_weight(), model.scales)
     thr, tie_below = selection_threshold(config, score)
     info = {"n_before": n, "n_after": n, "n_pruned": 0, "threshold": thr}
     if n == 0:
+        if field is not None:
+            info["field"] = field
         return info
     old_m = optimizer.exp_avg if optimizer is not None else None
     old_v = optimizer.exp_avg_sq if optimizer is not None else None
@@ -265,10 +271,13 @@ def prune(model, optimizer, scores: ContributionScores, config: Optional[PruneCo
                                      L.ptr(model.flat_params), L.ptr(old_m), L.ptr(old_v), model.layout.c_begin_ptr,
                                      L.ptr(new_p), L.ptr(new_m), L.ptr(new_v), new.c_begin_ptr, _stream()),
                 "qed_densify_emit")
+        kept = flags != 0
     else:
         idx = torch.arange(n, device=dev)
         keep = torch.nonzero((score > thr) | ((score == thr) & (idx < tie_below))).reshape(-1)
         k = int(keep.numel())
+        kept = torch.zeros(n, dtype=torch.bool, device=dev)
+        kept[keep] = True
         new = model.layout.resized(k)
         new_p, new_m, new_v = new.empty_like_state(dev)
         for src, dst in ((model.flat_params, new_p), (old_m, new_m), (old_v, new_v)):
@@ -282,6 +291,8 @@ def prune(model, optimizer, scores: ContributionScores, config: Optional[PruneCo
     if densifier is not None:
         densifier.xys_grad_norm = densifier.vis_counts = densifier.max_2Dsize = None
     info.update(n_after=k, n_pruned=n - k)
+    if field is not None:
+        info["field"] = field.select(kept)
     return info
 
 

@@ -16,7 +16,9 @@ stream while the next frame renders, PNG encoding in a thread pool.
 Files: ``rgb/00042.png``, ``depth/00042.png`` (16-bit, in the dataset's own unit: ``depth_unit_scale_factor`` metres of
 the ORIGINAL scene per step, i.e. value = rendered depth / (dataparser_scale * depth_unit_scale_factor); 0 = no surface,
 as the datasets store "no measurement"), ``depth_vis/00042.png`` (colour map over white), ``accumulation/00042.png``;
-with ``--planes ... normal`` also ``normal/00042.png``, the rendered normal map (normals.py) in the usual colouring.
+with ``--planes ... normal`` also ``normal/00042.png``, the rendered normal map (normals.py) in the usual colouring;
+with ``--planes ... semantic --field FIELD.pt`` also ``semantic/00042.png`` (the palette colour of every pixel's class) and
+``semantic_label/00042.png`` (the class byte, 255 where the accumulation is below 0.5), semantic.py.
 The depth files are read back by datamanager._load_depth, init_pointcloud and PDMetrics like any dataset's.
 
 Camera paths are float64 host arithmetic.  ``load_camera_path`` reads the viewer's ``camera_path.json``; its layout is
@@ -53,9 +55,13 @@ PLANES = ("rgb", "depth16", "depthmap", "alpha")
 # depth_distortion.py) config.output_depth_spread
 EXTRA_PLANES = ("normal",)
 SPREAD_PLANES = ("depth_std",)
-ALL_PLANES = PLANES + EXTRA_PLANES + SPREAD_PLANES
+# "semantic" (with a field, semantic.py: --field FIELD.pt) writes two directories: semantic/ (the class colours) and
+# semantic_label/ (the class byte); SEMANTIC_FILES are the names of the two in a frame's dict
+SEMANTIC_PLANES = ("semantic",)
+SEMANTIC_FILES = ("semantic", "semantic_label")
+ALL_PLANES = PLANES + EXTRA_PLANES + SPREAD_PLANES + SEMANTIC_PLANES
 PLANE_DIRS = {"rgb": "rgb", "depth16": "depth", "depthmap": "depth_vis", "alpha": "accumulation", "normal": "normal",
-              "depth_std": "depth_std"}
+              "depth_std": "depth_std", "semantic": "semantic", "semantic_label": "semantic_label"}
 MAX_WORKERS = 16
 
 _TURBO_HEX = (
@@ -227,6 +233,8 @@ class FrameWriter:
             raise ValueError("n_slots and n_workers must be at least 1")
         self.out_dir = Path(out_dir)
         self.planes = tuple(planes)
+        if "semantic" in self.planes:           # (one plane, two files per frame)
+            self.planes += ("semantic_label",)
         self.compress_level = int(png_compress_level)
         for p in self.planes:
             (self.out_dir / PLANE_DIRS[p]).mkdir(parents=True, exist_ok=True)
@@ -498,11 +506,21 @@ def _on_device(cam: PinholeCameras, device) -> PinholeCameras:
 
 def render_frames(model: QEDSplatterModel, cameras: Sequence[PinholeCameras], writer: FrameWriter, *, depth_unit: float,
                   near: Optional[float] = None, far: Optional[float] = None, lut=None, start_index: int = 0,
-                  timings: Optional[dict] = None) -> int:
+                  timings: Optional[dict] = None, field=None) -> int:
     """Every camera through ``get_outputs`` (eval mode, no gradients), ``present_frame`` and ``writer.submit``, numbered
     from ``start_index``; the model's training mode is restored afterwards.  Returns the number of frames.  The writer is
     left open (``close()`` it to wait for the files).  ``timings``: a dict that receives lists of (start, end) event pairs
-    under "render" and "finish" for measurements."""
+    under "render" and "finish" for measurements.  ``field`` (a semantic.SemanticField of the model's Gaussians): what the
+    "semantic" plane is rendered from; the plane without it is refused, and so is the plane under a crop box."""
+    semantic = "semantic" in writer.planes
+    if semantic:
+        if field is None:
+            raise ValueError("planes: 'semantic' needs a field (render.py --field FIELD.pt; semantic.py fits one)")
+        if model.crop_box is not None:
+            raise NotImplementedError("planes: 'semantic' under a crop box: the field's rows are the whole model's")
+        field.check_model(model)
+        from .semantic import composite_features, present_labels
+    frame_planes = tuple(p for p in writer.planes if p not in SEMANTIC_FILES)
     was_training = model.training
     model.eval()
     had_normals = bool(getattr(model.config, "output_normals", False))
@@ -511,6 +529,8 @@ def render_frames(model: QEDSplatterModel, cameras: Sequence[PinholeCameras], wr
         model.config.output_normals = True      # (asking for the plane turns the normal pass on for this run)
     if "depth_std" in writer.planes:
         model.config.output_depth_spread = True
+    if semantic:
+        model.__dict__["_score_records"] = True  # (the records and lists of every render stay for the field's pass)
     n = 0
     try:
         with torch.no_grad():
@@ -522,7 +542,13 @@ def render_frames(model: QEDSplatterModel, cameras: Sequence[PinholeCameras], wr
                 outputs = model.get_outputs(cam)
                 if ev:
                     ev[1].record()
-                frame = present_frame(outputs, depth_unit=depth_unit, near=near, far=far, lut=lut, planes=writer.planes)
+                frame = present_frame(outputs, depth_unit=depth_unit, near=near, far=far, lut=lut, planes=frame_planes)
+                if semantic:
+                    info = model.info
+                    logits = composite_features(info, 1, model.num_points, field.logits)[0]
+                    info.pop("_splats", None)
+                    info.pop("_isect_offsets_full", None)
+                    frame["semantic_label"], frame["semantic"] = present_labels(logits, outputs["accumulation"], field.palette)
                 if ev:
                     ev[2].record()
                     timings.setdefault("render", []).append((ev[0], ev[1]))
@@ -530,6 +556,7 @@ def render_frames(model: QEDSplatterModel, cameras: Sequence[PinholeCameras], wr
                 writer.submit(start_index + n, frame)
                 n += 1
     finally:
+        model.__dict__.pop("_score_records", None)
         model.train(was_training)
         model.config.output_normals = had_normals
         model.config.output_depth_spread = had_spread
@@ -547,7 +574,7 @@ def load_model(ckpt_path, device, background_color: str = "random"):
 
 
 def render_to_directory(model, cameras, out_dir, *, depth_unit, planes=PLANES, colormap_name="turbo", near=None, far=None,
-                        n_workers: int = 8, n_slots: Optional[int] = None, png_compress_level: int = 1) -> dict:
+                        n_workers: int = 8, n_slots: Optional[int] = None, png_compress_level: int = 1, field=None) -> dict:
     """``render_frames`` into a fresh ``FrameWriter`` on ``out_dir``, closed; -> {"frames", "frames_per_s",
     "bytes_written", "output"}.  ``n_slots`` None: half as many slots as workers, at least 3 -- a slot is held until the
     slowest of its frame's files is written, and three slots keep no more than eight threads busy (profiles/render.txt)."""
@@ -556,7 +583,7 @@ def render_to_directory(model, cameras, out_dir, *, depth_unit, planes=PLANES, c
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     with FrameWriter(out_dir, planes, n_slots=n_slots, n_workers=n_workers, png_compress_level=png_compress_level) as writer:
-        n = render_frames(model, cameras, writer, depth_unit=depth_unit, near=near, far=far, lut=colormap_name)
+        n = render_frames(model, cameras, writer, depth_unit=depth_unit, near=near, far=far, lut=colormap_name, field=field)
     elapsed = time.perf_counter() - t0
     return {"frames": n, "frames_per_s": n / elapsed if elapsed > 0 and n else 0.0,
             "bytes_written": writer.bytes_written, "output": str(out_dir)}
@@ -586,7 +613,9 @@ def main(argv=None) -> dict:
     ap.add_argument("--order-poses", action="store_true", help="interpolate: visit the cameras nearest-first")
     ap.add_argument("--camera-path-file", metavar="JSON", default=None)
     ap.add_argument("--planes", nargs="+", choices=ALL_PLANES, default=list(PLANES),
-                    help="'normal' (not in the default) adds normal/: the rendered normal map as 8-bit RGB")
+                    help="'normal' (not in the default) adds normal/: the rendered normal map as 8-bit RGB; 'semantic' (with "
+                         "--field) adds semantic/ and semantic_label/")
+    ap.add_argument("--field", metavar="FIELD.pt", default=None, help="a semantic field (semantic.py fit) for the 'semantic' plane")
     ap.add_argument("--colormap", choices=("turbo", "gray"), default="turbo")
     ap.add_argument("--near", type=float, default=None)
     ap.add_argument("--far", type=float, default=None, help="depth map range in model units (default: every frame's own)")
@@ -605,6 +634,8 @@ def main(argv=None) -> dict:
         ap.error(f"{a.command} needs --data (and the dataparser options of the training run)")
     if a.command == "camera-path" and not a.camera_path_file:
         ap.error("camera-path needs --camera-path-file")
+    if "semantic" in a.planes and not a.field:
+        ap.error("--planes semantic needs --field FIELD.pt")
     if not torch.cuda.is_available():
         raise SystemExit("qed_splatter_amd.render needs a GPU")
     L.load()
@@ -634,8 +665,13 @@ def main(argv=None) -> dict:
         for cam in cameras:
             cam.rescale_output_resolution(1.0 / a.downscale)
     depth_unit = float(ckpt.get("dataparser_scale", 1.0)) * a.depth_unit_scale_factor
+    field = None
+    if a.field:
+        from .semantic import SemanticField
+        field = SemanticField.load(a.field, device)
     result = render_to_directory(model, cameras, a.output, depth_unit=depth_unit, planes=tuple(a.planes),
-                                 colormap_name=a.colormap, near=a.near, far=a.far, n_workers=a.workers, n_slots=a.slots)
+                                 colormap_name=a.colormap, near=a.near, far=a.far, n_workers=a.workers, n_slots=a.slots,
+                                 field=field)
     result["command"] = a.command
     print(json.dumps(result))
     return result
